@@ -15,6 +15,13 @@ GPU (weak scaling, M * N members in all).
   python bench.py [--gpus N --steps K --warmup W] [--population P | --members M]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
+A plain run does what the headline needs: set-up, GPU preheat, W warmup steps, the K timed
+steps, then the JSON line (its roofline block holds the in-step figures of the dominant
+kernel, which the timed steps stamp themselves).  ``--full`` adds the legs that take runs
+of their own: the isolated replay of the dominant kernel and the profile-file views of the
+roofline, the world-model rollout, the env-model training and the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step left (see dump_outputs).
+
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py is its own
 launcher: the parent (which makes no GPU call) starts N rank processes with
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rank r on cuda:r over RCCL, and
@@ -410,6 +417,40 @@ def envmodel_train_leg(wl: dict, data: dict, steps: int) -> dict:
     return out
 
 
+DUMP_SAMPLE = 1 << 18        # state positions per member and array in --dump-outputs
+DUMP_BUDGET_BYTES = 48 << 20  # all sampled arrays together (the whole dump stays under 64 MB)
+
+
+def dump_outputs(pop, info: np.ndarray, out_dir: str, rank: int, world: int) -> dict:
+    """What a caller of the timed path (Population.step) holds after the last timed step,
+    as float32 ``<name>.npy`` files in ``out_dir`` (``<name>.rank<r>.npy`` with several ranks):
+
+    * ``train_info``: the last step's train info of every member, [members, len(TRAIN_INFO_KEYS)];
+    * ``params``, ``adam_m``, ``adam_v``: every member's parameters (target critic included)
+      and Adam moments at one fixed, seeded sample of positions of the flat state (the same
+      positions for every member and array), [members, sample].
+
+    Seeds, data and step counts follow from the arguments alone, so two builds run with the
+    same arguments write comparable files."""
+    from fqlpop._lib import STATE_ADAM_M, STATE_ADAM_V, STATE_PARAMS, TRAIN_INFO_KEYS
+    os.makedirs(out_dir, exist_ok=True)
+    k = max(1, min(pop.state_size, DUMP_SAMPLE, DUMP_BUDGET_BYTES // (3 * 4 * pop.n)))
+    idx = np.sort(np.random.default_rng(0).choice(pop.state_size, size=k, replace=False))
+    arrays = {"train_info": np.ascontiguousarray(info[:, :len(TRAIN_INFO_KEYS)], dtype=np.float32)}
+    for name, which in (("params", STATE_PARAMS), ("adam_m", STATE_ADAM_M), ("adam_v", STATE_ADAM_V)):
+        arrays[name] = np.stack([pop.get_flat(m, which)[idx] for m in range(pop.n)])
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    return {"dir": out_dir, "arrays": {name + suffix: list(a.shape) for name, a in arrays.items()},
+            "bytes": int(sum(a.nbytes for a in arrays.values())), "state_size": pop.state_size,
+            "sample": "numpy default_rng(0).choice(state_size, size, replace=False), sorted"}
+
+
+def _round(x, n):
+    return None if x is None else round(x, n)
+
+
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
         so.bind(("127.0.0.1", 0))
@@ -455,6 +496,13 @@ def main(argv=None):
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cube")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: isolated replay of the dominant kernel and "
+                         "the profile-file roofline views, world-model rollout, env-model training, CPU "
+                         "baseline (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's train info and a seeded sample of "
+                         "every member's parameters and Adam moments as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=100)
@@ -630,6 +678,7 @@ def main(argv=None):
     pop.set_probe(False)
     info = pop.read_info_array()
     finite = bool(np.all(np.isfinite(info[:, :13])))
+    dumped = dump_outputs(pop, info, args.dump_outputs, rank, world) if args.dump_outputs else None
 
     member_steps = n_total * args.steps
     value = member_steps / el
@@ -638,12 +687,17 @@ def main(argv=None):
     # dominant kernel of the step (all members, one launch): the persistent
     # Euler flow (H = 512) or else the Euler hidden-layer GEMM
     kname, kflops, kbytes = pop.dominant_kernel_info()
-    iso_us, _ = pop.time_dominant_kernel(args.kernel_iters)  # the same launch replayed alone
-    _, _, (cc_event_us, cc_stamp_us) = pop.read_probe()     # stamp clock vs HIP events, one launch
+    iso_us, timing_check = None, "not run (--full replays one isolated launch under HIP events)"
+    if args.full:
+        iso_us, _ = pop.time_dominant_kernel(args.kernel_iters)  # the same launch replayed alone
+        _, _, (cc_event_us, cc_stamp_us) = pop.read_probe()     # stamp clock vs HIP events, one launch
+        timing_check = f"HIP events {cc_event_us:.2f} us vs stamps {cc_stamp_us:.2f} us"
     launch_us = probe_us if probe_n else iso_us
-    achieved = kflops / (launch_us * 1e-6) / 1e12
+    achieved = kflops / (launch_us * 1e-6) / 1e12 if launch_us else None
+    frac = achieved / MI355X_FP32_MFMA_PEAK_TFLOPS if achieved is not None else None
+    frac_iso = kflops / (iso_us * 1e-6) / 1e12 / MI355X_FP32_MFMA_PEAK_TFLOPS if iso_us else None
     traffic, traffic_src = None, None
-    if os.path.exists(args.pmc_json):
+    if args.full and os.path.exists(args.pmc_json):
         with open(args.pmc_json) as f:
             pmc = json.load(f)
         # the counters were collected on one workload's launch (pmc_dominant.json "workload")
@@ -656,7 +710,7 @@ def main(argv=None):
     # the roofline's other views of the same kernel: alone (live replays
     # above), serial-stream launch and in-step top kernel by time (rocprofv3, kernel_times.json)
     serial_view, top_view = None, None
-    if os.path.exists(args.kernel_times_json):
+    if args.full and os.path.exists(args.kernel_times_json):
         with open(args.kernel_times_json) as f:
             kt = json.load(f)
         if kt.get("members") == pop.n and kt.get("workload", "cube") == args.workload:
@@ -720,12 +774,12 @@ def main(argv=None):
             "kernel": kname + (" (Euler flow steps 1..9 of all members: 16-column blocks, weights streamed, "
                                "activations LDS-resident)" if kname == "euler_flow_kernel" else
                                " (Euler-flow hidden layer y' = gelu(W^T x' + b), one launch per layer)"),
-            "achieved": round(achieved, 3),
+            "achieved": _round(achieved, 3),
             "peak": MI355X_FP32_MFMA_PEAK_TFLOPS,
             "unit": "TFLOP/s",
-            "frac": round(achieved / MI355X_FP32_MFMA_PEAK_TFLOPS, 4),
-            "frac_in_step": round(achieved / MI355X_FP32_MFMA_PEAK_TFLOPS, 4),
-            "frac_isolated": round(kflops / (iso_us * 1e-6) / 1e12 / MI355X_FP32_MFMA_PEAK_TFLOPS, 4),
+            "frac": _round(frac, 4),
+            "frac_in_step": _round(frac, 4),
+            "frac_isolated": _round(frac_iso, 4),
             "frac_serial_stream": serial_view,
             "step_frac": round(step_frac, 4),
             "in_step_top_kernel": top_view,
@@ -733,11 +787,11 @@ def main(argv=None):
                          "sharing the CUs with the other streams; frac_isolated: the same launch replayed alone "
                          "(this run); frac_serial_stream: its launch in a serial-stream step (rocprofv3, "
                          "kernel_times.json); step_frac: the whole step's flops / wall time / peak",
-            "avg_launch_us": round(launch_us, 3),
+            "avg_launch_us": _round(launch_us, 3),
             "launches_timed": probe_n,
-            "isolated_launch_us": round(iso_us, 3),
+            "isolated_launch_us": _round(iso_us, 3),
             "timing": "in-step launches timed by per-block s_memrealtime stamps (100 MHz); cross-check on one "
-                      f"isolated launch: HIP events {cc_event_us:.2f} us vs stamps {cc_stamp_us:.2f} us",
+                      f"isolated launch: {timing_check}",
             "flops_per_launch": kflops,
             "algorithmic_bytes_per_launch": kbytes,
             "traffic": traffic,
@@ -754,11 +808,14 @@ def main(argv=None):
     }
     if scratch is not None:
         scratch.close()
-    if args.eval_envs > 0:
+    result["full"] = bool(args.full)
+    if dumped is not None:
+        result["dump_outputs"] = dumped
+    if args.full and args.eval_envs > 0:
         result["eval_rollout"] = eval_rollout_leg(pop, wl, args.eval_envs, args.eval_steps, dev)
-    if args.envmodel_train_steps > 0 and rank == 0:
+    if args.full and args.envmodel_train_steps > 0 and rank == 0:
         result["envmodel_train"] = envmodel_train_leg(wl, data, args.envmodel_train_steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log(f"[rank 0] cpu baseline ({args.cpu_baseline_seconds:.0f} s budget)")
         result["cpu_baseline"] = cpu_baseline(wl, data, args.cpu_baseline_seconds)
     if fq_env:

@@ -16,7 +16,7 @@ T=$R/flow-q-learning_amd/csrc/tools
 mkdir -p "$O"
 cd "$R"
 s0=$(date +%s.%N)
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/driver_bench.json" 2> "$O/driver_bench.err" \
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/driver_bench.json" 2> "$O/driver_bench.err" \
     || { echo "driver bench failed"; tail -5 "$O/driver_bench.err"; exit 1; }
 s1=$(date +%s.%N)
 python3 -c "print(f'wall {${s1} - ${s0}:.2f} s')" > "$O/driver_bench.wall"

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--rows", "20000",
-           "--no-cpu-baseline", "--eval-envs", "2", "--eval-steps", "20", "--envmodel-train-steps", "5",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--rows",
+           "20000", "--no-cpu-baseline", "--eval-envs", "2", "--eval-steps", "20", "--envmodel-train-steps", "5",
            "--kernel-iters", "2", "--preheat-ms", "20"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -21,8 +21,10 @@ def test_bench_json_contract():
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
-              "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "preheat"):
+              "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "preheat",
+              "eval_rollout", "envmodel_train"):
         assert k in d, k
+    assert d["full"] is True and d["roofline"]["isolated_launch_us"] > 0
     assert d["steps"] == 4 and d["warmup"] == 2 and d["n_gpus"] == 1
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         assert d["metric"] == json.load(f)["metric"]  # the north-star metric, verbatim
@@ -90,6 +92,42 @@ def test_bench_population_is_sharded_over_ranks():
     assert d["config"]["members_this_rank"] == 3 and d["config"]["members_per_gpu"] == 3
     assert "over 6-" in d["metric"]
     assert abs(d["value"] - 6 * 1000.0 / d["ms_per_step"]) <= 1e-3 * d["value"] + 1.0
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the run stops at the headline: no isolated replay, rollout, env-model
+    or CPU leg, while the headline keys and the in-step roofline figures stay.
+    --dump-outputs writes float32 arrays of the last timed step, and a second run with the
+    same arguments writes the same bits."""
+    import numpy as np
+    from fqlpop._lib import TRAIN_INFO_KEYS
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "20000", "--population", "2",
+                    "--preheat-ms", "20", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1
+        assert d["cpu_baseline"] is None and "eval_rollout" not in d and "envmodel_train" not in d
+        rf = d["roofline"]
+        assert rf["isolated_launch_us"] is None and rf["frac_isolated"] is None and rf["traffic"] is None
+        assert rf["launches_timed"] == 3 and rf["avg_launch_us"] > 0
+        assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) <= 1e-3 * d["value"] + 1.0
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["adam_m.npy", "adam_v.npy", "params.npy", "train_info.npy"]
+        arrs = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.all(np.isfinite(a)) for a in arrs.values())
+        assert arrs["train_info"].shape == (2, len(TRAIN_INFO_KEYS))
+        k = arrs["params"].shape[1]
+        assert arrs["params"].shape == arrs["adam_m"].shape == arrs["adam_v"].shape == (2, k) and k > 1000
+        assert sum(a.nbytes for a in arrs.values()) <= 64e6 and d["dump_outputs"]["bytes"] <= 64e6
+        assert np.any(arrs["adam_v"] > 0) and np.any(arrs["params"][0] != arrs["params"][1])
+        dumps.append(arrs)
+    for k, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][k], err_msg=k)
 
 
 def test_two_hardware_queues_smoke_and_bench():
