@@ -200,6 +200,41 @@ struct Graphs {
     int nz = -1;
 };
 
+// A slot-strided workspace buffer (fqlpop::alloc): the pointer and the per-slot stride it
+// was allocated for, so no use restates the buffer's size.
+struct Buf {
+    float* p = nullptr;
+    long long ss = 0;
+    TRef ref(long long sy = 0) const { return TRef{p, ss, sy}; }
+    TRef cols(long long off, long long sy = 0) const { return TRef{p + off, ss, sy}; }  // from column `off`
+};
+
+// One network as the step runs it (built once by fqlpop_create): the layout, the parameter
+// arena it reads, its input and per-layer activation buffers with their leading dimensions
+// and ensemble strides, and the identity of its whole-network launches (optimiser index,
+// split launch sites, FQLPOP_SKIP bits).  The target critic and the per-layer Euler flow are
+// forward-only views of the critic's / BC actor's layout with their own buffers.
+struct Net {
+    const NetLayout* lay = nullptr;
+    float* const* arena = nullptr;  // &params (the current buffer of the pair) or &target
+    long long arena_ss = 0;         // its slot stride (P or PT)
+    int ni = 0;                     // 0 critic, 1 bc, 2 os: optimiser chunks, W^T copies
+    const Buf* X = nullptr;         // input [K0][ld]
+    int ld = 0;                     // leading dim of X, U, G, MU, RS
+    int ld_d = 0, ld_o = 0;         // leading dims of DU / DH / C1 / C2 and of the head gradient
+    long long sy = 0, st_sy = 0;    // ensemble strides of U / G and of MU / RS (0: one member)
+    bool keep_u = true;             // the per-layer forward keeps u beside gelu(u) (backward / LN)
+    bool dominant = false;          // its per-layer hidden GEMMs are the probed dominant kernel
+    std::vector<Buf> U, G, MU, RS, DU;
+    Buf DH, C1, C2, part;
+    int fwd_site = -1, bwd_site = -1;  // SITE_*
+    int skip_fwd = 0, skip_bwd = 0;    // FQLPOP_SKIP bits
+    TRef par(long long off) const { return tref(*arena + lay->off + off, arena_ss, lay->ens_size); }
+    TRef act(const Buf& b, long long coff = 0) const { return b.cols(coff, sy); }
+    TRef stat(const Buf& b, long long coff = 0) const { return b.cols(coff, st_sy); }
+    TRef grad(const Buf& b) const { return b.ref((long long)lay->H * ld_d); }  // DU / DH
+};
+
 }  // namespace
 
 struct fqlpop {
@@ -219,7 +254,7 @@ struct fqlpop {
     // after enqueueing a train step (flip_params).  So no kernel of a step has
     // to wait for another's last read of a parameter before updating it.
     float* params_buf[2] = {nullptr, nullptr};
-    float* paramsT_buf[2] = {nullptr, nullptr};
+    Buf paramsT_buf[2];
     int cur = 0;
     float *params = nullptr, *params_nx = nullptr;
     float *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr, *target = nullptr;
@@ -256,15 +291,12 @@ struct fqlpop {
 
     // activations (slot-strided)
     std::vector<float*> allocs;
-    float *os_in, *bc_in, *eu_in, *cr_in, *tg_in;
-    float* cr_in_buf[2] = {nullptr, nullptr};  // cr_in per parameter buffer (cr_in = cr_in_buf[cur])
-    std::vector<float*> os_u, os_g, bc_u, bc_g, eu_g, cr_u, cr_h, cr_mu, cr_rs, tg_u, tg_h, tg_mu, tg_rs;
-    std::vector<float*> cr_du, bc_du, os_du;
-    float *cr_dh, *bc_dh, *os_dh, *cr_c1, *cr_c2;
-    float *q, *qt, *dq, *vpred, *dv, *act_t, *x0_t, *rew_t, *mask_t, *apiraw, *aflow, *amet, *da, *dout_os;
-    float *info, *vinfo;
-    float *inj_batch = nullptr, *inj_noise = nullptr;
-    long long inj_bs = 0, inj_ns = 0;
+    Buf os_in, bc_in, eu_in, cr_in, tg_in;
+    Buf cr_in_buf[2];  // cr_in per parameter buffer (cr_in = cr_in_buf[cur])
+    Net n_cr, n_tg, n_bc, n_eu, n_os;  // critic, target critic, BC flow, per-layer Euler flow, one-step actor
+    Buf q, qt, dq, vpred, dv, act_t, x0_t, rew_t, mask_t, apiraw, aflow, amet, da, dout_os;
+    Buf info, vinfo;
+    Buf inj_batch, inj_noise;
 
     hipStream_t sM = nullptr, sF = nullptr, sB = nullptr, sX = nullptr;  // sX: small-population schedule
     hipEvent_t ev_sample, ev_bcfwd, ev_bcloss, ev_flow, ev_bdone;
@@ -294,11 +326,10 @@ struct fqlpop {
     bool split_ok = false;
     bool stream_fwd = false;       // whole-network forward launches (stream_fwd_kernel)
     bool stream_bwd = false;       // whole-network dX chains (stream_bwd_kernel)
-    float *part_cr = nullptr, *part_bc = nullptr, *part_os = nullptr;  // stream_bwd column-sum partials
     // W_l^T copies of the hidden kernels (l = 1..L-1) for stream_bwd, per slot:
     // [critic e=0..E-1 | bc | os] x (L-1) x H x H; refreshed after each Adam
-    float *paramsT = nullptr, *paramsT_nx = nullptr;   // current / next buffer (see params)
-    long long PTT = 0, wt_net_off[3] = {0, 0, 0};
+    Buf paramsT, paramsT_nx;   // current / next buffer (see params)
+    long long wt_net_off[3] = {0, 0, 0};
     bool wt_dirty = true;          // params changed on the host side: re-transpose before the next step
     // world-model rollout evaluator (fqlpop_set_env_model / fqlpop_rollout)
     fqlpop_envmodel_config em{};
@@ -331,12 +362,14 @@ struct fqlpop {
     double clock_check_event_us = 0.0, clock_check_stamp_us = 0.0;
     std::map<long long, Graphs> graphs;  // key: mode, active count, probe set, current buffer
 
-    float* alloc(long long per_slot) {
+    // `per_slot` floats per slot, zeroed; `stride` is the slot stride its users address it by
+    // (the five input buffers: allocated rounded up, strided by their unrounded size)
+    Buf alloc(long long per_slot, long long stride = -1) {
         float* p = nullptr;
         HIPCHK(hipMalloc(&p, sizeof(float) * std::max<long long>(1, per_slot * n)));
         HIPCHK(hipMemset(p, 0, sizeof(float) * std::max<long long>(1, per_slot * n)));
         allocs.push_back(p);
-        return p;
+        return Buf{p, stride < 0 ? per_slot : stride};
     }
 };
 
@@ -526,18 +559,13 @@ void init_member(fqlpop* h, int slot, uint64_t seed) {
 
 // ------------------------------------------------------------- DAG helpers
 // the network whose backward the phase probe stamps (diagnostic builds): FQLPOP_PHASE_NET =
-// bc / os, else the critic
-const NetLayout* phase_net(const fqlpop* h) {
+// bc / os, else the critic (Net::ni)
+int phase_net() {
     const char* v = diag_env("FQLPOP_PHASE_NET");
-    if (v != nullptr && std::strcmp(v, "bc") == 0) return &h->bc;
-    if (v != nullptr && std::strcmp(v, "os") == 0) return &h->os;
-    return &h->critic;
+    if (v != nullptr && std::strcmp(v, "bc") == 0) return 1;
+    if (v != nullptr && std::strcmp(v, "os") == 0) return 2;
+    return 0;
 }
-
-struct Ctx {
-    fqlpop* h;
-    int nz;
-};
 
 TRef pref(fqlpop* h, float* arena, const NetLayout& N, long long off) {
     return tref(arena + N.off + off, h->P, N.ens_size);
@@ -593,7 +621,7 @@ constexpr long long split_cap(int site) {
     return (site == SITE_BCF || site == SITE_TGT || site == SITE_CRF || site == SITE_OSB) ? kSplitMaxClustersSide
                                                                                         : kSplitMaxClusters;
 }
-constexpr long long kSplitMaxBlocks = 256;       // one block per CU (see split_factor)
+constexpr long long kSplitMaxBlocks = 256;       // one block per CU (see split_factor_opts)
 
 // Blocks per 16-column tile of a split launch (1 = the unsplit kernel).  Only where the
 // unsplit kernel leaves CUs idle (<= split_cap tiles); the most of
@@ -624,19 +652,22 @@ int split_factor_opts(const EngineOptions& o, bool split_ok, int site, long long
     }
     return 1;
 }
-int split_factor(const fqlpop* h, int site, long long clusters, bool min4, long long max_blocks = kSplitMaxBlocks) {
-    return split_factor_opts(h->opt, h->split_ok, site, clusters, min4, max_blocks);
-}
-
 // The split plan of a step over nz members: F per launch site (1 = unsplit) and whether the
-// 4th-stream schedule runs, from the shapes and engine options alone (no GPU).  The
-// launches compute their F at the call sites (stream_fwd, euler_split, bwd_split) and check it
-// against this plan, so the plan that fqlpop_split_plan reports is the one that runs.
+// 4th-stream schedule runs, from the shapes and engine options alone (no GPU).  enqueue
+// computes it once per step and every launch reads its F from it (Ctx::plan), so the plan
+// that fqlpop_split_plan reports is the one that runs.  The BC backward (sB) is outside the
+// plan: always unsplit.
 struct SplitShape {
     int H, L, A, B, E, K0bc, K0os, K0cr;
     bool critic_ln, stream_fwd, stream_bwd, fused_adam, euler_fused, multi_stream;
 };
-void split_plan(const EngineOptions& o, const SplitShape& d, int nz, int F[SITE_N], bool* small) {
+struct SplitPlan {
+    int F[SITE_N];
+    bool small;
+};
+SplitPlan split_plan(const EngineOptions& o, const SplitShape& d, int nz) {
+    SplitPlan p{};
+    int* F = p.F;
     const bool ok = d.stream_fwd && o.split != 0;
     const int B = d.B, B2 = 2 * B, B3 = 3 * B, T = B / 16;
     auto fwd = [&](int site, int K0, int nout, int M, long long clusters, bool min4) {
@@ -645,17 +676,18 @@ void split_plan(const EngineOptions& o, const SplitShape& d, int nz, int F[SITE_
     };
     fwd(SITE_EULER, d.K0bc, d.A, B, (long long)T * nz, true);
     if (!d.euler_fused) F[SITE_EULER] = 1;
-    *small = o.small_sched && d.multi_stream && d.stream_fwd && d.stream_bwd && d.fused_adam &&
-             (long long)T * nz <= kSmallSchedTiles;
+    p.small = o.small_sched && d.multi_stream && d.stream_fwd && d.stream_bwd && d.fused_adam &&
+              (long long)T * nz <= kSmallSchedTiles;
     fwd(SITE_BCF, d.K0bc, d.A, B2, (long long)(B2 / 16) * nz, false);
     fwd(SITE_OSF, d.K0os, d.A, B3, (long long)(B3 / 16) * nz, false);
     fwd(SITE_TGT, d.K0cr, 1, B, (long long)T * d.E * nz, false);
     fwd(SITE_CRF, d.K0cr, 1, B2, (long long)(B2 / 16) * d.E * nz, false);
+    // (the critic's LN backward: its 2-block form would spill, so 4 or 8 blocks per tile)
     auto bwd = [&](int site, int nout, int M, int Mg, long long clusters, bool min4) {
         F[site] = d.stream_bwd && split_bwd_supported(d.H, d.L, nout, M, Mg)
                       ? split_factor_opts(o, ok, site, clusters, min4, kSplitMaxBlocks) : 1;
     };
-    if (*small) {
+    if (p.small) {
         bwd(SITE_CRB, 1, B, 0, (long long)T * d.E * nz, d.critic_ln);  // the Q-loss columns
         bwd(SITE_CRB2, 1, B, B, (long long)T * d.E * nz, d.critic_ln);  // the TD columns (sX)
     } else {
@@ -663,19 +695,21 @@ void split_plan(const EngineOptions& o, const SplitShape& d, int nz, int F[SITE_
         F[SITE_CRB2] = 1;
     }
     bwd(SITE_OSB, d.A, B, B, (long long)T * nz, false);
+    return p;
 }
-SplitShape split_shape(const fqlpop* h) {
-    return SplitShape{h->H, h->L, h->A, h->B, h->E, h->bc.in_dim, h->os.in_dim, h->critic.in_dim, h->critic.ln,
-                      h->stream_fwd, h->stream_bwd, h->fused_adam, h->euler_fused, h->sX != h->sM};
+SplitPlan split_plan(const fqlpop* h, int nz) {
+    const SplitShape d{h->H, h->L, h->A, h->B, h->E, h->bc.in_dim, h->os.in_dim, h->critic.in_dim, h->critic.ln,
+                       h->stream_fwd, h->stream_bwd, h->fused_adam, h->euler_fused, h->sX != h->sM};
+    return split_plan(h->opt, d, nz);
 }
-// the call site's F against the plan (a divergence would make fqlpop_split_plan report a
-// schedule that does not run)
-void check_plan(const fqlpop* h, int site, int nz, int F) {
-    int plan[SITE_N];
-    bool small = false;
-    split_plan(h->opt, split_shape(h), nz, plan, &small);
-    ARGCHK(plan[site] == F, "split launch differs from the split plan");
-}
+
+// One step being enqueued over the nz active members, with its split plan.
+struct Ctx {
+    fqlpop* h;
+    int nz;
+    SplitPlan plan;
+};
+Ctx step_ctx(fqlpop* h) { return Ctx{h, h->nz, split_plan(h, h->nz)}; }
 
 // The site's synchronisation state for one launch over `clusters` tiles.  Its counters (per
 // cluster, then the ticket and the exit counter) are zero at every launch: zeroed at
@@ -687,38 +721,29 @@ SplitSync split_prep(fqlpop* h, int site, long long clusters, hipStream_t) {
     return SplitSync{st.xch, st.cnt, st.gen, h->split_err};
 }
 
-// Blocks per tile of a streamed backward launch (1 = unsplit): the critic (LN: its 2-block
-// form would spill, so 4 or 8, up to 2 blocks per CU: 4 x 128 tiles for a 2-member
-// population) and the one-step actor on sM; never the BC actor on sB.
-int bwd_split(const fqlpop* h, int site, const NetLayout& N, int M, int Mg, int nz) {
-    if (&N == &h->bc || !split_bwd_supported(N.H, N.L, N.out_dim, M, Mg)) return 1;
-    return split_factor(h, site, (long long)(M / 16) * N.E * nz, N.ln, kSplitMaxBlocks);
-}
-
-// Forward of the hidden stack of `N` over `M` columns of input X (ld = ldx).
-// U[l]/G[l]: pre-activation and layer output buffers (ld = ldx).  store_u:
-// keep u (needed by backward / LN); otherwise G[l] = gelu(u) directly.
-void fwd_hidden(const Ctx& c, hipStream_t s, const NetLayout& N, TRef X, int ldx, int M,
-                const std::vector<float*>& U, const std::vector<float*>& G, long long act_sy,
-                const std::vector<float*>* MU, const std::vector<float*>* RS, long long st_sy,
-                bool store_u, bool euler = false) {
+// Per-layer forward of the hidden stack of `n` over all ld columns of its input, into U / G
+// (pre-activations and layer outputs; without keep_u, G[l] = gelu(u) directly).
+void fwd_hidden(const Ctx& c, hipStream_t s, const Net& n) {
     fqlpop* h = c.h;
+    const NetLayout& N = *n.lay;
     for (int l = 0; l < N.L; ++l) {
         GemmArgs g{};
-        g.A = pref(h, h->params, N, N.W[l]);
-        g.B = l == 0 ? X : tref(G[l - 1], (long long)N.H * ldx * N.E, act_sy);
+        g.A = n.par(N.W[l]);
+        g.B = l == 0 ? n.X->ref() : n.act(n.G[l - 1]);
         if (N.ln) {
-            g.C = tref(U[l], (long long)N.H * ldx * N.E, act_sy);
+            g.C = n.act(n.U[l]);
+        } else if (n.keep_u) {
+            g.C = n.act(n.U[l]);
+            g.C2 = n.act(n.G[l]);
         } else {
-            g.C = tref(store_u ? U[l] : G[l], (long long)N.H * ldx * N.E, act_sy);
-            g.C2 = tref(G[l], (long long)N.H * ldx * N.E, act_sy);
+            g.C = n.act(n.G[l]);
         }
-        g.bias = pref(h, h->params, N, N.b[l]);
-        g.M = N.H; g.N = M; g.K = N.kdim(l);
-        g.lda = N.H; g.ldb = ldx; g.ldc = ldx;
+        g.bias = n.par(N.b[l]);
+        g.M = N.H; g.N = n.ld; g.K = N.kdim(l);
+        g.lda = N.H; g.ldb = n.ld; g.ldc = n.ld;
         g.ny = N.E; g.nz = c.nz; g.slots = h->slots;
-        const int epi = N.ln ? EPI_BIAS : (store_u ? EPI_BIAS_GELU2 : EPI_BIAS_GELU);
-        if (euler && l >= 1 && epi == EPI_BIAS_GELU && g.M % 64 == 0 && g.N % 64 == 0) {
+        const int epi = N.ln ? EPI_BIAS : (n.keep_u ? EPI_BIAS_GELU2 : EPI_BIAS_GELU);
+        if (n.dominant && l >= 1 && epi == EPI_BIAS_GELU && g.M % 64 == 0 && g.N % 64 == 0) {
             // the dominant kernel: its own symbol, optionally with in-kernel timing stamps
             if (h->probe_set >= 0 && h->probe_idx < h->probe_pairs)
                 g.probe = h->probe_slots + 2 * h->probe_blocks * ((long long)h->probe_set * h->probe_pairs + h->probe_idx++);
@@ -728,94 +753,90 @@ void fwd_hidden(const Ctx& c, hipStream_t s, const NetLayout& N, TRef X, int ldx
         }
         if (N.ln) {
             LnArgs a{};
-            a.u = tref(U[l], (long long)N.H * ldx * N.E, act_sy);
-            a.h = tref(G[l], (long long)N.H * ldx * N.E, act_sy);
-            a.mu = tref((*MU)[l], (long long)ldx * N.E, st_sy);
-            a.rstd = tref((*RS)[l], (long long)ldx * N.E, st_sy);
-            a.gamma = pref(h, h->params, N, N.gam[l]);
-            a.beta = pref(h, h->params, N, N.bet[l]);
-            a.H = N.H; a.M = M; a.ld = ldx; a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
+            a.u = n.act(n.U[l]);
+            a.h = n.act(n.G[l]);
+            a.mu = n.stat(n.MU[l]);
+            a.rstd = n.stat(n.RS[l]);
+            a.gamma = n.par(N.gam[l]);
+            a.beta = n.par(N.bet[l]);
+            a.H = N.H; a.M = n.ld; a.ld = n.ld; a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
             launch_ln_gelu_fwd(a, s);
         }
     }
 }
 
-HeadArgs head_args(const Ctx& c, const NetLayout& N, float* Glast, int ldx, int M, long long act_sy) {
+// The head of `n` over all ld columns of its last layer output (the caller adds the outputs).
+HeadArgs head_args(const Ctx& c, const Net& n) {
     fqlpop* h = c.h;
+    const NetLayout& N = *n.lay;
     HeadArgs a{};
-    a.h = tref(Glast, (long long)N.H * ldx * N.E, act_sy);
-    a.W = pref(h, h->params, N, N.W[N.L]);
-    a.b = pref(h, h->params, N, N.b[N.L]);
-    a.H = N.H; a.M = M; a.ld = ldx; a.nout = N.out_dim;
+    a.h = n.act(n.G[N.L - 1]);
+    a.W = n.par(N.W[N.L]);
+    a.b = n.par(N.b[N.L]);
+    a.H = N.H; a.M = n.ld; a.ld = n.ld; a.nout = N.out_dim;
     a.B = h->B; a.D = h->D;
     a.steps_f = (float)h->S;
     a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
     return a;
 }
 
-// Backward of one network from its head-output gradient `dout` ([nout][ld_o]).
-// Activations (U, G, X0) are read at column offset `coff` with leading dim
-// `ld`; M columns are back-propagated, of which the first Mg feed the
-// parameter gradients.
-void bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, int ld_o, TRef X0, int ld,
-             long long coff, int M, int Mg, const std::vector<float*>& U, const std::vector<float*>& G,
-             long long act_sy, const std::vector<float*>* MU, const std::vector<float*>* RS, long long st_sy,
-             const std::vector<float*>& DU, float* DH, float* C1, float* C2, int ld_d, hipStream_t sw) {
+// Columns of one backward: activations and input are read from column `coff`; M columns
+// are back-propagated, of which the first Mg feed the parameter gradients.  site: the
+// launch site where it is not the net's own (the critic's TD columns on the 4th stream).
+struct BwdCols {
+    int coff, M, Mg;
+    int site = -1;
+};
+
+// Per-layer backward of `n` on `s` from its head-output gradient `dout` ([nout][ld_o]).
+void bwd_net(const Ctx& c, hipStream_t s, const Net& n, const BwdCols& k, TRef dout) {
     fqlpop* h = c.h;
-    const long long act_ss = (long long)N.H * ld * N.E;
-    const long long d_ss = (long long)N.H * ld_d * N.E, d_sy = (long long)N.H * ld_d;
-    auto act = [&](float* p) { return tref(p + coff, act_ss, act_sy); };
+    const NetLayout& N = *n.lay;
     for (int l = N.L - 1; l >= 0; --l) {
         const bool head = (l == N.L - 1);
         BwdArgs b{};
         if (head) {
             b.dout = dout;
-            b.W5 = pref(h, h->params, N, N.W[N.L]);
-            b.x_head = act(G[l]);
+            b.W5 = n.par(N.W[N.L]);
+            b.x_head = n.act(n.G[l], k.coff);
             b.g_W5 = pref(h, h->grads, N, N.W[N.L]);
         } else {
-            b.dh = tref(DH, d_ss, d_sy);
+            b.dh = n.grad(n.DH);
         }
-        b.u = act(U[l]);
+        b.u = n.act(n.U[l], k.coff);
         if (N.ln) {
-            b.mu = tref((*MU)[l] + coff, (long long)ld * N.E, st_sy);
-            b.rstd = tref((*RS)[l] + coff, (long long)ld * N.E, st_sy);
-            b.gamma = pref(h, h->params, N, N.gam[l]);
-            b.c1 = tref(C1, (long long)ld_d * N.E, ld_d);
-            b.c2 = tref(C2, (long long)ld_d * N.E, ld_d);
+            b.mu = n.stat(n.MU[l], k.coff);
+            b.rstd = n.stat(n.RS[l], k.coff);
+            b.gamma = n.par(N.gam[l]);
+            b.c1 = n.C1.ref(n.ld_d);
+            b.c2 = n.C2.ref(n.ld_d);
             b.g_gamma = pref(h, h->grads, N, N.gam[l]);
             b.g_beta = pref(h, h->grads, N, N.bet[l]);
         }
-        b.du = tref(DU[l], d_ss, d_sy);
+        b.du = n.grad(n.DU[l]);
         b.g_b = pref(h, h->grads, N, N.b[l]);
-        b.H = N.H; b.M = M; b.Mg = Mg; b.ld = ld; b.ld_d = ld_d; b.ld_o = ld_o; b.nout = N.out_dim;
+        b.H = N.H; b.M = k.M; b.Mg = k.Mg; b.ld = n.ld; b.ld_d = n.ld_d; b.ld_o = n.ld_o; b.nout = N.out_dim;
         b.ny = N.E; b.nz = c.nz; b.slots = h->slots;
         if (N.ln) launch_bwd_rowstats(head, b, s);
         launch_bwd_cols(head, N.ln, b, s);
 
-        // dW_l = X_l^T du_l over the first Mg columns, on the dW stream `sw`
-        // (off the dX chain's critical path)
-        if (sw != s) {
-            hipEvent_t ev = next_event(h);
-            HIPCHK(hipEventRecord(ev, s));
-            HIPCHK(hipStreamWaitEvent(sw, ev, 0));
-        }
+        // dW_l = X_l^T du_l over the first Mg columns
         GemmArgs gw{};
-        gw.A = l == 0 ? X0 : act(G[l - 1]);
-        gw.B = tref(DU[l], d_ss, d_sy);
+        gw.A = l == 0 ? n.X->cols(k.coff) : n.act(n.G[l - 1], k.coff);
+        gw.B = n.grad(n.DU[l]);
         gw.C = pref(h, h->grads, N, N.W[l]);
-        gw.M = N.kdim(l); gw.N = N.H; gw.K = Mg;
-        gw.lda = ld; gw.ldb = ld_d; gw.ldc = N.H;
+        gw.M = N.kdim(l); gw.N = N.H; gw.K = k.Mg;
+        gw.lda = n.ld; gw.ldb = n.ld_d; gw.ldc = N.H;
         gw.ny = N.E; gw.nz = c.nz; gw.slots = h->slots;
-        gemm(LAYOUT_DW, EPI_STORE, gw, sw);
+        gemm(LAYOUT_DW, EPI_STORE, gw, s);
         if (l > 0) {
             // dh_{l-1} = W_l du_l  (all M columns)
             GemmArgs gx{};
-            gx.A = pref(h, h->params, N, N.W[l]);
-            gx.B = tref(DU[l], d_ss, d_sy);
-            gx.C = tref(DH, d_ss, d_sy);
-            gx.M = N.H; gx.N = M; gx.K = N.H;
-            gx.lda = N.H; gx.ldb = ld_d; gx.ldc = ld_d;
+            gx.A = n.par(N.W[l]);
+            gx.B = n.grad(n.DU[l]);
+            gx.C = n.grad(n.DH);
+            gx.M = N.H; gx.N = k.M; gx.K = N.H;
+            gx.lda = N.H; gx.ldb = n.ld_d; gx.ldc = n.ld_d;
             gx.ny = N.E; gx.nz = c.nz; gx.slots = h->slots;
             gemm(LAYOUT_DX, EPI_STORE, gx, s);
         }
@@ -823,29 +844,23 @@ void bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, int ld_
 }
 
 AdamArgs adam_args(const Ctx& c, int ni);
-
-// Whole-network backward of `N` (stream_bwd_kernel) on `s`: dX chain from the
-// head gradient `dout` ([nout][ld_o]) down to du_0, LayerNorm / GELU' fused,
-// parameter-grad column sums as per-tile partials.  Then, on `sw`, the
-// partial reduction (bias / LN / head-kernel grads) and the dW_l GEMMs.
-// Activations are read at column offset `coff` (ld `ld`), du_l written with
-// ld `ld_d`; M columns are back-propagated, the first Mg feed the grads.
 int skip_mask();
 
-void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, int ld_o, TRef X0, int ld,
-                    long long coff, int M, int Mg, const std::vector<float*>& U, const std::vector<float*>& G,
-                    long long act_sy, const std::vector<float*>* MU, const std::vector<float*>* RS, long long st_sy,
-                    const std::vector<float*>& DU, int ld_d, float* part, hipStream_t sw,
+// Whole-network backward of `n` (stream_bwd_kernel) on `s`: dX chain from the
+// head gradient `dout` ([nout][ld_o]) down to du_0, LayerNorm / GELU' fused,
+// parameter-grad column sums as per-tile partials.  Then, on `sw`, the
+// partial reduction (bias / LN / head-kernel grads) and the dW_l GEMMs: now, or
+// by the caller later (`defer`).  `ig`: the critic's dQ/da in the layer-0 epilogue.
+void stream_bwd_net(const Ctx& c, hipStream_t s, const Net& n, const BwdCols& k, TRef dout, hipStream_t sw,
                     const InGradArgs* ig = nullptr, std::function<void()>* defer = nullptr) {
     fqlpop* h = c.h;
-    const long long act_ss = (long long)N.H * ld * N.E;
-    const long long d_ss = (long long)N.H * ld_d * N.E, d_sy = (long long)N.H * ld_d;
+    const NetLayout& N = *n.lay;
+    const int M = k.M, Mg = k.Mg;
     StreamBwdArgs a{};
-    a.params = h->params + N.off;
-    a.P = h->P; a.ens = N.ens_size;
-    const int ni = &N == &h->critic ? 0 : &N == &h->bc ? 1 : 2;
-    a.paramsT = h->paramsT + h->wt_net_off[ni];
-    a.PT = h->PTT; a.ensT = (long long)(N.L - 1) * N.H * N.H;
+    a.params = *n.arena + N.off;
+    a.P = n.arena_ss; a.ens = N.ens_size;
+    a.paramsT = h->paramsT.p + h->wt_net_off[n.ni];
+    a.PT = h->paramsT.ss; a.ensT = (long long)(N.L - 1) * N.H * N.H;
     for (int l = 1; l < N.L; ++l) a.wt_off[l] = (long long)(l - 1) * N.H * N.H;
     for (int l = 0; l <= N.L; ++l) {
         a.w_off[l] = N.W[l];
@@ -854,19 +869,19 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, 
             if (N.ln) {
                 a.g_off[l] = N.gam[l];
                 a.be_off[l] = N.bet[l];
-                a.MU[l] = (*MU)[l];
-                a.RS[l] = (*RS)[l];
+                a.MU[l] = n.MU[l].p;
+                a.RS[l] = n.RS[l].p;
             }
-            a.U[l] = U[l];
-            a.DU[l] = DU[l];
+            a.U[l] = n.U[l].p;
+            a.DU[l] = n.DU[l].p;
         }
     }
-    a.dout = dout.p; a.dout_ss = dout.ss; a.dout_sy = dout.sy; a.ld_o = ld_o;
-    a.Ghead = G[N.L - 1];
-    a.s_ss = act_ss; a.s_sy = act_sy; a.st_ss = (long long)ld * N.E; a.st_sy = st_sy;
-    a.ld_s = ld; a.coff = (int)coff;
-    a.d_ss = d_ss; a.d_sy = d_sy; a.ld_d = ld_d;
-    a.part = part; a.NP = stream_bwd_np(N.L, N.H, N.out_dim, N.ln);
+    a.dout = dout.p; a.dout_ss = dout.ss; a.dout_sy = dout.sy; a.ld_o = n.ld_o;
+    a.Ghead = n.G[N.L - 1].p;
+    a.s_ss = n.U[0].ss; a.s_sy = n.sy; a.st_ss = (long long)n.ld * N.E; a.st_sy = n.st_sy;
+    a.ld_s = n.ld; a.coff = k.coff;
+    a.d_ss = n.DU[0].ss; a.d_sy = (long long)N.H * n.ld_d; a.ld_d = n.ld_d;
+    a.part = n.part.p; a.NP = stream_bwd_np(N.L, N.H, N.out_dim, N.ln);
     a.L = N.L; a.M = M; a.Mg = Mg; a.nout = N.out_dim;
     a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
     if (ig) {
@@ -876,20 +891,16 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, 
         a.da = ig->da.p; a.da_ss = ig->da.ss; a.da_sy = (long long)ig->A * ig->M;
         a.ld_da = ig->M; a.D0 = ig->D; a.na = ig->A;
     }
-    if (h->phase_dev != nullptr && &N == phase_net(h)) {
-        ARGCHK((long long)(M / 16) * N.E * c.nz <= h->phase_blocks, "phase probe: too many blocks");
+    const long long clusters = (long long)(M / 16) * N.E * c.nz;
+    if (h->phase_dev != nullptr && n.ni == phase_net()) {
+        ARGCHK(clusters <= h->phase_blocks, "phase probe: too many blocks");
         a.phase = h->phase_dev;
     }
-    if (!(skip_mask() & (&N == &h->critic ? 32 : &N == &h->bc ? 64 : 128))) {
-        const int site = &N != &h->critic ? SITE_OSB : (s == h->sX && h->sX != h->sM) ? SITE_CRB2 : SITE_CRB;
-        const int F = bwd_split(h, site, N, M, Mg, c.nz);
-        if (&N != &h->bc) check_plan(h, site, c.nz, F);
-        if (F > 1) {
-            const long long clusters = (long long)(M / 16) * N.E * c.nz;
-            launch_split_bwd(N.ln, F, a, split_prep(h, site, clusters, s), s);
-        } else {
-            launch_stream_bwd(N.ln, a, s);
-        }
+    if (!(skip_mask() & n.skip_bwd)) {
+        const int site = k.site >= 0 ? k.site : n.bwd_site;
+        const int F = site >= 0 ? c.plan.F[site] : 1;  // (the BC backward has no site: unsplit)
+        if (F > 1) launch_split_bwd(N.ln, F, a, split_prep(h, site, clusters, s), s);
+        else launch_stream_bwd(N.ln, a, s);
     }
     if (Mg == 0) return;  // (the critic's Q-loss columns alone: no parameter grads)
     hipEvent_t ev = nullptr;
@@ -900,11 +911,11 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, 
     // the parameter-grad half (partial reduction + dW, fused optimiser): now,
     // or by the caller later (`defer`), so that the step's critical chain is
     // captured ahead of it
-    const int NP = a.NP;
-    auto dw_half = [=, &N]() {
+    const int NP = a.NP, coff = k.coff;
+    auto dw_half = [=, &n, &N]() {
     if (ev) HIPCHK(hipStreamWaitEvent(sw, ev, 0));
     ColsumArgs r{};
-    r.part = part; r.NP = NP; r.tiles = Mg / 16;
+    r.part = n.part.p; r.NP = NP; r.tiles = Mg / 16;
     r.grads = h->grads + N.off; r.P = h->P; r.ens = N.ens_size;
     for (int l = 0; l < N.L; ++l) {
         r.b_off[l] = N.b[l];
@@ -915,25 +926,25 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, 
     r.ny = N.E; r.nz = c.nz; r.slots = h->slots;
     if (!(skip_mask() & 512)) launch_colsum_reduce(r, sw);
     // dW_l = X_l^T du_l over the first Mg columns, every layer in one grouped launch
-    auto act = [&](float* p) { return tref(p + coff, act_ss, act_sy); };
     std::vector<GemmArgs> gs;
     for (int l = N.L - 1; l >= 0; --l) {
         GemmArgs gw{};
-        gw.A = l == 0 ? X0 : act(G[l - 1]);
-        gw.B = tref(DU[l], d_ss, d_sy);
+        gw.A = l == 0 ? n.X->cols(coff) : n.act(n.G[l - 1], coff);
+        gw.B = n.grad(n.DU[l]);
         gw.C = pref(h, h->grads, N, N.W[l]);
         gw.M = N.kdim(l); gw.N = N.H; gw.K = Mg;
-        gw.lda = ld; gw.ldb = ld_d; gw.ldc = N.H;
+        gw.lda = n.ld; gw.ldb = n.ld_d; gw.ldc = N.H;
         gw.ny = N.E; gw.nz = c.nz; gw.slots = h->slots;
         gs.push_back(gw);
     }
+    const int ni = n.ni;
     if (h->fused_adam) {
         // dW of every layer with Adam / EMA / W^T / grad stats in the epilogue
         AdamEpi ae{};
         ae.p_in = h->params; ae.p_out = h->params_nx; ae.m = h->adam_m; ae.v = h->adam_v;
         ae.target = ni == 0 ? h->target : nullptr;
-        ae.wt_out = h->paramsT_nx;
-        ae.P = h->P; ae.PT = h->PT; ae.PTT = h->PTT;
+        ae.wt_out = h->paramsT_nx.p;
+        ae.P = h->P; ae.PT = h->PT; ae.PTT = h->paramsT_nx.ss;
         ae.ens = N.ens_size;
         ae.wt_sy = (long long)(N.L - 1) * N.H * N.H;
         for (int gi = 0; gi < (int)gs.size(); ++gi) {
@@ -972,10 +983,10 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const NetLayout& N, TRef dout, 
 // W^T copies (dst, a paramsT buffer) of the hidden kernels of the nets in
 // `mask` (bit ni: 0 critic, 1 bc, 2 os) from src (a params buffer), for the
 // active slots (all slots when all_slots).
-void transpose_nets(fqlpop* h, hipStream_t s, int mask, bool all_slots, const float* src, float* dst) {
+void transpose_nets(fqlpop* h, hipStream_t s, int mask, bool all_slots, const float* src, const Buf& dst) {
     TransposeArgs t{};
     t.src = src; t.src_ss = h->P;
-    t.dst = dst; t.dst_ss = h->PTT;
+    t.dst = dst.p; t.dst_ss = dst.ss;
     t.H = h->H;
     const NetLayout* nets[3] = {&h->critic, &h->bc, &h->os};
     const long long HH = (long long)h->H * h->H;
@@ -1030,18 +1041,22 @@ void adam_net(const Ctx& c, hipStream_t s, int ni) {
     if (a.n_chunks > 0) launch_adam(a, s);
 }
 
-// One whole-network forward launch (stream_fwd_kernel).  `arena` + N.off is the
-// net's parameter block (slot stride P); activations for the backward pass are
-// stored for columns [st_lo, st_hi) into U/G (slot stride s_ss, ensemble
-// stride s_sy, leading dim ld_s) and MU/RS (st_ss, st_sy) when given.
-void stream_fwd(const Ctx& c, hipStream_t s, const NetLayout& N, const float* arena, long long P, TRef X, int ldx,
-                int M, const std::vector<float*>* U, const std::vector<float*>* G, const std::vector<float*>* MU,
-                const std::vector<float*>* RS, long long s_ss, long long s_sy, long long st_ss, long long st_sy,
-                int st_lo, int st_hi, int mode, const HeadArgs& head, int g_hi = -1) {
+// Columns of a streamed forward: [st_lo, st_hi) keep their activations (U, G, MU / RS) for
+// the backward pass, the layer outputs G only up to g_hi (default st_hi).  An empty range
+// stores nothing (the target critic).
+struct FwdCols {
+    int st_lo, st_hi;
+    int g_hi = -1;
+};
+
+// One whole-network forward launch (stream_fwd_kernel) of `n` over all ld columns of its input.
+void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int mode, const HeadArgs& head) {
     fqlpop* h = c.h;
+    const NetLayout& N = *n.lay;
+    const bool store = k.st_hi > k.st_lo, stats = store && !n.MU.empty();
     StreamArgs a{};
-    a.params = arena + N.off;
-    a.P = P;
+    a.params = *n.arena + N.off;
+    a.P = n.arena_ss;
     a.ens = N.ens_size;
     for (int l = 0; l <= N.L; ++l) {
         a.w_off[l] = N.W[l];
@@ -1050,46 +1065,39 @@ void stream_fwd(const Ctx& c, hipStream_t s, const NetLayout& N, const float* ar
             a.g_off[l] = N.gam[l];
             a.be_off[l] = N.bet[l];
         }
-        if (l < N.L) {
-            a.U[l] = U ? (*U)[l] : nullptr;
-            a.G[l] = G ? (*G)[l] : nullptr;
-            a.MU[l] = MU ? (*MU)[l] : nullptr;
-            a.RS[l] = RS ? (*RS)[l] : nullptr;
+        if (l < N.L && store) {
+            a.U[l] = n.U[l].p;
+            a.G[l] = n.G[l].p;
+            if (stats && N.ln) { a.MU[l] = n.MU[l].p; a.RS[l] = n.RS[l].p; }
         }
     }
-    a.x0 = X.p;
-    a.x0_ss = X.ss;
-    a.ld_x = ldx; a.K0 = N.in_dim; a.L = N.L; a.M = M;
-    a.s_ss = s_ss; a.s_sy = s_sy; a.st_ss = st_ss; a.st_sy = st_sy;
-    a.ld_s = ldx; a.st_lo = st_lo; a.st_hi = st_hi;
-    a.g_hi = g_hi < 0 ? st_hi : g_hi;
+    a.x0 = n.X->p;
+    a.x0_ss = n.X->ss;
+    a.ld_x = n.ld; a.K0 = N.in_dim; a.L = N.L; a.M = n.ld;
+    if (store) { a.s_ss = n.U[0].ss; a.s_sy = n.sy; }
+    if (stats) { a.st_ss = n.MU[0].ss; a.st_sy = n.st_sy; }
+    a.ld_s = n.ld; a.st_lo = k.st_lo; a.st_hi = k.st_hi;
+    a.g_hi = k.g_hi < 0 ? k.st_hi : k.g_hi;
     a.head = head;
     a.head.nout = N.out_dim;
     a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
-    const int sk = skip_mask();
-    const int bit = &N == &h->bc ? 16 : &N == &h->os ? 8 : arena == h->target ? 2 : 4;
-    if (sk & bit) return;
-    const int site = &N == &h->bc ? SITE_BCF : &N == &h->os ? SITE_OSF : arena == h->target ? SITE_TGT : SITE_CRF;
-    const long long clusters = (long long)(M / 16) * N.E * c.nz;
-    const int F = split_fwd_supported(N.H, N.L, N.in_dim, N.out_dim, M) ? split_factor(h, site, clusters, false, h->opt.split_blocks) : 1;
-    check_plan(h, site, c.nz, F);
+    if (skip_mask() & n.skip_fwd) return;
+    const int F = c.plan.F[n.fwd_site];
     if (F > 1) {
         SplitFwdArgs sa{};
         sa.s = a;
-        sa.sync = split_prep(h, site, clusters, s);
+        sa.sync = split_prep(h, n.fwd_site, (long long)(n.ld / 16) * N.E * c.nz, s);
         launch_split_fwd(mode, N.ln, false, F, sa, s);
     } else {
         launch_stream_fwd(mode, N.ln, a, s);
     }
 }
 
-// The split form of the persistent Euler flow (euler_args' launch), or F = 1.
-int euler_split(const fqlpop* h, int nz) {
-    const NetLayout& N = h->bc;
-    if (!h->euler_fused || !split_fwd_supported(N.H, N.L, N.in_dim, N.out_dim, h->B)) return 1;
-    return split_factor(h, SITE_EULER, (long long)(h->B / 16) * nz, true, h->opt.split_blocks);
-}
-SplitFwdArgs euler_split_args(fqlpop* h, const EulerArgs& ea, hipStream_t s) {
+// The persistent Euler flow (euler_args' launch): euler_flow_kernel, or its split form where
+// the plan splits it.
+long long euler_blocks(const Ctx& c) { return (long long)(c.h->B / 16) * c.nz * c.plan.F[SITE_EULER]; }
+SplitFwdArgs euler_split_args(const Ctx& c, const EulerArgs& ea, hipStream_t s) {
+    fqlpop* h = c.h;
     const NetLayout& N = h->bc;
     SplitFwdArgs sa{};
     StreamArgs& a = sa.s;
@@ -1104,17 +1112,15 @@ SplitFwdArgs euler_split_args(fqlpop* h, const EulerArgs& ea, hipStream_t s) {
     sa.phase = ea.phase;
     sa.sync = split_prep(h, SITE_EULER, (long long)(ea.B / 16) * ea.nz, s);
     // the layer-0 scratch when it covers the launch (else the kernel's full layer-0 chain)
-    const long long blocks = (long long)(ea.B / 16) * ea.nz * euler_split(h, ea.nz);
-    sa.pre0 = h->euler_pre0 && blocks <= h->euler_pre0_blocks ? h->euler_pre0 : nullptr;
+    sa.pre0 = h->euler_pre0 && euler_blocks(c) <= h->euler_pre0_blocks ? h->euler_pre0 : nullptr;
     return sa;
 }
-long long euler_blocks(const fqlpop* h, int nz) { return (long long)(h->B / 16) * nz * euler_split(h, nz); }
-void launch_euler(fqlpop* h, const EulerArgs& ea, hipStream_t s) {
-    const int F = euler_split(h, ea.nz);
+void launch_euler(const Ctx& c, const EulerArgs& ea, hipStream_t s) {
+    const int F = c.plan.F[SITE_EULER];
     // every block of the launch writes its two probe stamps and its phase stamps
-    ARGCHK(ea.probe == nullptr || euler_blocks(h, ea.nz) <= h->probe_blocks, "Euler probe: too many blocks");
-    ARGCHK(ea.phase == nullptr || euler_blocks(h, ea.nz) <= h->ephase_blocks, "Euler phase probe: too many blocks");
-    if (F > 1) launch_split_fwd(HEAD_EULER, false, true, F, euler_split_args(h, ea, s), s);
+    ARGCHK(ea.probe == nullptr || euler_blocks(c) <= c.h->probe_blocks, "Euler probe: too many blocks");
+    ARGCHK(ea.phase == nullptr || euler_blocks(c) <= c.h->ephase_blocks, "Euler phase probe: too many blocks");
+    if (F > 1) launch_split_fwd(HEAD_EULER, false, true, F, euler_split_args(c, ea, s), s);
     else launch_euler_flow(ea, s);
 }
 
@@ -1139,8 +1145,8 @@ EulerArgs euler_args(fqlpop* h, int nz) {
         ea.w_off[l] = N.W[l];
         ea.b_off[l] = N.b[l];
     }
-    ea.eu = tref(h->eu_in, (long long)(h->D + h->A + 1) * h->B);
-    ea.aflow = tref(h->aflow, (long long)h->A * h->B);
+    ea.eu = h->eu_in.ref();
+    ea.aflow = h->aflow.ref();
     ea.D = h->D; ea.A = h->A; ea.H = h->H; ea.L = h->L; ea.B = h->B; ea.S = h->S; ea.first = 1;
     ea.steps_f = (float)h->S;
     ea.nz = nz; ea.slots = h->slots;
@@ -1294,10 +1300,9 @@ void flip_params(fqlpop* h);
 // side streams form a chain: sF and sB fork from sM, sB waits on sF (the BC forward), and sF
 // never waits on sB; everything joins back into sM.
 void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
-    const Ctx c{h, h->nz};
-    const int B = h->B, D = h->D, A = h->A, H = h->H, E = h->E, L = h->L, S = h->S;
-    const int Kc = D + A, Kb = D + A + 1;
-    const int B2 = 2 * B, B3 = 3 * B;
+    const Ctx c = step_ctx(h);
+    const int B = h->B, D = h->D, A = h->A, L = h->L, S = h->S;
+    const int B2 = 2 * B;
     hipStream_t sM = h->sM, sF = h->sF, sB = h->sB, sX = h->sX;
     h->ev_next = 0;
     h->probe_idx = 0;
@@ -1321,37 +1326,34 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     SampleArgs sa{};
     sa.obs = dset.obs; sa.act = dset.act; sa.rew = dset.rew; sa.mask = dset.mask; sa.nobs = dset.nobs;
     sa.n_rows = dset.rows;
-    sa.inj_batch = inj_batch ? h->inj_batch : nullptr;
-    sa.inj_noise = inj_noise ? h->inj_noise : nullptr;
+    sa.inj_batch = inj_batch ? h->inj_batch.p : nullptr;
+    sa.inj_noise = inj_noise ? h->inj_noise.p : nullptr;
     sa.seeds = h->skeys; sa.count = h->count;
     sa.step_add = 0;
     sa.stream_salt = train ? 0x51A7u : 0x5A1Du;
     sa.B = B; sa.D = D; sa.A = A;
-    sa.os_in = tref(h->os_in, (long long)Kc * B3);
-    sa.bc_in = tref(h->bc_in, (long long)Kb * B2);
-    sa.cr_in = tref(h->cr_in, (long long)Kc * B2);
-    sa.tg_in = tref(h->tg_in, (long long)Kc * B);
-    sa.eu_in = tref(h->eu_in, (long long)Kb * B);
-    sa.act_t = tref(h->act_t, (long long)A * B);
-    sa.x0_t = tref(h->x0_t, (long long)A * B);
-    sa.rew_t = tref(h->rew_t, B);
-    sa.mask_t = tref(h->mask_t, B);
+    sa.os_in = h->os_in.ref();
+    sa.bc_in = h->bc_in.ref();
+    sa.cr_in = h->cr_in.ref();
+    sa.tg_in = h->tg_in.ref();
+    sa.eu_in = h->eu_in.ref();
+    sa.act_t = h->act_t.ref();
+    sa.x0_t = h->x0_t.ref();
+    sa.rew_t = h->rew_t.ref();
+    sa.mask_t = h->mask_t.ref();
     sa.nz = c.nz; sa.slots = h->slots;
     // one-step actor forward on [s'; s; s] (z_next; z_d; z_metric), on sM
     auto os_forward = [&]() {
-        const NetLayout& N = h->os;
-        HeadArgs ha = head_args(c, N, h->os_g[L - 1], B3, B3, 0);
-        ha.o0 = tref(h->apiraw, (long long)A * B); ha.ld0 = B;
-        ha.o1 = tref(h->tg_in, (long long)Kc * B); ha.ld1 = B;
-        ha.o2 = tref(h->cr_in, (long long)Kc * B2); ha.ld2 = B2;
-        ha.o3 = tref(h->amet, (long long)A * B); ha.ld3 = B;
+        HeadArgs ha = head_args(c, h->n_os);
+        ha.o0 = h->apiraw.ref(); ha.ld0 = B;
+        ha.o1 = h->tg_in.ref(); ha.ld1 = B;
+        ha.o2 = h->cr_in.ref(); ha.ld2 = B2;
+        ha.o3 = h->amet.ref(); ha.ld3 = B;
         if (h->stream_fwd) {
             // only the z_d rows [B, 2B) are back-propagated (distill + Q loss)
-            stream_fwd(c, sM, N, h->params, h->P, tref(h->os_in, (long long)Kc * B3), B3, B3, &h->os_u, &h->os_g,
-                       nullptr, nullptr, (long long)H * B3, 0, 0, 0, B, 2 * B, HEAD_OS, ha);
+            stream_fwd(c, sM, h->n_os, FwdCols{B, 2 * B}, HEAD_OS, ha);
         } else {
-            fwd_hidden(c, sM, N, tref(h->os_in, (long long)Kc * B3), B3, B3, h->os_u, h->os_g, 0,
-                       nullptr, nullptr, 0, true);
+            fwd_hidden(c, sM, h->n_os);
             launch_head_fwd(HEAD_OS, ha, sM);
         }
     };
@@ -1360,48 +1362,44 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     if (sF != sM) HIPCHK(hipStreamWaitEvent(sF, h->ev_sample, 0));
     if (sB != sM) HIPCHK(hipStreamWaitEvent(sB, h->ev_sample, 0));
 
-    float* info = train ? h->info : h->vinfo;
     LossArgs la{};
-    la.q = tref(h->q, (long long)E * B2, B2);
-    la.qt = tref(h->qt, (long long)E * B, B);
-    la.rew = tref(h->rew_t, B);
-    la.mask = tref(h->mask_t, B);
-    la.vpred = tref(h->vpred, (long long)A * B);
-    la.act = tref(h->act_t, (long long)A * B);
-    la.x0 = tref(h->x0_t, (long long)A * B);
-    la.amet = tref(h->amet, (long long)A * B);
-    la.apiraw = tref(h->apiraw, (long long)A * B);
-    la.aflow = tref(h->aflow, (long long)A * B);
-    la.da = tref(h->da, (long long)E * A * B, (long long)A * B);
-    la.da_n = h->stream_bwd ? E : 1;  // per-ensemble partials of the streamed backward, else one sum
-    la.dq = tref(h->dq, (long long)E * B2, B2);
-    la.dv = tref(h->dv, (long long)A * B);
-    la.dout_os = tref(h->dout_os, (long long)A * B);
+    la.q = h->q.ref(B2);
+    la.qt = h->qt.ref(B);
+    la.rew = h->rew_t.ref();
+    la.mask = h->mask_t.ref();
+    la.vpred = h->vpred.ref();
+    la.act = h->act_t.ref();
+    la.x0 = h->x0_t.ref();
+    la.amet = h->amet.ref();
+    la.apiraw = h->apiraw.ref();
+    la.aflow = h->aflow.ref();
+    la.da = h->da.ref((long long)A * B);
+    la.da_n = h->stream_bwd ? h->E : 1;  // per-ensemble partials of the streamed backward, else one sum
+    la.dq = h->dq.ref(B2);
+    la.dv = h->dv.ref();
+    la.dout_os = h->dout_os.ref();
     la.g_cb4 = pref(h, h->grads, h->critic, h->critic.b[L]);
     la.g_bcb4 = pref(h, h->grads, h->bc, h->bc.b[L]);
     la.g_osb4 = pref(h, h->grads, h->os, h->os.b[L]);
-    la.info = tref(info, FQLPOP_INFO_STRIDE);
+    la.info = (train ? h->info : h->vinfo).ref();
     la.alpha = h->alpha;
-    la.B = B; la.A = A; la.E = E;
+    la.B = B; la.A = A; la.E = h->E;
     la.q_min = h->cfg.q_agg_min; la.normq = h->cfg.normalize_q_loss;
     la.discount = h->cfg.discount;
     la.nz = c.nz; la.slots = h->slots;
 
     // ---- sF: BC-flow forward (train rows) fused with Euler step 0 --------
     {
-        const NetLayout& N = h->bc;
-        HeadArgs ha = head_args(c, N, h->bc_g[L - 1], B2, B2, 0);
-        ha.o0 = tref(h->vpred, (long long)A * B); ha.ld0 = B;
-        ha.o1 = tref(h->bc_in, (long long)Kb * B2); ha.ld1 = B2;
-        ha.o2 = tref(h->eu_in, (long long)Kb * B); ha.ld2 = B;
+        HeadArgs ha = head_args(c, h->n_bc);
+        ha.o0 = h->vpred.ref(); ha.ld0 = B;
+        ha.o1 = h->bc_in.ref(); ha.ld1 = B2;
+        ha.o2 = h->eu_in.ref(); ha.ld2 = B;
         ha.t_next = (float)(1.0 / (double)S);
         if (h->stream_fwd) {
             // train rows [0, B) feed the BC backward; rows [B, 2B) are Euler step 0
-            stream_fwd(c, sF, N, h->params, h->P, tref(h->bc_in, (long long)Kb * B2), B2, B2, &h->bc_u, &h->bc_g,
-                       nullptr, nullptr, (long long)H * B2, 0, 0, 0, 0, B, HEAD_BC_FUSED, ha);
+            stream_fwd(c, sF, h->n_bc, FwdCols{0, B}, HEAD_BC_FUSED, ha);
         } else {
-            fwd_hidden(c, sF, N, tref(h->bc_in, (long long)Kb * B2), B2, B2, h->bc_u, h->bc_g, 0,
-                       nullptr, nullptr, 0, true);
+            fwd_hidden(c, sF, h->n_bc);
             launch_head_fwd(HEAD_BC_FUSED, ha, sF);
         }
         HIPCHK(hipEventRecord(h->ev_bcfwd, sF));
@@ -1409,15 +1407,14 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
             EulerArgs ea = euler_args(h, c.nz);
             if (h->probe_set >= 0 && h->probe_idx < h->probe_pairs)
                 ea.probe = h->probe_slots + 2 * h->probe_blocks * ((long long)h->probe_set * h->probe_pairs + h->probe_idx++);
-            if (!(skip_mask() & 1)) launch_euler(h, ea, sF);
+            if (!(skip_mask() & h->n_eu.skip_fwd)) launch_euler(c, ea, sF);
         }
         for (int i = 1; !h->euler_fused && i < S + (S == 1 ? 1 : 0); ++i) {
             // S == 1: one zero-cost pass that only clips (not used by the configs here)
-            fwd_hidden(c, sF, N, tref(h->eu_in, (long long)Kb * B), B, B, h->eu_g, h->eu_g, 0,
-                       nullptr, nullptr, 0, false, /*euler=*/true);
-            HeadArgs he = head_args(c, N, h->eu_g[L - 1], B, B, 0);
-            he.o0 = tref(h->aflow, (long long)A * B); he.ld0 = B;
-            he.o2 = tref(h->eu_in, (long long)Kb * B); he.ld2 = B;
+            fwd_hidden(c, sF, h->n_eu);
+            HeadArgs he = head_args(c, h->n_eu);
+            he.o0 = h->aflow.ref(); he.ld0 = B;
+            he.o2 = h->eu_in.ref(); he.ld2 = B;
             he.last = (i == S - 1) ? 1 : 0;
             he.t_next = (float)((double)(i + 1) / (double)S);
             launch_head_fwd(HEAD_EULER, he, sF);
@@ -1431,13 +1428,9 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     launch_loss_bc(la, sB);
     HIPCHK(hipEventRecord(h->ev_bcloss, sB));
     if (train) {
-        const NetLayout& N = h->bc;
-        if (h->stream_bwd)
-            stream_bwd_net(c, sB, N, tref(h->dv, (long long)A * B), B, tref(h->bc_in, (long long)Kb * B2), B2, 0, B,
-                           B, h->bc_u, h->bc_g, 0, nullptr, nullptr, 0, h->bc_du, B, h->part_bc, sB);
-        else
-            bwd_net(c, sB, N, tref(h->dv, (long long)A * B), B, tref(h->bc_in, (long long)Kb * B2), B2, 0, B, B,
-                    h->bc_u, h->bc_g, 0, nullptr, nullptr, 0, h->bc_du, h->bc_dh, nullptr, nullptr, B, sB);
+        const BwdCols cols{0, B, B};
+        if (h->stream_bwd) stream_bwd_net(c, sB, h->n_bc, cols, h->dv.ref(), sB);
+        else bwd_net(c, sB, h->n_bc, cols, h->dv.ref());
         if (!h->fused_adam) {
             adam_net(c, sB, 1);
             if (h->stream_bwd) transpose_nets(h, sB, 2, false, h->params_nx, h->paramsT_nx);
@@ -1447,8 +1440,6 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
 
     // ---- sM: one-step actor forward on [s'; s; s] (z_next; z_d; z_metric) --
     os_forward();
-    const NetLayout& NC = h->critic;
-    const long long sy2 = (long long)H * B2, sy1 = (long long)H * B;
     // The 4th-stream schedule ("small-population schedule", since round 5
     // at every population size): the target critic and, later, the critic's TD-column backward
     // run on a 4th stream sX beside the main chain, which then carries the critic forward, the
@@ -1456,71 +1447,32 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     // sM / sB; it never waits on sB or sF (capture rule above).  Same box against three
     // streams: +3.7 % at 6 members, +3.3 % at 8, +0.9 % at 12, +1.6 / +2.1 % at ant 2 / 4,
     // neutral at 4 and 16 (round 4's -12-14 % at 4 members was under the old split plan),
-    // -1.1 % at ant 16 (1 024 tiles): on up to kSmallSchedTiles 16-column tiles
-    const bool small = h->opt.small_sched && h->sX != h->sM && h->stream_fwd && h->stream_bwd && h->fused_adam &&
-                       (long long)(h->B / 16) * c.nz <= kSmallSchedTiles;
-    {
-        int plan[SITE_N];
-        bool plan_small = false;
-        split_plan(h->opt, split_shape(h), c.nz, plan, &plan_small);
-        ARGCHK(plan_small == small && plan[SITE_EULER] == euler_split(h, c.nz), "step differs from the split plan");
-    }
+    // -1.1 % at ant 16 (1 024 tiles): on up to kSmallSchedTiles 16-column tiles (split_plan)
+    const bool small = c.plan.small;
     hipStream_t sT = small ? h->sX : sM;
     dep(sM, sT);  // a' is in the target-critic input
     // ---- sM (sX): target critic on [s', a'] (params from the target arena) -----
     if (h->stream_fwd) {
         HeadArgs ht{};
         ht.B = B; ht.D = D; ht.steps_f = (float)S;
-        ht.o0 = tref(h->qt, (long long)E * B, B); ht.ld0 = B;
-        stream_fwd(c, sT, NC, h->target, h->PT, tref(h->tg_in, (long long)Kc * B), B, B, nullptr, nullptr, nullptr,
-                   nullptr, 0, 0, 0, 0, 0, 0, HEAD_STORE, ht);
+        ht.o0 = h->qt.ref(B); ht.ld0 = B;
+        stream_fwd(c, sT, h->n_tg, FwdCols{0, 0}, HEAD_STORE, ht);
     } else {
-        const NetLayout& N = NC;
-        for (int l = 0; l < L; ++l) {
-            GemmArgs g{};
-            g.A = tref(h->target + N.W[l], h->PT, N.ens_size);
-            g.B = l == 0 ? tref(h->tg_in, (long long)Kc * B, 0) : tref(h->tg_h[l - 1], (long long)H * B * E, sy1);
-            g.C = tref(N.ln ? h->tg_u[l] : h->tg_h[l], (long long)H * B * E, sy1);
-            g.bias = tref(h->target + N.b[l], h->PT, N.ens_size);
-            g.M = H; g.N = B; g.K = N.kdim(l);
-            g.lda = H; g.ldb = B; g.ldc = B;
-            g.ny = E; g.nz = c.nz; g.slots = h->slots;
-            gemm(LAYOUT_FWD, N.ln ? EPI_BIAS : EPI_BIAS_GELU, g, sM);
-            if (N.ln) {
-                LnArgs a{};
-                a.u = tref(h->tg_u[l], (long long)H * B * E, sy1);
-                a.h = tref(h->tg_h[l], (long long)H * B * E, sy1);
-                a.mu = tref(h->tg_mu[l], (long long)B * E, B);
-                a.rstd = tref(h->tg_rs[l], (long long)B * E, B);
-                a.gamma = tref(h->target + N.gam[l], h->PT, N.ens_size);
-                a.beta = tref(h->target + N.bet[l], h->PT, N.ens_size);
-                a.H = H; a.M = B; a.ld = B; a.ny = E; a.nz = c.nz; a.slots = h->slots;
-                launch_ln_gelu_fwd(a, sM);
-            }
-        }
-        HeadArgs ht{};
-        ht.h = tref(h->tg_h[L - 1], (long long)H * B * E, sy1);
-        ht.W = tref(h->target + N.W[L], h->PT, N.ens_size);
-        ht.b = tref(h->target + N.b[L], h->PT, N.ens_size);
-        ht.H = H; ht.M = B; ht.ld = B; ht.nout = 1; ht.B = B; ht.D = D; ht.steps_f = (float)S;
-        ht.o0 = tref(h->qt, (long long)E * B, B); ht.ld0 = B;
-        ht.ny = E; ht.nz = c.nz; ht.slots = h->slots;
-        launch_head_fwd(HEAD_STORE, ht, sM);
+        fwd_hidden(c, sT, h->n_tg);
+        HeadArgs ht = head_args(c, h->n_tg);
+        ht.o0 = h->qt.ref(B); ht.ld0 = B;
+        launch_head_fwd(HEAD_STORE, ht, sT);
     }
     // ---- sM: critic on [s,a ; s,clip(a_pi)] -------------------------------
     {
-        const NetLayout& N = NC;
-        HeadArgs hc = head_args(c, N, h->cr_h[L - 1], B2, B2, sy2);
-        hc.o0 = tref(h->q, (long long)E * B2, B2); hc.ld0 = B2;
+        HeadArgs hc = head_args(c, h->n_cr);
+        hc.o0 = h->q.ref(B2); hc.ld0 = B2;
         if (h->stream_fwd) {
             // the a_pi columns [B, 2B) are back-propagated for dQ/da only: their layer outputs
             // (the dW GEMMs' operand) are not needed by the streamed backward
-            stream_fwd(c, sM, N, h->params, h->P, tref(h->cr_in, (long long)Kc * B2, 0), B2, B2, &h->cr_u, &h->cr_h,
-                       N.ln ? &h->cr_mu : nullptr, N.ln ? &h->cr_rs : nullptr, (long long)H * B2 * E, sy2,
-                       (long long)B2 * E, B2, 0, B2, HEAD_STORE, hc, h->stream_bwd ? B : B2);
+            stream_fwd(c, sM, h->n_cr, FwdCols{0, B2, h->stream_bwd ? B : B2}, HEAD_STORE, hc);
         } else {
-            fwd_hidden(c, sM, N, tref(h->cr_in, (long long)Kc * B2, 0), B2, B2, h->cr_u, h->cr_h, sy2,
-                       &h->cr_mu, &h->cr_rs, B2, true);
+            fwd_hidden(c, sM, h->n_cr);
             launch_head_fwd(HEAD_STORE, hc, sM);
         }
     }
@@ -1532,11 +1484,12 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     std::function<void()> critic_dw;
     if (train) {
         // critic backward: the dX chain on sM
+        const Net& cr = h->n_cr;
         InGradArgs ig{};
-        ig.W0 = pref(h, h->params, NC, NC.W[0]);
-        ig.du0 = tref(h->cr_du[0], (long long)H * B2 * E, sy2);
-        ig.da = tref(h->da, (long long)E * A * B);
-        ig.H = H; ig.D = D; ig.A = A; ig.E = E; ig.ld = B2; ig.off = B; ig.M = B;
+        ig.W0 = cr.par(h->critic.W[0]);
+        ig.du0 = cr.grad(cr.DU[0]);
+        ig.da = h->da.ref();
+        ig.H = h->H; ig.D = D; ig.A = A; ig.E = h->E; ig.ld = B2; ig.off = B; ig.M = B;
         ig.nz = c.nz; ig.slots = h->slots;
         if (small) {
             // the Q-loss columns [B, 2B) on sM (dQ/da: the actor chain waits for it), the TD columns
@@ -1544,20 +1497,13 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
             dep(sM, sX);
             InGradArgs ig0 = ig;
             ig0.off = 0;  // (relative to the launch's columns)
-            stream_bwd_net(c, sM, NC, tref(h->dq + B, (long long)E * B2, B2), B2, tref(h->cr_in, (long long)Kc * B2, 0),
-                           B2, B, B, 0, h->cr_u, h->cr_h, sy2, &h->cr_mu, &h->cr_rs, B2, h->cr_du, B2, h->part_cr, sM,
-                           &ig0, nullptr);
-            stream_bwd_net(c, sX, NC, tref(h->dq, (long long)E * B2, B2), B2, tref(h->cr_in, (long long)Kc * B2, 0),
-                           B2, 0, B, B, h->cr_u, h->cr_h, sy2, &h->cr_mu, &h->cr_rs, B2, h->cr_du, B2, h->part_cr, sB,
-                           nullptr, &critic_dw);
+            stream_bwd_net(c, sM, cr, BwdCols{B, B, 0}, h->dq.cols(B, B2), sM, &ig0);
+            stream_bwd_net(c, sX, cr, BwdCols{0, B, B, SITE_CRB2}, h->dq.ref(B2), sB, nullptr, &critic_dw);
         } else if (h->stream_bwd) {
-            stream_bwd_net(c, sM, NC, tref(h->dq, (long long)E * B2, B2), B2, tref(h->cr_in, (long long)Kc * B2, 0),
-                           B2, 0, B2, B, h->cr_u, h->cr_h, sy2, &h->cr_mu, &h->cr_rs, B2, h->cr_du, B2, h->part_cr,
-                           h->fused_adam ? sB : sM, &ig, h->fused_adam ? &critic_dw : nullptr);
+            stream_bwd_net(c, sM, cr, BwdCols{0, B2, B}, h->dq.ref(B2), h->fused_adam ? sB : sM, &ig,
+                           h->fused_adam ? &critic_dw : nullptr);
         } else {
-            bwd_net(c, sM, NC, tref(h->dq, (long long)E * B2, B2), B2, tref(h->cr_in, (long long)Kc * B2, 0), B2, 0,
-                    B2, B, h->cr_u, h->cr_h, sy2, &h->cr_mu, &h->cr_rs, B2, h->cr_du, h->cr_dh, h->cr_c1, h->cr_c2,
-                    B2, sM);
+            bwd_net(c, sM, cr, BwdCols{0, B2, B}, h->dq.ref(B2));
             launch_input_grad(ig, sM);
         }
         // critic Adam + target EMA (the unfused paths)
@@ -1570,7 +1516,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     if (sB != sM) HIPCHK(hipStreamWaitEvent(sM, h->ev_bcloss, 0));
     if (!(skip_mask() & 256)) launch_loss_actor(la, sM);
     if (train) {
-        const NetLayout& N = h->os;
+        const BwdCols cols{B, B, B};  // the z_d rows
         if (h->fused_adam) {
             // the critic's dW launch waits for the actor loss too, so that the actor backward
             // (the critical chain) is dispatched first: a dW launch dispatched ahead of it
@@ -1580,19 +1526,13 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
             // actor dX chain, then the critic's grads + Adam (sB) beside the actor's (sM), then
             // the join
             std::function<void()> os_dw;
-            stream_bwd_net(c, sM, N, tref(h->dout_os, (long long)A * B), B, tref(h->os_in + B, (long long)Kc * B3), B3,
-                           B, B, B, h->os_u, h->os_g, 0, nullptr, nullptr, 0, h->os_du, B, h->part_os, sM, nullptr,
-                           &os_dw);
+            stream_bwd_net(c, sM, h->n_os, cols, h->dout_os.ref(), sM, nullptr, &os_dw);
             critic_dw();  // the fused launches include each net's small-leaf Adam
             os_dw();
             dep(sB, sM);
         } else {
-            if (h->stream_bwd)
-                stream_bwd_net(c, sM, N, tref(h->dout_os, (long long)A * B), B, tref(h->os_in + B, (long long)Kc * B3),
-                               B3, B, B, B, h->os_u, h->os_g, 0, nullptr, nullptr, 0, h->os_du, B, h->part_os, sM);
-            else
-                bwd_net(c, sM, N, tref(h->dout_os, (long long)A * B), B, tref(h->os_in + B, (long long)Kc * B3), B3, B,
-                        B, B, h->os_u, h->os_g, 0, nullptr, nullptr, 0, h->os_du, h->os_dh, nullptr, nullptr, B, sM);
+            if (h->stream_bwd) stream_bwd_net(c, sM, h->n_os, cols, h->dout_os.ref(), sM);
+            else bwd_net(c, sM, h->n_os, cols, h->dout_os.ref());
             adam_net(c, sM, 2);
             if (h->stream_bwd) transpose_nets(h, sM, 4, false, h->params_nx, h->paramsT_nx);
         }
@@ -1600,7 +1540,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         FinalArgs fa{};
         fa.stats = h->stats; fa.chunk_leaf = h->chunk_leaf; fa.leaf_first = h->leaf_first;
         fa.n_total_chunks = h->n_chunks_total; fa.n_leaves = h->n_train_leaves;
-        fa.info = tref(h->info, FQLPOP_INFO_STRIDE);
+        fa.info = h->info.ref();
         fa.count = h->count;
         fa.nz = c.nz; fa.slots = h->slots;
         launch_finalize(fa, sM);
@@ -1851,11 +1791,9 @@ int fqlpop_split_plan(const fqlpop_config* cfg, int n_members, int* blocks_per_t
                      euler_flow_supported(H, L, D, A, B) && !cfg->actor_layer_norm && eo.euler_fused != 0,
                      step_streams(eo) > 1};
         d.fused_adam = d.stream_bwd && H % 128 == 0 && L <= GEMM_GROUP_MAX && eo.fused_adam;
-        int F[SITE_N];
-        bool small = false;
-        split_plan(eo, d, n_members, F, &small);
-        for (int i = 0; i < SITE_N; ++i) blocks_per_tile[i] = F[i];
-        *small_sched = small ? 1 : 0;
+        const SplitPlan p = split_plan(eo, d, n_members);
+        for (int i = 0; i < SITE_N; ++i) blocks_per_tile[i] = p.F[i];
+        *small_sched = p.small ? 1 : 0;
     });
 }
 
@@ -2003,42 +1941,68 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         build_chunks(h.get());
 
         const int Kc = D + A, Kb = D + A + 1, B2 = 2 * B, B3 = 3 * B;
-        h->os_in = h->alloc(align_up((long long)Kc * B3));
-        h->bc_in = h->alloc(align_up((long long)Kb * B2));
-        h->eu_in = h->alloc(align_up((long long)Kb * B));
-        for (float*& cb : h->cr_in_buf) cb = h->alloc(align_up((long long)Kc * B2));
+        // the network inputs [K][ld]: allocated rounded up, strided by their size
+        auto input = [&](int K, int ld) { return h->alloc(align_up((long long)K * ld), (long long)K * ld); };
+        h->os_in = input(Kc, B3);
+        h->bc_in = input(Kb, B2);
+        h->eu_in = input(Kb, B);
+        for (Buf& cb : h->cr_in_buf) cb = input(Kc, B2);
         h->cr_in = h->cr_in_buf[0];
-        h->tg_in = h->alloc(align_up((long long)Kc * B));
-        for (int l = 0; l < L; ++l) {
-            h->os_u.push_back(h->alloc((long long)H * B3));
-            h->os_g.push_back(h->alloc((long long)H * B3));
-            h->bc_u.push_back(h->alloc((long long)H * B2));
-            h->bc_g.push_back(h->alloc((long long)H * B2));
-            h->eu_g.push_back(h->alloc((long long)H * B));
-            h->cr_u.push_back(h->alloc((long long)H * B2 * E));
-            h->cr_h.push_back(h->alloc((long long)H * B2 * E));
-            h->cr_mu.push_back(h->alloc((long long)B2 * E));
-            h->cr_rs.push_back(h->alloc((long long)B2 * E));
-            h->tg_u.push_back(h->alloc((long long)H * B * E));
-            h->tg_h.push_back(h->alloc((long long)H * B * E));
-            h->tg_mu.push_back(h->alloc((long long)B * E));
-            h->tg_rs.push_back(h->alloc((long long)B * E));
-            h->cr_du.push_back(h->alloc((long long)H * B2 * E));
-            h->bc_du.push_back(h->alloc((long long)H * B));
-            h->os_du.push_back(h->alloc((long long)H * B));
+        h->tg_in = input(Kc, B);
+        // the network bundles: identity and leading dimensions here, their buffers below
+        Net& cr = h->n_cr;
+        cr.lay = &h->critic; cr.arena = &h->params; cr.arena_ss = h->P; cr.ni = 0;
+        cr.X = &h->cr_in; cr.ld = B2; cr.sy = (long long)H * B2; cr.st_sy = B2;
+        cr.fwd_site = SITE_CRF; cr.skip_fwd = 4;
+        cr.ld_d = B2; cr.ld_o = B2; cr.bwd_site = SITE_CRB; cr.skip_bwd = 32;
+        Net& tg = h->n_tg;  // forward only, parameters from the target arena
+        tg.lay = &h->critic; tg.arena = &h->target; tg.arena_ss = h->PT; tg.ni = 0;
+        tg.X = &h->tg_in; tg.ld = B; tg.sy = (long long)H * B; tg.st_sy = B; tg.keep_u = false;
+        tg.fwd_site = SITE_TGT; tg.skip_fwd = 2;
+        Net& bc = h->n_bc;  // (no backward site: the BC backward stays unsplit)
+        bc.lay = &h->bc; bc.arena = &h->params; bc.arena_ss = h->P; bc.ni = 1;
+        bc.X = &h->bc_in; bc.ld = B2;
+        bc.fwd_site = SITE_BCF; bc.skip_fwd = 16;
+        bc.ld_d = B; bc.ld_o = B; bc.skip_bwd = 64;
+        Net& eu = h->n_eu;  // forward only: the BC actor's Euler steps on B columns, layer by layer
+        eu.lay = &h->bc; eu.arena = &h->params; eu.arena_ss = h->P; eu.ni = 1;
+        eu.X = &h->eu_in; eu.ld = B; eu.keep_u = false; eu.dominant = true;
+        eu.fwd_site = SITE_EULER; eu.skip_fwd = 1;
+        Net& os = h->n_os;
+        os.lay = &h->os; os.arena = &h->params; os.arena_ss = h->P; os.ni = 2;
+        os.X = &h->os_in; os.ld = B3;
+        os.fwd_site = SITE_OSF; os.skip_fwd = 8;
+        os.ld_d = B; os.ld_o = B; os.bwd_site = SITE_OSB; os.skip_bwd = 128;
+        for (Net* n : {&os, &bc, &eu, &cr, &tg}) {
+            const NetLayout& N = *n->lay;
+            const bool ens = n->st_sy != 0;  // the critic's layout: LN statistics and row sums per ensemble member
+            for (int l = 0; l < L; ++l) {
+                if (n->keep_u || N.ln) n->U.push_back(h->alloc((long long)H * n->ld * N.E));
+                n->G.push_back(h->alloc((long long)H * n->ld * N.E));
+                if (ens) {
+                    n->MU.push_back(h->alloc((long long)n->ld * N.E));
+                    n->RS.push_back(h->alloc((long long)n->ld * N.E));
+                }
+                if (n->ld_d) n->DU.push_back(h->alloc((long long)H * n->ld_d * N.E));
+            }
+            if (n->ld_d == 0) continue;  // forward only
+            n->DH = h->alloc((long long)H * n->ld_d * N.E);
+            if (ens) {
+                n->C1 = h->alloc((long long)n->ld_d * N.E);
+                n->C2 = h->alloc((long long)n->ld_d * N.E);
+            }
+            // column-sum partials of the B columns that feed the parameter grads (Mg = B for every net)
+            if (h->stream_bwd) n->part = h->alloc((long long)N.E * (B / 16) * stream_bwd_np(L, H, N.out_dim, N.ln));
         }
         if (h->stream_bwd) {
-            const int T = B / 16;  // tiles with partials (Mg = B for every net)
-            h->part_cr = h->alloc((long long)E * T * stream_bwd_np(L, H, 1, h->critic.ln));
-            h->part_bc = h->alloc((long long)T * stream_bwd_np(L, H, A, h->bc.ln));
-            h->part_os = h->alloc((long long)T * stream_bwd_np(L, H, A, h->os.ln));
             const long long HH = (long long)H * H;
             h->wt_net_off[0] = 0;
             h->wt_net_off[1] = (long long)E * (L - 1) * HH;
             h->wt_net_off[2] = (long long)(E + 1) * (L - 1) * HH;
-            h->PTT = (long long)(E + 2) * (L - 1) * HH;
-            h->paramsT_buf[0] = h->paramsT = h->alloc(std::max<long long>(1, h->PTT));
-            h->paramsT_buf[1] = h->paramsT_nx = h->alloc(std::max<long long>(1, h->PTT));
+            const long long PTT = (long long)(E + 2) * (L - 1) * HH;
+            for (Buf& tb : h->paramsT_buf) tb = h->alloc(std::max<long long>(1, PTT), PTT);
+            h->paramsT = h->paramsT_buf[0];
+            h->paramsT_nx = h->paramsT_buf[1];
         }
         // split launch sites: exchange and counters for up to kSplitMaxClusters tiles each
         h->split_ok = h->stream_fwd && eo.split != 0;
@@ -2057,10 +2021,14 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
                 HIPCHK(hipMemset(st.gen, 0, 64));
             }
             // the split Euler flow's layer-0 accumulators: 32 KB per block, for the largest split
-            // Euler launch (up to 128 tiles at 8 blocks each)
+            // Euler launch the plan makes over 1..n active members
             if (split_euler_pre0(D + A + 1, D)) {
-                h->euler_pre0_blocks = std::min<long long>(h->split_site[SITE_EULER].clusters, 128) * 8;
-                HIPCHK(hipMalloc(&h->euler_pre0, sizeof(float) * split_euler_pre0_floats() * h->euler_pre0_blocks));
+                for (int nz = 1; nz <= n; ++nz) {
+                    const int F = split_plan(h.get(), nz).F[SITE_EULER];
+                    if (F > 1) h->euler_pre0_blocks = std::max(h->euler_pre0_blocks, (long long)(B / 16) * nz * F);
+                }
+                if (h->euler_pre0_blocks > 0)
+                    HIPCHK(hipMalloc(&h->euler_pre0, sizeof(float) * split_euler_pre0_floats() * h->euler_pre0_blocks));
             }
             // the error word lives in host memory so that every entry point can test it without a
             // device-to-host copy (fqlpop_step does, before it enqueues more steps)
@@ -2068,25 +2036,18 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
             std::memset(h->split_err_host, 0, 64);
             HIPCHK(hipHostGetDevicePointer((void**)&h->split_err, h->split_err_host, 0));
         }
-        h->cr_dh = h->alloc((long long)H * B2 * E);
-        h->bc_dh = h->alloc((long long)H * B);
-        h->os_dh = h->alloc((long long)H * B);
-        h->cr_c1 = h->alloc((long long)B2 * E);
-        h->cr_c2 = h->alloc((long long)B2 * E);
         h->q = h->alloc((long long)E * B2);
         h->dq = h->alloc((long long)E * B2);
         h->qt = h->alloc((long long)E * B);
-        for (float** p : {&h->vpred, &h->dv, &h->act_t, &h->x0_t, &h->apiraw, &h->aflow, &h->amet, &h->dout_os})
+        for (Buf* p : {&h->vpred, &h->dv, &h->act_t, &h->x0_t, &h->apiraw, &h->aflow, &h->amet, &h->dout_os})
             *p = h->alloc((long long)A * B);
         h->da = h->alloc((long long)E * A * B);  // dQ/da, one partial per critic ensemble member
         h->rew_t = h->alloc(B);
         h->mask_t = h->alloc(B);
         h->info = h->alloc(FQLPOP_INFO_STRIDE);
         h->vinfo = h->alloc(FQLPOP_INFO_STRIDE);
-        h->inj_bs = (long long)B * (2 * D + A + 2);
-        h->inj_ns = (long long)B * (4 * A + 1);
-        h->inj_batch = h->alloc(h->inj_bs);
-        h->inj_noise = h->alloc(h->inj_ns);
+        h->inj_batch = h->alloc((long long)B * (2 * D + A + 2));
+        h->inj_noise = h->alloc((long long)B * (4 * A + 1));
 
         h->h_alpha.assign(alphas, alphas + n);
         h->h_seeds.assign(seeds_in, seeds_in + n);
@@ -2141,13 +2102,13 @@ int fqlpop_destroy(fqlpop_t* h) {
                     std::fclose(fp);
                 }
             }
-            const NetLayout* pn = phase_net(h);
-            phase_report(h->phase_host, h->phase_blocks, h->L, pn->ln,
-                         pn == &h->critic ? "critic" : pn == &h->bc ? "BC" : "one-step");
+            const NetLayout* nets[3] = {&h->critic, &h->bc, &h->os};
+            const char* const names[3] = {"critic", "BC", "one-step"};
+            phase_report(h->phase_host, h->phase_blocks, h->L, nets[phase_net()]->ln, names[phase_net()]);
             (void)hipHostFree(h->phase_host);
         }
         if (h->ephase_host) {
-            if (euler_split(h, h->nz) > 1)
+            if (split_plan(h, h->nz).F[SITE_EULER] > 1)
                 split_euler_phase_report(h->ephase_host, h->ephase_blocks, h->L, h->S - 1);
             else
                 euler_phase_report(h->ephase_host, h->ephase_blocks, h->L, h->S - 1);
@@ -2216,7 +2177,7 @@ int fqlpop_step(fqlpop_t* h, int n_steps) {
                 const int set = (int)(h->probe_step & 1);
                 if (h->probe_pending[set]) probe_consume(h, set);  // the step i-2 that used this set
                 h->probe_set = set;
-                h->probe_nb[set] = euler_blocks(h, h->nz);
+                h->probe_nb[set] = euler_blocks(step_ctx(h));
                 run(h, true, false, false);
                 h->probe_set = -1;
                 HIPCHK(hipEventRecord(h->probe_done[set], h->sM));
@@ -2232,9 +2193,11 @@ int fqlpop_step(fqlpop_t* h, int n_steps) {
 // stage the injected batch / noise of every active member on sM
 static void stage_injected(fqlpop* h, const float* batch, const float* noise) {
     if (batch)
-        HIPCHK(hipMemcpyAsync(h->inj_batch, batch, sizeof(float) * h->inj_bs * h->nz, hipMemcpyHostToDevice, h->sM));
+        HIPCHK(hipMemcpyAsync(h->inj_batch.p, batch, sizeof(float) * h->inj_batch.ss * h->nz, hipMemcpyHostToDevice,
+                              h->sM));
     if (noise)
-        HIPCHK(hipMemcpyAsync(h->inj_noise, noise, sizeof(float) * h->inj_ns * h->nz, hipMemcpyHostToDevice, h->sM));
+        HIPCHK(hipMemcpyAsync(h->inj_noise.p, noise, sizeof(float) * h->inj_noise.ss * h->nz, hipMemcpyHostToDevice,
+                              h->sM));
 }
 
 int fqlpop_step_injected(fqlpop_t* h, const float* batch, const float* noise) {
@@ -2269,7 +2232,8 @@ int fqlpop_read_info(fqlpop_t* h, int which, float* out) {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->sM));
         check_split_error(h);
-        HIPCHK(hipMemcpy(out, which ? h->vinfo : h->info, sizeof(float) * FQLPOP_INFO_STRIDE * h->n,
+        const Buf& info = which ? h->vinfo : h->info;
+        HIPCHK(hipMemcpy(out, info.p, sizeof(float) * info.ss * h->n,
                          hipMemcpyDeviceToHost));
     });
 }
@@ -2500,18 +2464,19 @@ int fqlpop_time_dominant_kernel(fqlpop_t* h, int iters, double* avg_us, double* 
         // the dominant launch, replayed alone on sF with the buffers of the last step:
         // the persistent Euler flow (reads eu_in, writes aflow: idempotent), or
         // Euler hidden layer 1: eu_g[1] = gelu(W1^T eu_g[0] + b1)
-        EulerArgs ea = euler_args(h, h->nz);
+        const Ctx c = step_ctx(h);
+        EulerArgs ea = euler_args(h, c.nz);
         GemmArgs g{};
         g.A = pref(h, h->params, N, N.W[1]);
-        g.B = tref(h->eu_g[0], (long long)H * B);
-        g.C = tref(h->eu_g[1], (long long)H * B);
+        g.B = h->n_eu.G[0].ref();
+        g.C = h->n_eu.G[1].ref();
         g.bias = pref(h, h->params, N, N.b[1]);
         g.M = H; g.N = B; g.K = H; g.lda = H; g.ldb = B; g.ldc = B;
         g.ny = 1; g.nz = h->nz; g.slots = h->slots;
         auto launch = [&](unsigned long long* probe) {
             if (h->euler_fused) {
                 ea.probe = probe;
-                launch_euler(h, ea, h->sF);
+                launch_euler(c, ea, h->sF);
             } else {
                 g.probe = probe;
                 launch_gemm_euler_hidden(g, h->sF);
@@ -2537,7 +2502,7 @@ int fqlpop_time_dominant_kernel(fqlpop_t* h, int iters, double* avg_us, double* 
         std::vector<unsigned long long> v(2 * h->probe_blocks);
         std::memcpy(v.data(), h->probe_host, sizeof(unsigned long long) * v.size());
         h->clock_check_event_us = 1000.0 * ms;
-        h->clock_check_stamp_us = probe_launch_us(v.data(), h->euler_fused ? euler_blocks(h, h->nz) : h->probe_blocks);
+        h->clock_check_stamp_us = probe_launch_us(v.data(), h->euler_fused ? euler_blocks(c) : h->probe_blocks);
     });
 }
 
@@ -2547,7 +2512,7 @@ int fqlpop_dominant_kernel_info(fqlpop_t* h, char* name, int name_cap, double* f
         const double B = h->B, H = h->H, K0 = h->D + h->A + 1, A = h->A, L = h->L, nz = h->nz;
         std::string nm;
         if (h->euler_fused) {
-            const int F = euler_split(h, h->nz);
+            const int F = split_plan(h, h->nz).F[SITE_EULER];
             nm = F > 1 ? "split_fwd_kernel<HEAD_EULER> F=" + std::to_string(F) : "euler_flow_kernel";
             // unique bytes: the bc net's Dense kernels + biases, the state in, a_flow out
             *bytes = 4.0 * nz * (K0 * H + (L - 1) * H * H + H * A + L * H + A + K0 * B + A * B);
