@@ -409,11 +409,9 @@ void launch_init(const InitArgs& a, hipStream_t s);
 // until every env has terminated or max_steps.  Block = 16 envs of one member.
 constexpr int RO_MAX_LAYERS = 8;   // env-model Dense layers (hidden + output)
 constexpr int RO_MAX_W = 512;      // widest env-model layer
-struct RolloutArgs {
-    const float* params;           // population arena (slot stride P), one-step actor at os_off
-    long long P, os_off;
-    long long w_off[EF_MAX_LAYERS + 1], b_off[EF_MAX_LAYERS + 1];
-    int D, A, L;                   // actor hidden width 512
+// The env model both evaluators run (fqlpop_set_env_model): flat flax-ordered parameters
+// of the state predictor and the termination predictor, and their layer tables.
+struct EnvModelNet {
     const float* sp;               // state predictor params (flat, flax order)
     int sp_n;                      // Dense layers (hidden + output)
     int sp_dims[RO_MAX_LAYERS + 1];
@@ -422,6 +420,12 @@ struct RolloutArgs {
     int tp_n;
     int tp_dims[RO_MAX_LAYERS + 1];
     long long tp_w[RO_MAX_LAYERS], tp_b[RO_MAX_LAYERS];
+};
+struct RolloutArgs : EnvModelNet {
+    const float* params;           // population arena (slot stride P), one-step actor at os_off
+    long long P, os_off;
+    long long w_off[EF_MAX_LAYERS + 1], b_off[EF_MAX_LAYERS + 1];
+    int D, A, L;                   // actor hidden width 512
     const float* init_obs;         // [n_envs][D]
     int n_envs, max_steps;
     uint64_t seed;
@@ -433,9 +437,33 @@ struct RolloutArgs {
     float* out_logit;              // null or [nz][n_envs]: termination logit of the last step
     int nz;
     const int* slots;
+    // fqlpop_rollout_record (both null otherwise; zeroed by the host): entry [t] of an env is the
+    // observation before step t + 1 and the clipped action taken there, for the steps it ran
+    float* traj_obs;               // null or [nz][max_steps][n_envs][D]
+    float* traj_act;               // null or [nz][max_steps][n_envs][A]
 };
 bool rollout_supported(int H, int L, int D, int A);
 void launch_rollout(const RolloutArgs& a, hipStream_t s);
+
+// Open-loop replay of recorded actions through the env model (fqlpop_envmodel_replay):
+// for every episode x = init_obs, then per step t < length: x = anchor_obs[t] when
+// anchor_every > 0, t > 0 and t % anchor_every == 0; x' = StatePredictor(x, actions[t]);
+// logit = TerminationPredictor(x'); x = x'.  Block = 16 episodes for all T steps, no actor.
+// The outputs are zeroed by the host; the kernel writes the steps t < length only.
+struct ReplayArgs {
+    EnvModelNet em;
+    int D, A;
+    const float* init_obs;         // [n][D]
+    const float* actions;          // [n][T][A]
+    const float* next_obs;         // null or [n][T][D]: recorded observation after step t
+    const float* anchor_obs;       // null or [n][T][D]: recorded observation before step t
+    const int* lengths;            // null (= T) or [n], each in 1..T
+    int n, T, anchor_every;
+    float* out_logits;             // [n][T]
+    float* out_err;                // null or [n][T][2]: mean_k (s' - next)^2, mean_k |s' - next|
+    float* out_obs;                // null or [n][T][D]: predicted s'
+};
+void launch_replay(const ReplayArgs& a, hipStream_t s);
 
 // The C ABI's thread-local last-error message (runtime.cpp), for entry points
 // defined in other translation units (emtrain.hip).

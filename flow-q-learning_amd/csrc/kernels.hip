@@ -3836,12 +3836,78 @@ DEV void ro_dense_t(const float* __restrict__ W, const float* __restrict__ bias,
         }
     }
 }
-template <bool RELU>
+// KSMAX caps the k-steps whose W fragments a wave holds at once (registers); the MFMA
+// order, and so the result, does not depend on it.
+template <bool RELU, int KSMAX = 32>
 DEV void ro_dense(const float* W, const float* bias, const float* xin, int Wi, int Wo, float* yout, const float* res,
                   int w, int li, int lk) {
-    if (Wi <= 32) ro_dense_t<RELU, 8>(W, bias, xin, Wi, Wo, yout, res, w, li, lk);
-    else if (Wi <= 64) ro_dense_t<RELU, 16>(W, bias, xin, Wi, Wo, yout, res, w, li, lk);
+    if (Wi <= 32 || KSMAX <= 8) ro_dense_t<RELU, 8>(W, bias, xin, Wi, Wo, yout, res, w, li, lk);
+    else if (Wi <= 64 || KSMAX <= 16) ro_dense_t<RELU, 16>(W, bias, xin, Wi, Wo, yout, res, w, li, lk);
     else ro_dense_t<RELU, 32>(W, bias, xin, Wi, Wo, yout, res, w, li, lk);
+}
+
+// One env-model step of a block's 16 columns for replay_kernel: the same statements, in the
+// same order, as the env-model part of rollout_kernel's step (bitwise the same results:
+// tests/test_gpu_replay.py).  rollout_kernel keeps its own inline copy: calling this from
+// it measured 1.3-2.1 % slower on the rollout, so a change to either
+// copy goes into both.  All EF_NW waves; the caller has synchronised on obs_s / act_s:
+//   s'    = Dense(D)(... Dense+ReLU(LayerNorm([s, a]))) + s  -> obs_n  (LDS [D][16])
+//   logit = Dense(1)(... Dense+ReLU(s'))                     -> the returned LDS row [16]
+// bufA / bufB: [RO_MAX_W][16] scratch; lnp: [2][16].  Ends with a block barrier.
+template <int KSMAX>
+DEV const float* em_chain(const EnvModelNet& g, int D, int A, const float* obs_s, const float* act_s, float* obs_n,
+                          float* bufA, float* bufB, float (*lnp)[EF_NC], int tid, int w, int li, int lk) {
+    constexpr int NC = EF_NC, NT = EF_NW * 64;
+    const int K0 = D + A;
+    // ---- state predictor: LayerNorm([s, a]) -> Dense+ReLU ... -> Dense(D) + s
+    if (tid < NC) {
+        float s1 = 0.f, s2 = 0.f;
+        for (int k = 0; k < K0; ++k) {
+            const float x = k < D ? obs_s[k * NC + tid] : act_s[(k - D) * NC + tid];
+            s1 += x;
+            s2 += x * x;
+        }
+        const float mean = s1 / (float)K0;
+        const float var = fmaxf(s2 / (float)K0 - mean * mean, 0.f);
+        lnp[0][tid] = mean;
+        lnp[1][tid] = 1.0f / sqrtf(var + 1e-6f);
+    }
+    __syncthreads();
+    for (int e = tid; e < K0 * NC; e += NT) {
+        const int k = e / NC, c = e % NC;
+        const float x = k < D ? obs_s[e] : act_s[(k - D) * NC + c];
+        bufA[e] = (x - lnp[0][c]) * lnp[1][c] * g.sp[g.sp_ln_scale + k] + g.sp[g.sp_ln_bias + k];
+    }
+    __syncthreads();
+    {
+        float* cur = bufA;
+        float* nxt = bufB;
+        for (int i = 0; i < g.sp_n; ++i) {
+            const bool last = i == g.sp_n - 1;
+            if (last)
+                ro_dense<false, KSMAX>(g.sp + g.sp_w[i], g.sp + g.sp_b[i], cur, g.sp_dims[i], g.sp_dims[i + 1], obs_n,
+                                       obs_s, w, li, lk);
+            else
+                ro_dense<true, KSMAX>(g.sp + g.sp_w[i], g.sp + g.sp_b[i], cur, g.sp_dims[i], g.sp_dims[i + 1], nxt,
+                                      nullptr, w, li, lk);
+            __syncthreads();
+            float* tmp = cur; cur = nxt; nxt = tmp;
+        }
+    }
+    // ---- termination predictor on s' ----------------------------------
+    const float* cur = obs_n;
+    for (int i = 0; i < g.tp_n; ++i) {
+        float* dst = (i & 1) ? bufB : bufA;
+        if (i == g.tp_n - 1)
+            ro_dense<false, KSMAX>(g.tp + g.tp_w[i], g.tp + g.tp_b[i], cur, g.tp_dims[i], g.tp_dims[i + 1], dst,
+                                   nullptr, w, li, lk);
+        else
+            ro_dense<true, KSMAX>(g.tp + g.tp_w[i], g.tp + g.tp_b[i], cur, g.tp_dims[i], g.tp_dims[i + 1], dst,
+                                  nullptr, w, li, lk);
+        __syncthreads();
+        cur = dst;
+    }
+    return cur;
 }
 
 __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_kernel(const RolloutArgs g) {
@@ -3975,6 +4041,18 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_kernel(const RolloutArg
             __syncthreads();
         }
       }
+        if (g.traj_obs) {  // fqlpop_rollout_record: (s, a) of the envs that run this step
+            for (int e = tid; e < (D + A) * NC; e += NT) {
+                const bool ob = e < D * NC;
+                const int R = ob ? D : A, q = ob ? e : e - D * NC;
+                const int c = q / R, k = q % R;
+                if (!done_s[c]) {
+                    const long long row = ((long long)z * g.max_steps + (t - 1)) * g.n_envs + e0 + c;
+                    if (ob) g.traj_obs[row * D + k] = obs_s[k * NC + c];
+                    else g.traj_act[row * A + k] = act_s[k * NC + c];
+                }
+            }
+        }
         // ---- state predictor: LayerNorm([s, a]) -> Dense+ReLU ... -> Dense(D) + s
         if (tid < NC) {
             float s1 = 0.f, s2 = 0.f;
@@ -4065,6 +4143,121 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_kernel(const RolloutArg
 void launch_rollout(const RolloutArgs& a, hipStream_t s) {
     const dim3 grid(((a.n_envs + EF_NC - 1) / EF_NC) * a.nz);
     hipLaunchKernelGGL(rollout_kernel, grid, dim3(EF_NW * 64), 0, s, a);
+}
+
+// ================================================== recorded-action replay ==
+// (ReplayArgs, kernels.h)  One block = 16 episodes (columns) for all T steps; the state
+// stays in LDS and every step is em_chain, the rollout's env-model arithmetic.  Per step a
+// block reads A*16 actions and up to 2*D*16 recorded observations, strided by T*A and
+// T*D floats: the values of step t + 1 are loaded into registers (RP_NV per thread, a
+// looped stage: (A + 2D)*16 exceeds the block's threads) before step t's Dense layers
+// and stored to LDS at the top of step t + 1.  No actor slab: ~77 KB of LDS, so two blocks
+// fit a CU if a wave stays within 128 VGPRs, which the compiler reaches without scratch
+// only with the Dense W fragments in batches of 8 k-steps (RP_KS; the rollout holds 32,
+// which measured under 1.5 % faster per launch here: DESIGN.md section 5).
+constexpr int RP_KS = 8;
+constexpr int RP_WAVES_PER_SIMD = 4;  // two blocks of 8 waves per CU
+constexpr int RP_NV = ((8 + 2 * 64) * EF_NC + EF_NW * 64 - 1) / (EF_NW * 64);
+
+// Staged value e of a step: section (0 action, 1 next_obs, 2 anchor_obs, -1 none), row k
+// and column c.  Within a section k runs fastest, as in memory.
+struct RpWhere {
+    int sec, k, c;
+};
+DEV RpWhere rp_where(const ReplayArgs& g, int e, bool anchor) {
+    const int nA = g.A * EF_NC, nD = g.D * EF_NC, nN = g.next_obs ? nD : 0;
+    RpWhere r;
+    int R, q;
+    if (e < nA) { r.sec = 0; R = g.A; q = e; }
+    else if (e < nA + nN) { r.sec = 1; R = g.D; q = e - nA; }
+    else if (anchor && e < nA + nN + nD) { r.sec = 2; R = g.D; q = e - nA - nN; }
+    else { r.sec = -1; R = 1; q = 0; }
+    r.c = q / R;
+    r.k = q % R;
+    return r;
+}
+DEV bool rp_anchor(const ReplayArgs& g, int t) { return g.anchor_every > 0 && t > 0 && t % g.anchor_every == 0; }
+DEV void rp_load(const ReplayArgs& g, float (&v)[RP_NV], int t, int e0, int tid) {
+    const bool anchor = rp_anchor(g, t);
+#pragma unroll
+    for (int u = 0; u < RP_NV; ++u) {
+        const RpWhere p = rp_where(g, tid + u * EF_NW * 64, anchor);
+        v[u] = 0.f;
+        if (p.sec >= 0 && e0 + p.c < g.n) {
+            const long long row = (long long)(e0 + p.c) * g.T + t;
+            v[u] = p.sec == 0 ? g.actions[row * g.A + p.k]
+                              : (p.sec == 1 ? g.next_obs : g.anchor_obs)[row * g.D + p.k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(EF_NW * 64, RP_WAVES_PER_SIMD) void replay_kernel(const ReplayArgs g) {
+    constexpr int NC = EF_NC, NT = EF_NW * 64;
+    __shared__ __attribute__((aligned(16))) float bufA[RO_MAX_W * NC];
+    __shared__ __attribute__((aligned(16))) float bufB[RO_MAX_W * NC];
+    __shared__ float obs_s[64 * NC], obs_n[64 * NC], ref_s[64 * NC], act_s[8 * NC];
+    __shared__ float lnp[2][NC];
+    __shared__ int len_s[NC];
+
+    const int e0 = blockIdx.x * NC;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lk = lane >> 4;
+    const int D = g.D, A = g.A, T = g.T;
+
+    for (int e = tid; e < D * NC; e += NT) {
+        const int c = e / D, k = e % D;
+        obs_s[k * NC + c] = e0 + c < g.n ? g.init_obs[(long long)(e0 + c) * D + k] : 0.f;
+    }
+    if (tid < NC) len_s[tid] = e0 + tid < g.n ? (g.lengths ? g.lengths[e0 + tid] : T) : 0;
+    float pre[RP_NV];
+    rp_load(g, pre, 0, e0, tid);
+    __syncthreads();
+    int tmax = 0;  // the block stops when all its columns are past their lengths
+    for (int c = 0; c < NC; ++c) tmax = max(tmax, len_s[c]);
+    tmax = min(tmax, T);
+
+    for (int t = 0; t < tmax; ++t) {
+        // ---- stage step t (loaded during step t - 1), then prefetch step t + 1 ----
+        const bool anchor = rp_anchor(g, t);
+#pragma unroll
+        for (int u = 0; u < RP_NV; ++u) {
+            const RpWhere p = rp_where(g, tid + u * NT, anchor);
+            if (p.sec >= 0) (p.sec == 0 ? act_s : p.sec == 1 ? ref_s : obs_s)[p.k * NC + p.c] = pre[u];
+        }
+        if (t + 1 < tmax) rp_load(g, pre, t + 1, e0, tid);
+        __syncthreads();
+        const float* logit = em_chain<RP_KS>(g.em, D, A, obs_s, act_s, obs_n, bufA, bufB, lnp, tid, w, li, lk);
+        // ---- outputs of step t, for the columns still inside their episode ----
+        if (w == 0) {
+            if (tid < NC && t < len_s[tid]) g.out_logits[(long long)(e0 + tid) * T + t] = logit[tid];
+        } else if (w == 1 && g.out_err) {
+            const int c = tid - 64;
+            if (c < NC && t < len_s[c]) {
+                float s2 = 0.f, s1 = 0.f;
+                for (int k = 0; k < D; ++k) {
+                    const float d = obs_n[k * NC + c] - ref_s[k * NC + c];
+                    s2 += d * d;
+                    s1 += fabsf(d);
+                }
+                float* o = g.out_err + ((long long)(e0 + c) * T + t) * 2;
+                o[0] = s2 / (float)D;
+                o[1] = s1 / (float)D;
+            }
+        }
+        for (int e = tid; e < D * NC; e += NT) {
+            const int c = e / D, k = e % D;
+            const float v = obs_n[k * NC + c];
+            if (g.out_obs && t < len_s[c]) g.out_obs[((long long)(e0 + c) * T + t) * D + k] = v;
+            obs_s[k * NC + c] = v;
+        }
+        __syncthreads();
+    }
+}
+
+void launch_replay(const ReplayArgs& a, hipStream_t s) {
+    if (a.n <= 0 || a.T <= 0) return;
+    hipLaunchKernelGGL(replay_kernel, dim3((unsigned)((a.n + EF_NC - 1) / EF_NC)), dim3(EF_NW * 64), 0, s, a);
 }
 
 }  // namespace fq

@@ -336,6 +336,7 @@ struct fqlpop {
     float *sp_params = nullptr, *tp_params = nullptr;
     RolloutArgs em_args{};
     bool em_set = false;
+    double replay_kernel_us = -1.0;  // replay_kernel's time in the last fqlpop_envmodel_replay (HIP events)
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
@@ -2641,9 +2642,11 @@ int fqlpop_set_env_model(fqlpop_t* h, const fqlpop_envmodel_config* cfg, const f
     });
 }
 
-int fqlpop_rollout(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise,
-                   float* out, float* out_obs) {
-    return guard([&] {
+namespace {
+// fqlpop_rollout / fqlpop_rollout_record (the latter with both trace outputs)
+void rollout_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise,
+                 float* out, float* out_obs, float* out_traj_obs, float* out_traj_act) {
+    {
         ARGCHK(h && init_obs && out, "null argument");
         ARGCHK(n_envs > 0 && max_steps > 0, "n_envs and max_steps must be positive");
         if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
@@ -2661,7 +2664,9 @@ int fqlpop_rollout(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps
         r.sp = h->sp_params; r.tp = h->tp_params;
         r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
         r.nz = nz; r.slots = h->slots;
-        float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr;
+        float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_tobs = nullptr,
+              *d_tact = nullptr;
+        const size_t n_traj = (size_t)nz * max_steps * n_envs;
         const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
         HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
         HIPCHK(hipMalloc(&d_out, sizeof(float) * nz * n_envs * 2));
@@ -2671,16 +2676,42 @@ int fqlpop_rollout(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps
             HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
         }
         if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * nz * n_envs * D));
+        if (out_traj_obs) {
+            HIPCHK(hipMalloc(&d_tobs, sizeof(float) * n_traj * D));
+            HIPCHK(hipMalloc(&d_tact, sizeof(float) * n_traj * A));
+            HIPCHK(hipMemsetAsync(d_tobs, 0, sizeof(float) * n_traj * D, h->sM));
+            HIPCHK(hipMemsetAsync(d_tact, 0, sizeof(float) * n_traj * A, h->sM));
+        }
         r.init_obs = d_obs; r.noise = d_noise; r.out = d_out; r.out_obs = d_oobs;
+        r.traj_obs = d_tobs; r.traj_act = d_tact;
         launch_rollout(r, h->sM);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->sM));
         HIPCHK(hipMemcpy(out, d_out, sizeof(float) * nz * n_envs * 2, hipMemcpyDeviceToHost));
         if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * nz * n_envs * D, hipMemcpyDeviceToHost));
-        for (float* p : {d_obs, d_noise, d_out, d_oobs})
+        if (out_traj_obs) {
+            HIPCHK(hipMemcpy(out_traj_obs, d_tobs, sizeof(float) * n_traj * D, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out_traj_act, d_tact, sizeof(float) * n_traj * A, hipMemcpyDeviceToHost));
+        }
+        for (float* p : {d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact})
             if (p) (void)hipFree(p);
+    }
+}
+}  // namespace
+
+int fqlpop_rollout(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise,
+                   float* out, float* out_obs) {
+    return guard([&] { rollout_run(h, init_obs, n_envs, max_steps, seed, noise, out, out_obs, nullptr, nullptr); });
+}
+
+int fqlpop_rollout_record(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                          const float* noise, float* out, float* out_obs, float* out_traj_obs, float* out_traj_act) {
+    return guard([&] {
+        ARGCHK(out_traj_obs && out_traj_act, "null argument");
+        rollout_run(h, init_obs, n_envs, max_steps, seed, noise, out, out_obs, out_traj_obs, out_traj_act);
     });
 }
+
 
 int fqlpop_envmodel_step(fqlpop_t* h, const float* obs, const float* actions, int n, float* next_obs, float* logits) {
     return guard([&] {
@@ -2711,5 +2742,74 @@ int fqlpop_envmodel_step(fqlpop_t* h, const float* obs, const float* actions, in
         HIPCHK(hipMemcpy(next_obs, d_oobs, sizeof(float) * n * D, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(logits, d_logit, sizeof(float) * n, hipMemcpyDeviceToHost));
         for (float* p : {d_obs, d_act, d_out, d_oobs, d_logit}) (void)hipFree(p);
+    });
+}
+
+int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* actions, const float* next_obs,
+                           const float* anchor_obs, const int32_t* lengths, int n, int T, int anchor_every,
+                           float* out_logits, float* out_err, float* out_obs) {
+    return guard([&] {
+        ARGCHK(h && init_obs && actions && out_logits, "null argument");
+        ARGCHK(n > 0 && T > 0, "n and T must be positive");
+        ARGCHK(anchor_every >= 0, "anchor_every must be >= 0");
+        if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
+        ARGCHK(h->D + h->A <= 64 && h->D <= 64 && h->A <= 8, "obs_dim + action_dim must be <= 64");
+        ARGCHK(anchor_every == 0 || anchor_obs, "anchor_every > 0 needs anchor_obs");
+        ARGCHK(!out_err || next_obs, "out_err needs next_obs");
+        if (lengths)
+            for (int e = 0; e < n; ++e) ARGCHK(lengths[e] >= 1 && lengths[e] <= T, "lengths must be in 1..T");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        const size_t D = h->D, A = h->A, nT = (size_t)n * T;
+        ReplayArgs r{};
+        r.em = h->em_args;
+        r.em.sp = h->sp_params; r.em.tp = h->tp_params;
+        r.D = h->D; r.A = h->A; r.n = n; r.T = T; r.anchor_every = anchor_every;
+        float *d_obs = nullptr, *d_act = nullptr, *d_next = nullptr, *d_anchor = nullptr, *d_logit = nullptr,
+              *d_err = nullptr, *d_oobs = nullptr;
+        int* d_len = nullptr;
+        auto up = [&](float** d, const float* src, size_t cnt) {
+            HIPCHK(hipMalloc(d, sizeof(float) * cnt));
+            HIPCHK(hipMemcpy(*d, src, sizeof(float) * cnt, hipMemcpyHostToDevice));
+        };
+        auto zeros = [&](float** d, size_t cnt) {  // the kernel writes the steps t < length only
+            HIPCHK(hipMalloc(d, sizeof(float) * cnt));
+            HIPCHK(hipMemsetAsync(*d, 0, sizeof(float) * cnt, h->sM));
+        };
+        up(&d_obs, init_obs, n * D);
+        up(&d_act, actions, nT * A);
+        if (next_obs) up(&d_next, next_obs, nT * D);
+        if (anchor_every > 0) up(&d_anchor, anchor_obs, nT * D);
+        if (lengths) {
+            HIPCHK(hipMalloc(&d_len, sizeof(int) * n));
+            HIPCHK(hipMemcpy(d_len, lengths, sizeof(int) * n, hipMemcpyHostToDevice));
+        }
+        zeros(&d_logit, nT);
+        if (out_err) zeros(&d_err, nT * 2);
+        if (out_obs) zeros(&d_oobs, nT * D);
+        r.init_obs = d_obs; r.actions = d_act; r.next_obs = d_next; r.anchor_obs = d_anchor; r.lengths = d_len;
+        r.out_logits = d_logit; r.out_err = d_err; r.out_obs = d_oobs;
+        HIPCHK(hipEventRecord(h->ev_t0, h->sM));
+        launch_replay(r, h->sM);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev_t1, h->sM));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+        h->replay_kernel_us = 1000.0 * ms;
+        HIPCHK(hipMemcpy(out_logits, d_logit, sizeof(float) * nT, hipMemcpyDeviceToHost));
+        if (out_err) HIPCHK(hipMemcpy(out_err, d_err, sizeof(float) * nT * 2, hipMemcpyDeviceToHost));
+        if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * nT * D, hipMemcpyDeviceToHost));
+        for (float* p : {d_obs, d_act, d_next, d_anchor, d_logit, d_err, d_oobs})
+            if (p) (void)hipFree(p);
+        if (d_len) (void)hipFree(d_len);
+    });
+}
+
+int fqlpop_envmodel_replay_time(fqlpop_t* h, double* kernel_us) {
+    return guard([&] {
+        ARGCHK(h && kernel_us, "null argument");
+        if (h->replay_kernel_us < 0) throw FqErr{FQLPOP_E_STATE, "no fqlpop_envmodel_replay call yet"};
+        *kernel_us = h->replay_kernel_us;
     });
 }

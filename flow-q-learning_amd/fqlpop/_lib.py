@@ -131,6 +131,11 @@ _SIGS = {
                                             ctypes.c_int64]),
     "fqlpop_rollout": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F, _F, _F]),
     "fqlpop_envmodel_step": (ctypes.c_int, [_P, _F, _F, ctypes.c_int, _F, _F]),
+    "fqlpop_rollout_record": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F, _F, _F, _F,
+                                             _F]),
+    "fqlpop_envmodel_replay": (ctypes.c_int, [_P, _F, _F, _F, _F, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, _F, _F, _F]),
+    "fqlpop_envmodel_replay_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "fqlpop_emtrain_param_count": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_create": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

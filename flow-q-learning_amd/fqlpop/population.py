@@ -292,11 +292,16 @@ class Population:
         check(self.lib.fqlpop_set_env_model(self._h, ctypes.byref(c), fptr(sp), sp.shape[0], fptr(tp), tp.shape[0]))
         self._em_cfg = c
 
-    def rollout(self, init_obs, max_steps: int, seed: int = 0, noise=None, return_obs: bool = False):
+    def rollout(self, init_obs, max_steps: int, seed: int = 0, noise=None, return_obs: bool = False,
+                record: bool = False):
         """World-model evaluation of every ACTIVE member in one launch.
 
         Returns (success [n_active, n_envs], lengths [n_active, n_envs]) and,
-        with return_obs, the observations after the last step [n_active, n_envs, obs]."""
+        with return_obs, the observations after the last step [n_active, n_envs, obs].
+        With record (fqlpop_rollout_record) the transitions follow: traj_obs
+        [n_active, max_steps, n_envs, obs] and traj_act [n_active, max_steps, n_envs, act],
+        entry [t] the observation before step t + 1 and the clipped action taken there, 0
+        from an env's episode length on."""
         obs = _f32(init_obs).reshape(-1, self.cfg.obs_dim)
         n_envs = obs.shape[0]
         na = len(self.active_ids)
@@ -305,13 +310,62 @@ class Population:
             nz = _f32(noise).reshape(na, int(max_steps), n_envs, self.cfg.action_dim)
         out = np.zeros((na, n_envs, 2), dtype=np.float32)
         oobs = np.zeros((na, n_envs, self.cfg.obs_dim), dtype=np.float32) if return_obs else None
-        check(self.lib.fqlpop_rollout(self._h, fptr(obs), n_envs, int(max_steps),
-                                      ctypes.c_uint64(int(seed) & (2**64 - 1)),
-                                      None if nz is None else fptr(nz), fptr(out),
-                                      None if oobs is None else fptr(oobs)))
-        if return_obs:
-            return out[..., 0], out[..., 1], oobs
-        return out[..., 0], out[..., 1]
+        args = (self._h, fptr(obs), n_envs, int(max_steps), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+                None if nz is None else fptr(nz), fptr(out), None if oobs is None else fptr(oobs))
+        res = [out[..., 0], out[..., 1]] + ([oobs] if return_obs else [])
+        if record:
+            tobs = np.zeros((na, int(max_steps), n_envs, self.cfg.obs_dim), dtype=np.float32)
+            tact = np.zeros((na, int(max_steps), n_envs, self.cfg.action_dim), dtype=np.float32)
+            check(self.lib.fqlpop_rollout_record(*args, fptr(tobs), fptr(tact)))
+            res += [tobs, tact]
+        else:
+            check(self.lib.fqlpop_rollout(*args))
+        return tuple(res)
+
+    def envmodel_replay(self, init_obs, actions, next_obs=None, anchor_obs=None, lengths=None,
+                        anchor_every: int = 0, return_obs: bool = False) -> dict:
+        """Open-loop replay of recorded actions through the env model, every episode in one
+        launch (fqlpop_envmodel_replay): init_obs [n, obs], actions [n, T, act], next_obs /
+        anchor_obs None or [n, T, obs] (recorded observation after / before step t), lengths
+        None or [n] in 1..T.  Every anchor_every steps (0: never) the state is reset to
+        anchor_obs[:, t].  Returns {"logits" [n, T]} plus "mse" / "mae" [n, T] (over the
+        observation dims, against next_obs) when next_obs is given and "obs" [n, T, obs]
+        with return_obs; entries at t >= lengths are 0."""
+        D, A = self.cfg.obs_dim, self.cfg.action_dim
+        obs = _f32(init_obs).reshape(-1, D)
+        n = obs.shape[0]
+        act = _f32(actions)
+        if act.ndim != 3 or act.shape[0] != n or act.shape[2] != A:
+            raise ValueError(f"actions must be [n={n}, T, {A}], got {act.shape}")
+        T = act.shape[1]
+
+        def _seq(a, what):
+            if a is None:
+                return None
+            a = _f32(a)
+            if a.shape != (n, T, D):
+                raise ValueError(f"{what} must be [{n}, {T}, {D}], got {a.shape}")
+            return a
+        nxt, anc = _seq(next_obs, "next_obs"), _seq(anchor_obs, "anchor_obs")
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int32)
+            if ln.shape[0] != n:
+                raise ValueError(f"lengths must have {n} entries")
+        logits = np.zeros((n, T), dtype=np.float32)
+        err = np.zeros((n, T, 2), dtype=np.float32) if nxt is not None else None
+        oobs = np.zeros((n, T, D), dtype=np.float32) if return_obs else None
+        opt = lambda a: None if a is None else fptr(a)  # noqa: E731
+        check(self.lib.fqlpop_envmodel_replay(
+            self._h, fptr(obs), fptr(act), opt(nxt), opt(anc),
+            None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            n, T, int(anchor_every), fptr(logits), opt(err), opt(oobs)))
+        out = {"logits": logits}
+        if err is not None:
+            out["mse"], out["mae"] = err[..., 0], err[..., 1]
+        if oobs is not None:
+            out["obs"] = oobs
+        return out
 
     def envmodel_step(self, observations, actions):
         """One state-predictor + termination-predictor step on the GPU:
@@ -325,6 +379,12 @@ class Population:
         logit = np.zeros(n, dtype=np.float32)
         check(self.lib.fqlpop_envmodel_step(self._h, fptr(obs), fptr(act), n, fptr(nxt), fptr(logit)))
         return nxt, logit
+
+    def replay_kernel_us(self) -> float:
+        """GPU time of the replay kernel in the last envmodel_replay call (HIP events)."""
+        us = ctypes.c_double()
+        check(self.lib.fqlpop_envmodel_replay_time(self._h, ctypes.byref(us)))
+        return us.value
 
     # ----------------------------------------------------------------- state
     def get_flat(self, member: int, which: int = STATE_PARAMS) -> np.ndarray:

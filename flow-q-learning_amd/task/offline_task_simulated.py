@@ -108,21 +108,29 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         idx = rng.integers(0, self.initial_observations.shape[0], size=self.num_envs)
         return self.initial_observations[idx].astype(np.float32)
 
-    def evaluate_members(self, population, members, seed: int = 0) -> dict:
+    def evaluate_members(self, population, members, seed: int = 0, record: bool = False) -> dict:
         """Success rate of each member in ``members`` (population slots): every
-        member's episodes in one GPU launch.  Restores the active mask."""
+        member's episodes in one GPU launch.  Restores the active mask.  With
+        ``record`` each member's entry also holds its ``transitions`` (the reference's
+        evaluate_agent second result): (observations [max_steps, n_envs, obs], clipped
+        actions [max_steps, n_envs, act]), 0 from an env's episode length on."""
         self.attach(population)
         saved = population.active.copy()
         mask = np.zeros(population.n, dtype=bool)
         mask[list(members)] = True
         population.set_active(mask)
         try:
-            success, lengths = population.rollout(self.reset_observations(seed), self.max_episode_steps, seed=seed)
+            res = population.rollout(self.reset_observations(seed), self.max_episode_steps, seed=seed, record=record)
         finally:
             population.set_active(saved)
+        success, lengths = res[0], res[1]
         ids = [int(i) for i in np.nonzero(mask)[0]]
-        return {m: {"success": float(success[k].mean()), "episode_length": float(lengths[k].mean())}
-                for k, m in enumerate(ids)}
+        out = {m: {"success": float(success[k].mean()), "episode_length": float(lengths[k].mean())}
+               for k, m in enumerate(ids)}
+        if record:
+            for k, m in enumerate(ids):
+                out[m]["transitions"] = (res[2][k], res[3][k])
+        return out
 
     # ------------------------------------------- reference per-step contract
     def reset(self, seed: int | None = None):

@@ -281,6 +281,43 @@ int fqlpop_rollout(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps
  * (terminated = logit > 0).  Host arrays; synchronises. */
 int fqlpop_envmodel_step(fqlpop_t* h, const float* obs, const float* actions, int n, float* next_obs, float* logits);
 
+/* fqlpop_rollout that also returns the transitions (the reference's evaluate_agent
+ * `transitions`): out_traj_obs host [n_active][max_steps][n_envs][obs_dim] and
+ * out_traj_act host [n_active][max_steps][n_envs][action_dim], both required.  Entry
+ * [t] of an env is the observation before step t + 1 and the clipped action taken
+ * there, for every step the env ran (t < episode length); later entries are 0.
+ * out / out_obs are exactly fqlpop_rollout's for the same arguments. */
+int fqlpop_rollout_record(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                          const float* noise, float* out, float* out_obs, float* out_traj_obs,
+                          float* out_traj_act);
+
+/* Open-loop replay of recorded actions through the env model, all n episodes in one
+ * launch (the reference's "real2sim", evaluator/env_model_evaluator.py:42-56).  Per
+ * episode e: x = init_obs[e]; for t = 0 .. lengths[e]-1: if anchor_every > 0, t > 0 and
+ * t % anchor_every == 0 then x = anchor_obs[e][t]; x' = state_predictor(x,
+ * actions[e][t]); logit = termination_predictor(x'); x = x'.  The replay does not
+ * stop at a predicted termination.  anchor_every 0: fully open loop; 1: the
+ * teacher-forced one-step error; k: the error at horizon k.
+ *   init_obs    [n][obs_dim]       state before step 0
+ *   actions     [n][T][action_dim] recorded actions, used as given (no clip)
+ *   next_obs    NULL or [n][T][obs_dim]  recorded observation after step t
+ *   anchor_obs  NULL or [n][T][obs_dim]  recorded observation before step t
+ *   lengths     NULL (= T for all) or [n], each in 1..T
+ *   out_logits  [n][T]             termination logit of the predicted x'
+ *   out_err     NULL or [n][T][2]  mean_k (x' - next)^2, mean_k |x' - next|; needs next_obs
+ *   out_obs     NULL or [n][T][obs_dim]  predicted x'
+ * Output entries at t >= lengths[e] are 0.  Host arrays; synchronises.  Runs no actor
+ * and reads no member parameters: any hidden_dim; obs_dim + action_dim <= 64,
+ * action_dim <= 8 as fqlpop_envmodel_step. */
+int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* actions, const float* next_obs,
+                           const float* anchor_obs, const int32_t* lengths, int n, int T, int anchor_every,
+                           float* out_logits, float* out_err, float* out_obs);
+
+/* GPU time of the replay kernel in the last successful fqlpop_envmodel_replay call on this
+ * handle, in microseconds (HIP events around the launch; the call's wall time adds the
+ * allocations and copies).  FQLPOP_E_STATE before the first call.  [no reference counterpart] */
+int fqlpop_envmodel_replay_time(fqlpop_t* h, double* kernel_us);
+
 /* ---------------------------------------------------------------------------
  * Env-model trainer: the reference's world-model
  * trainers, one fused GPU step per train_step.
