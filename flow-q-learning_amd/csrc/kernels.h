@@ -400,6 +400,36 @@ struct InitArgs {                 // uniform(-lim, lim) fill of one tensor of on
 };
 void launch_init(const InitArgs& a, hipStream_t s);
 
+// --------------------------------------------------------- member clone ----
+// fqlpop_clone_members: the per-slot state arenas of member src[p] copied into member
+// dst[p] for every pair of the call in ONE launch, grid (chunk, pair), 16 bytes per lane
+// and access.  Every arena's slot stride is a multiple of 64 floats (align_up), so a slot's
+// block is float4-aligned.  The block with chunk 0 of a pair also writes dst's update count,
+// alpha, seed and sampling key.
+constexpr int CLONE_MAX_ARENAS = 8;
+constexpr int CLONE_MAX_PAIRS = 16;   // per launch; the host loops for more
+struct CloneArena {
+    const float* src;             // arena read for a pair whose dst steps (active)
+    const float* src_idle;        // arena read for a pair whose dst does not step: the CURRENT half of a
+                                  // double buffer for both halves of dst (fqlpop_set_active's invariant)
+    float* dst;
+    long long stride;             // floats per slot
+    long long n4;                 // float4s to copy per slot
+};
+struct CloneArgs {
+    CloneArena arena[CLONE_MAX_ARENAS];
+    int n_arenas, n_pairs;
+    int src[CLONE_MAX_PAIRS], dst[CLONE_MAX_PAIRS];
+    unsigned char dst_idle[CLONE_MAX_PAIRS];
+    float alphas[CLONE_MAX_PAIRS];
+    uint64_t seeds[CLONE_MAX_PAIRS], skeys[CLONE_MAX_PAIRS];
+    int* count;
+    float* alpha;
+    uint64_t* seed;
+    uint64_t* skey;
+};
+void launch_clone(const CloneArgs& a, hipStream_t s);
+
 // ------------------------------------------- world-model rollout eval ----
 // evaluator/evaluation.py:75-114 on task/offline_task_simulated.py:85-107 for
 // every active member in ONE launch: per step a = clip(onestep(s, z)),

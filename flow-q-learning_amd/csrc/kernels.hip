@@ -3785,6 +3785,46 @@ void launch_init(const InitArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(init_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
 }
 
+// ============================================================ member clone ==
+// Pure HBM copy: block (chunk, pair) walks every arena of the table with a grid-stride loop
+// over its float4s, four independent 16-byte loads in flight per lane before the stores.
+__global__ __launch_bounds__(256) void clone_members_kernel(const CloneArgs a) {
+    const int p = blockIdx.y;
+    const long long so = a.src[p], dn = a.dst[p];
+    const bool idle = a.dst_idle[p] != 0;
+    const long long step = (long long)gridDim.x * 256;
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    for (int e = 0; e < a.n_arenas; ++e) {
+        const CloneArena& ar = a.arena[e];
+        const float4* __restrict__ s4 = reinterpret_cast<const float4*>((idle ? ar.src_idle : ar.src) + so * ar.stride);
+        float4* __restrict__ d4 = reinterpret_cast<float4*>(ar.dst + dn * ar.stride);
+        const long long n4 = ar.n4;
+        long long i = i0;
+        for (; i + 3 * step < n4; i += 4 * step) {
+            const float4 v0 = s4[i], v1 = s4[i + step], v2 = s4[i + 2 * step], v3 = s4[i + 3 * step];
+            d4[i] = v0; d4[i + step] = v1; d4[i + 2 * step] = v2; d4[i + 3 * step] = v3;
+        }
+        for (; i < n4; i += step) d4[i] = s4[i];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.count[dn] = a.count[so];
+        a.alpha[dn] = a.alphas[p];
+        a.seed[dn] = a.seeds[p];
+        a.skey[dn] = a.skeys[p];
+    }
+}
+
+void launch_clone(const CloneArgs& a, hipStream_t s) {
+    if (a.n_pairs <= 0) return;
+    // about 2048 blocks (8 per CU) whatever the pair count; a block moves at least 4 KB per pass
+    long long most = 0;
+    for (int e = 0; e < a.n_arenas; ++e) most = a.arena[e].n4 > most ? a.arena[e].n4 : most;
+    long long chunks = 2048 / a.n_pairs;
+    if (chunks > (most + 255) / 256) chunks = (most + 255) / 256;
+    if (chunks < 1) chunks = 1;
+    hipLaunchKernelGGL(clone_members_kernel, dim3((unsigned)chunks, (unsigned)a.n_pairs), dim3(256), 0, s, a);
+}
+
 // ============================================== world-model rollout eval ==
 // (RolloutArgs, kernels.h)  One block = 16 envs (columns) of one member for
 // the whole episode; every network runs on LDS-resident activations:

@@ -2416,6 +2416,80 @@ int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int r
     });
 }
 
+// Per-slot buffers of struct fqlpop and what the clone does with them:
+//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count;
+//   written  alpha, seeds, skeys (the values given for dst), h_alpha / h_seeds;
+//   scratch  grads, stats, the network inputs (os_in .. tg_in, cr_in_buf), every Net's U / G /
+//            MU / RS / DU / DH / C1 / C2 / part, q .. dout_os, inj_batch / inj_noise: a step
+//            writes each before it reads it (fqlpop_set_state restores a member without them);
+//            info / vinfo: results of the last step of the slot, not read by a later one;
+//   no slot  split_site / euler_pre0 (per cluster, rewritten by every launch), probe slots.
+// A dst that does not step gets the source's CURRENT parameters (and W^T) in both halves of
+// the double buffers, as fqlpop_set_active leaves such a member: the halves swap under it
+// while the others step, so either may be current when it is activated.
+int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* dst, const float* alphas,
+                         const uint64_t* seeds) {
+    return guard([&] {
+        ARGCHK(h && src && dst && alphas && seeds, "null argument");
+        ARGCHK(n_pairs >= 1, "n_pairs must be >= 1");
+        std::vector<unsigned char> is_src((size_t)h->n, 0), is_dst((size_t)h->n, 0);
+        for (int i = 0; i < n_pairs; ++i) {
+            ARGCHK(src[i] >= 0 && src[i] < h->n && dst[i] >= 0 && dst[i] < h->n, "member index out of range");
+            is_src[src[i]] = 1;
+        }
+        for (int i = 0; i < n_pairs; ++i) {
+            ARGCHK(!is_dst[dst[i]], "a dst member appears twice");
+            ARGCHK(!is_src[dst[i]], "a dst member is also a src");
+            is_dst[dst[i]] = 1;
+        }
+        HIPCHK(hipSetDevice(h->device));
+        // never copy state a failed split launch wrote (no copy, no sync when the word is clear)
+        if (split_error_pending(h)) sync_all_streams(h);
+        (void)absorb_split_error(h);
+        for (int i = 0; i < n_pairs; ++i)
+            if (h->poisoned[src[i]])
+                throw FqErr{FQLPOP_E_STATE, "member " + std::to_string(src[i]) + "'s state was written by a failed "
+                                            "split launch; restore it before cloning from it"};
+        CloneArgs base{};
+        auto arena = [&](const float* s, const float* s_idle, float* d, long long stride) {
+            if (stride <= 0 || d == nullptr) return;
+            ARGCHK(base.n_arenas < CLONE_MAX_ARENAS && stride % 4 == 0, "clone arena table");
+            base.arena[base.n_arenas++] = CloneArena{s, s_idle, d, stride, stride / 4};
+        };
+        arena(h->params, h->params, h->params, h->P);
+        arena(h->params_nx, h->params, h->params_nx, h->P);
+        if (h->stream_bwd) {
+            arena(h->paramsT.p, h->paramsT.p, h->paramsT.p, h->paramsT.ss);
+            arena(h->paramsT_nx.p, h->paramsT.p, h->paramsT_nx.p, h->paramsT_nx.ss);
+        }
+        arena(h->target, h->target, h->target, h->PT);
+        arena(h->adam_m, h->adam_m, h->adam_m, h->P);
+        arena(h->adam_v, h->adam_v, h->adam_v, h->P);
+        base.count = h->count; base.alpha = h->alpha; base.seed = h->seeds; base.skey = h->skeys;
+        // on sM, the stream the step graphs are launched on: after the steps enqueued so far,
+        // before the later ones; every side stream of a step forks from and joins into sM
+        for (int p0 = 0; p0 < n_pairs; p0 += CLONE_MAX_PAIRS) {
+            CloneArgs a = base;
+            a.n_pairs = std::min(CLONE_MAX_PAIRS, n_pairs - p0);
+            for (int i = 0; i < a.n_pairs; ++i) {
+                a.src[i] = src[p0 + i]; a.dst[i] = dst[p0 + i];
+                a.dst_idle[i] = h->active[dst[p0 + i]] ? 0 : 1;
+                a.alphas[i] = alphas[p0 + i]; a.seeds[i] = seeds[p0 + i];
+                a.skeys[i] = sample_key(seeds[p0 + i], alphas[p0 + i]);
+            }
+            launch_clone(a, h->sM);
+        }
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < n_pairs; ++i) {
+            h->h_alpha[dst[i]] = alphas[i];
+            h->h_seeds[dst[i]] = seeds[i];
+            h->poisoned[dst[i]] = 0;  // every arena a failed launch may have written is overwritten
+            h->restored[dst[i]] = 0;
+        }
+        // wt_dirty stays as it is: the W^T arenas are copied with the parameters
+    });
+}
+
 int fqlpop_num_leaves(fqlpop_t* h, int* n) {
     return guard([&] {
         ARGCHK(h && n, "null argument");

@@ -108,6 +108,9 @@ _SIGS = {
     "fqlpop_set_count": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int32]),
     "fqlpop_set_member": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_float, ctypes.c_uint64,
                                          ctypes.c_int]),
+    "fqlpop_clone_members": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int), _F,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
     "fqlpop_num_leaves": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     "fqlpop_leaf_info": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_int64),

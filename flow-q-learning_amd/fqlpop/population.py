@@ -437,6 +437,35 @@ class Population:
         self.alphas[member] = alpha
         self.seeds[member] = seed
 
+    def clone_members(self, src, dst, alphas=None, seeds=None):
+        """Copy the complete training state of member ``src[i]`` into member ``dst[i]`` on
+        the device (fqlpop_clone_members: one launch, stream-ordered between the steps, no
+        host staging; it may return before the copy has run).  ``alphas`` / ``seeds`` None:
+        every dst keeps its OWN current value -- not the source's, which would make the two
+        members draw identical batches forever."""
+        src = np.ascontiguousarray(np.asarray(src, dtype=np.int32).reshape(-1))
+        dst = np.ascontiguousarray(np.asarray(dst, dtype=np.int32).reshape(-1))
+        if src.shape != dst.shape:
+            raise ValueError("src and dst must have the same length")
+
+        def per_pair(given, own, dtype):
+            if given is None:  # (an index out of range: the engine refuses the whole call)
+                given = own[np.clip(dst, 0, self.n - 1)]
+            return np.ascontiguousarray(np.asarray(given, dtype=dtype).reshape(-1))
+        al = per_pair(alphas, self.alphas, np.float32)
+        sd = per_pair(seeds, self.seeds, np.uint64)
+        if al.shape != dst.shape or sd.shape != dst.shape:
+            raise ValueError("alphas and seeds need one entry per pair")
+        ip = ctypes.POINTER(ctypes.c_int)
+        check(self.lib.fqlpop_clone_members(self._h, int(dst.shape[0]), src.ctypes.data_as(ip), dst.ctypes.data_as(ip),
+                                            fptr(al), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        self.alphas[dst] = al
+        self.seeds[dst] = sd
+
+    def clone_member(self, src: int, dst: int, alpha=None, seed=None):
+        """``clone_members`` for one pair."""
+        self.clone_members([src], [dst], None if alpha is None else [alpha], None if seed is None else [seed])
+
     def state_dict(self, member: int) -> dict:
         """Member state in flax ``to_state_dict`` shape: params (incl. target
         critic), Adam (count, mu, nu) -- names follow oracle/fql_oracle.py."""

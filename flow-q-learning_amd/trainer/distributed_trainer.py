@@ -39,12 +39,14 @@ from fqlpop import distributed as D
 from hpo.strategy import HpoStrategy
 from task.task import Task
 from trainer.config import TrainerConfig
-from trainer.trainer import Trainer
+from trainer.trainer import PBT_DISTRIBUTED_MSG, Trainer
 
 
 class DistributedTrainer(Trainer):
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
                  device: int = 0):
+        if hasattr(strategy, "parent_of"):
+            raise NotImplementedError(PBT_DISTRIBUTED_MSG)
         self.rank, self.world_size = D.world()
         self.task = task
         self.strategy = strategy

@@ -38,7 +38,10 @@ def agent_config_for(trainer_config: TrainerConfig, experiment_config: Experimen
 
 class Experiment:
     def __init__(self, task: Task, trainer_config: TrainerConfig, experiment_config: ExperimentConfig,
-                 state_dict: dict | None = None, population=None, member: int | None = None):
+                 state_dict: dict | None = None, population=None, member: int | None = None,
+                 start_step: int = 0):
+        # start_step: the step a fresh experiment begins at (a member cloned from another
+        # one mid-run continues from its parent's step; 0: a new run, as the reference)
         agent_config, tuned = agent_config_for(trainer_config, experiment_config)
         self.agent_config = agent_config
         example = task.sample("train", 1)
@@ -56,7 +59,7 @@ class Experiment:
         if state_dict is None:
             name = "_".join(f"{f}_{v}" for f, v in tuned)
             self.experiment_name = f"{name}_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
-            self.current_step = 0
+            self.current_step = int(start_step)
         else:
             self.agent.from_state_dict(state_dict["agent"])
             self.experiment_name = state_dict["experiment_name"]

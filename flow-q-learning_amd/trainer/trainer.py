@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import random
 import time
+from pathlib import Path
 
 import numpy as np
 
@@ -33,8 +34,15 @@ from trainer.config import TrainerConfig
 from trainer.experiment import Experiment, agent_config_for, train_population
 from dataclasses import asdict
 
+PBT_DISTRIBUTED_MSG = ("strategies that clone members (parent_of: PopulationBasedTraining) run on one GPU only: "
+                       "cross-rank exploit is not implemented; run tune_alpha.py --strategy pbt without "
+                       "torch.distributed.run (WORLD_SIZE = 1)")
+LINEAGE_COLUMNS = ("round", "step", "child", "parent", "parent_alpha", "child_alpha", "parent_score")
+
 
 class Trainer:
+    _clones = False  # (DistributedTrainer refuses cloning strategies)
+
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
                  device: int = 0):
         self.task = task
@@ -42,6 +50,12 @@ class Trainer:
         self.config = config
         self.experiments = {}
         self.member_of = {}
+        # a strategy that exposes parent_of (PopulationBasedTraining) refills the slots of the
+        # candidates it drops with clones of others; everything below keyed on _clones is new
+        # ground, and Identity / SuccessiveHalving runs take none of it
+        self._clones = hasattr(strategy, "parent_of")
+        self.retired_experiments = list(state_dict.get("retired", [])) if state_dict else []
+        self.lineage = list(state_dict.get("lineage", [])) if state_dict else []
         # strategy.sample() is called once on a fresh start (trainer/trainer.py:37-40 of the
         # reference): the same set sizes the population and becomes the candidates, so a
         # strategy whose sample() is stateful or random places the configs it returned
@@ -103,6 +117,15 @@ class Trainer:
         return exp
 
     def state_dict(self) -> dict:
+        sd = self._base_state_dict()
+        if self._clones:
+            # retired experiments are not under "experiments": a resumed trainer allocates
+            # exactly len(candidates) slots
+            sd["retired"] = list(self.retired_experiments)
+            sd["lineage"] = list(self.lineage)
+        return sd
+
+    def _base_state_dict(self) -> dict:
         return {
             "experiments": {cfg: exp.state_dict() for cfg, exp in self.experiments.items()},
             "candidates": self.candidates,
@@ -169,12 +192,76 @@ class Trainer:
             if all(cfg in self.finished_candidates for cfg in self.candidates):
                 break
             new_candidates = self.strategy.sample()
-            for cfg in new_candidates:
-                if cfg not in self.experiments:
-                    self.create_experiment(cfg)
-            for cfg in self.candidates:
-                if cfg not in new_candidates:
-                    self.experiments[cfg].stop()
+            if self._clones:
+                self._exploit(new_candidates)
+            else:
+                for cfg in new_candidates:
+                    if cfg not in self.experiments:
+                        self.create_experiment(cfg)
+                for cfg in self.candidates:
+                    if cfg not in new_candidates:
+                        self.experiments[cfg].stop()
             self.candidates = new_candidates
         for exp in self.experiments.values():
             exp.stop()
+        if self._clones:
+            self._write_lineage()
+
+    # ------------------------------------------------- exploit (strategies with parent_of)
+    def _retire(self, cfg) -> None:
+        """Stop a candidate the strategy dropped and give its slot back."""
+        exp = self.experiments.pop(cfg)
+        exp.stop()
+        self.retired_experiments.append({"experiment_name": exp.experiment_name, "current_step": exp.current_step,
+                                         "logger": exp.logger.state_dict()})
+        self._free_slots.append(self.member_of.pop(cfg))
+
+    def _exploit(self, new_candidates) -> None:
+        """Candidates that dropped out free their slots; each new candidate with a parent
+        takes a freed slot and the parent's complete training state, all of the round in ONE
+        on-device ``clone_members`` call, and continues from the parent's step in lock-step
+        with it."""
+        for cfg in D.ordered(self.candidates):
+            if cfg not in new_candidates:
+                self._retire(cfg)
+        pairs = []
+        for cfg in D.ordered(new_candidates):
+            if cfg in self.experiments:
+                continue
+            parent = self.strategy.parent_of.get(cfg)
+            if parent not in self.experiments:
+                self.create_experiment(cfg)  # no live parent: a fresh member
+                continue
+            if not self._free_slots:
+                raise RuntimeError("population is full: every slot holds a candidate")
+            pairs.append((cfg, parent, self._free_slots.pop(0)))
+        if not pairs:
+            return
+        alphas, seeds = [], []
+        for cfg, _, _ in pairs:
+            acfg, _ = agent_config_for(self.config, cfg)
+            alphas.append(acfg.alpha)
+            seeds.append(acfg.seed if cfg.seed is None else cfg.seed)
+        self.population.clone_members([self.member_of[p] for _, p, _ in pairs], [s for _, _, s in pairs],
+                                      alphas=alphas, seeds=seeds)
+        self.population.sync()
+        rows = {row["child"]: row for row in getattr(self.strategy, "lineage", [])}
+        for cfg, parent, slot in pairs:
+            pexp = self.experiments[parent]
+            self.member_of[cfg] = slot
+            exp = Experiment(self.task, self.config, cfg, population=self.population, member=slot,
+                             start_step=pexp.current_step)
+            self.experiments[cfg] = exp
+            row = rows.get(cfg, {})
+            self.lineage.append({"round": row.get("round", self.round_index), "step": pexp.current_step,
+                                 "child": exp.experiment_name, "parent": pexp.experiment_name,
+                                 "parent_alpha": parent.alpha, "child_alpha": cfg.alpha,
+                                 "parent_score": row.get("parent_score", "")})
+
+    def _write_lineage(self) -> None:
+        path = Path(self.config.save_directory) / self.config.env_name / "pbt_lineage.csv"
+        path.parent.mkdir(parents=True, exist_ok=True)
+        with open(path, "w") as f:
+            f.write(",".join(LINEAGE_COLUMNS) + "\n")
+            for row in self.lineage:
+                f.write(",".join(str(row[k]) for k in LINEAGE_COLUMNS) + "\n")

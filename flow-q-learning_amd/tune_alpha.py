@@ -4,7 +4,10 @@ random.sample(range(10000), --number_of_seeds) after random.seed(--seed);
 --single_experiment --job_id=i runs one (alpha, seed) to completion with a
 checkpoint every eval_interval; otherwise an Identity-strategy Trainer trains
 the whole population (here: all members together on the GPU) and writes
-<save>/<env>/checkpoint.pkl.  --strategy successive_halving selects halving.
+<save>/<env>/checkpoint.pkl.  --strategy successive_halving selects halving,
+--strategy pbt population-based training of alpha (hpo/pbt.py: the worst members are
+replaced by on-device clones of the best under a perturbed alpha, the population stays
+full; one GPU only; <save>/<env>/pbt_lineage.csv records every clone).
 
 Data: --task synthetic (default; SURVEY.md 8d transitions + a toy evaluation
 env), --task npz (local OGBench .npz files under --data_directory) or --task
@@ -30,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from argparser import build_config_from_args, get_argparser  # noqa: E402
 from hpo.identity import Identity  # noqa: E402
+from hpo.pbt import PopulationBasedTraining  # noqa: E402
 from hpo.successive_halving import SuccessiveHalving  # noqa: E402
 from trainer.config import ExperimentConfig  # noqa: E402
 from trainer.experiment import Experiment  # noqa: E402
@@ -63,7 +67,7 @@ def main(argv=None):
     parser.add_argument("--env_model", choices=("baseline", "multistep"), default="multistep")
     parser.add_argument("--max_episode_steps", type=int, default=1000)
     parser.add_argument("--synthetic_rows", type=int, default=100_000)
-    parser.add_argument("--strategy", choices=("identity", "successive_halving"), default="identity")
+    parser.add_argument("--strategy", choices=("identity", "successive_halving", "pbt"), default="identity")
     parser.add_argument("--fraction", type=float, default=0.5)
     parser.add_argument("--history_length", type=int, default=1)
     # SuccessiveHalving's evaluation horizon E (hpo/successive_halving.py milestones).  The
@@ -73,10 +77,18 @@ def main(argv=None):
     # rounds (steps / eval_interval); --halving_horizon selects that reading.  Default: the
     # reference wiring.
     parser.add_argument("--halving_horizon", type=int, default=None)
+    # population-based training (hpo/pbt.py); --history_length is shared with halving
+    parser.add_argument("--pbt_ready_interval", type=int, default=1)
+    parser.add_argument("--pbt_truncation", type=float, default=0.25)
+    parser.add_argument("--pbt_alpha_min", type=float, default=None)
+    parser.add_argument("--pbt_alpha_max", type=float, default=None)
     args = parser.parse_args(argv)
     config = build_config_from_args(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     device = 0
+    if world_size > 1 and args.strategy == "pbt" and not args.single_experiment:
+        from trainer.trainer import PBT_DISTRIBUTED_MSG
+        sys.exit(PBT_DISTRIBUTED_MSG)  # before any process group exists
     if world_size > 1 and not args.single_experiment:
         import torch
         import torch.distributed as dist
@@ -115,6 +127,14 @@ def main(argv=None):
             state = pickle.load(f)
     if args.strategy == "identity":
         strategy = Identity(population=configs, total_evaluations=0, state_dict=state.get("strategy"))
+    elif args.strategy == "pbt":
+        bounds = None
+        if args.pbt_alpha_min is not None or args.pbt_alpha_max is not None:
+            bounds = (args.pbt_alpha_min, args.pbt_alpha_max)
+        strategy = PopulationBasedTraining(population=set(configs), total_evaluations=args.max_evaluations,
+                                           ready_interval=args.pbt_ready_interval, truncation=args.pbt_truncation,
+                                           alpha_bounds=bounds, history_length=args.history_length,
+                                           seed=config.seed, state_dict=state.get("strategy"))
     else:
         horizon = args.max_evaluations if args.halving_horizon is None else args.halving_horizon
         strategy = SuccessiveHalving(population=set(configs), total_evaluations=horizon,

@@ -197,6 +197,19 @@ int fqlpop_set_count(fqlpop_t* h, int member, int32_t count);
  * trainer/config.py:25-28); re-initialises params when reinit != 0. */
 int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int reinit);
 
+/* Copies the complete training state of member src[i] into member dst[i], i < n_pairs, and
+ * gives dst[i] alpha alphas[i] and seed seeds[i]: both parameter buffers and their W^T
+ * copies, the target critic, Adam m and v and the update count, in one device launch on the
+ * stream the steps run on.  Ordered after the steps enqueued before it and before later
+ * ones; no host staging and no synchronisation, so it may return before the copy has run
+ * (fqlpop_sync waits).  FQLPOP_E_ARG, with nothing enqueued, unless n_pairs >= 1, every
+ * index is in range, the dst are pairwise distinct and no dst is also a src; a src may
+ * repeat, and neither has to be active.  A src poisoned by a failed split launch is refused
+ * (FQLPOP_E_STATE); a successful clone restores a poisoned dst as fqlpop_set_member with
+ * reinit does.  [no reference counterpart: PBT exploit] */
+int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* dst,
+                         const float* alphas, const uint64_t* seeds);
+
 /* Leaf table of the flat state: name (e.g. "critic/Dense_0/kernel"), offset
  * and shape (up to 3 dims, ndim returned).  i in [0, fqlpop_num_leaves). */
 int fqlpop_num_leaves(fqlpop_t* h, int* n);
@@ -207,7 +220,7 @@ int fqlpop_leaf_info(fqlpop_t* h, int i, char* name, int name_cap, int64_t* offs
  * members it stepped stay poisoned: fqlpop_step / _step_injected refuse while an active
  * member is poisoned, fqlpop_get_state / _get_count refuse for a poisoned member and
  * fqlpop_read_info while any is, until fqlpop_set_state has restored the member's params,
- * Adam m and Adam v (or fqlpop_set_member reinit).  [EXT: a JAX error surfaces at the next
+ * Adam m and Adam v (or fqlpop_set_member reinit, or fqlpop_clone_members into it).  [EXT: a JAX error surfaces at the next
  * blocking call of the reference's jitted update] */
 int fqlpop_sync(fqlpop_t* h);
 /* Test hook: sets the handle's split-error word exactly as a split launch whose hand-off
