@@ -1805,3 +1805,590 @@ int fqlpop_emtrain_sync(fqlpop_emtrain_t* h) {
 }
 
 }  // extern "C"
+
+// =================================================== initial-observation VAE ==
+// The reference's InitialObservationEnvModel and vae_loss (envmodel/initial_observation.py:
+// 8-78): encoder x -> relu Dense per hidden dim -> (mu, logvar), z = mu + eps exp(logvar / 2),
+// decoder z -> relu Dense per reversed hidden dim -> Dense(obs_dim);
+// loss = (w mean((x - xhat)^2) + kl) / (w + 1), kl = -0.5 mean(1 + logvar - mu^2 - exp(logvar)).
+// A train step is em_vae_grad_kernel (block = 16 minibatch rows, as em_grad_kernel: forward,
+// loss, backward, per-block partial grads, per-block log sums) and em_adam_kernel once per
+// parameter segment (its W^T refresh walks one chain of Dense layers, and the two encoder
+// heads both hang off the last hidden layer): decoder | encoder trunk + mu head | logvar
+// head, contiguous in the flat order (flax path-sorted: decoder/Dense_i/{bias, kernel} ...,
+// then encoder/Dense_i/{bias, kernel} with Dense_n = mu, Dense_{n+1} = logvar).
+//
+// Random numbers (Philox4x32-10, key = (seed lo, seed hi)):
+//   minibatch row of batch position p at update count s  counter (p, s, 0xE7, 0):
+//                                                        row = (x1 << 32 | x0) mod n_rows
+//   eps of batch position p, latent index j, count s     counter (p, j, s, 0x1E5)
+//   z of fqlpop_initobs_sample row r, latent index j     counter (r, j, 0, 0x5A3), key = the
+//                                                        call's seed
+//   normal from a counter's (x0, x1): u1 = ((x0 >> 8) + 1) / 2^24 in (0, 1],
+//   u2 = (x1 >> 8) / 2^24, n = sqrt(-2 ln u1) cos(2 pi u2)   (Box-Muller)
+namespace fq {
+namespace em {
+
+constexpr int VMAXH = 6;   // hidden layers per side
+constexpr int VLOG = 2;    // per-block log sums: squared error, kl terms
+constexpr int VAE_STATIC_LDS = VLOG * R * 4 + R * 8;  // lsum + rowid of em_vae_grad_kernel
+
+struct VaeDense {
+    int K, N, seg;          // in, out, Adam segment
+    long long w, b;         // flat offsets
+};
+struct VaeArgs {
+    int train;
+    int nh, D, L, B, maxd;
+    VaeDense enc[VMAXH], mu, lv, dec[VMAXH + 1];
+    const float* params;
+    const float* wt;                     // W^T copies (same offsets)
+    float* part[3];                      // per segment [blocks][segP]
+    long long segoff[3], segP[3];
+    float* logs;                         // [blocks][VLOG]
+    const float* obs;                    // injected [B][D] or the dataset [n_rows][D]
+    long long n_rows;
+    int injected;
+    const float* eps;                    // injected [B][L] or null (device draw)
+    uint64_t seed;
+    long long step;
+    float w;                             // reconstruction_weight
+};
+struct VaeDecArgs {
+    int nh, D, L;
+    VaeDense dec[VMAXH + 1];
+    const float* params;
+    const float* z;                      // [n][L] or null (device draw)
+    float* out;                          // [n][D]
+    long long n;
+    uint64_t seed;
+};
+
+DEV float nrand(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t salt) {
+    uint32_t x[4] = {c0, c1, c2, salt};
+    philox(x, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u1 = (float)((x[0] >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u2 = (float)(x[1] >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
+DEV float* vae_part(const VaeArgs& a, int seg, long long off) {
+    return a.part[seg] + (long long)blockIdx.x * a.segP[seg] + (off - a.segoff[seg]);
+}
+
+__global__ __launch_bounds__(NT) void em_vae_grad_kernel(const VaeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ float lsum[VLOG][R];
+    __shared__ long long rowid[R];
+    const int tid = threadIdx.x, blk = blockIdx.x;
+    const int nh = a.nh, D = a.D, L = a.L;
+    // LDS: x [D][R] | encoder hidden e_1..e_nh | mu, logvar, eps, z [L][R] | decoder hidden
+    //      d_1..d_nh | xhat [D][R] | gmu, glv [L][R] | gA, gB [maxd][R]
+    float* eact[VMAXH + 1];
+    float* dact[VMAXH + 1];
+    float* p = lds;
+    eact[0] = p;
+    p += D * R;
+    for (int i = 0; i < nh; ++i) {
+        eact[i + 1] = p;
+        p += a.enc[i].N * R;
+    }
+    float* mu = p;
+    float* lv = mu + L * R;
+    float* eps = lv + L * R;
+    float* z = eps + L * R;
+    p = z + L * R;
+    dact[0] = z;
+    for (int i = 0; i < nh; ++i) {
+        dact[i + 1] = p;
+        p += a.dec[i].N * R;
+    }
+    float* xhat = p;
+    float* gmu = xhat + D * R;
+    float* glv = gmu + L * R;
+    float* gA = glv + L * R;
+    float* gB = gA + a.maxd * R;
+    float* x = lds;
+
+    // ---- rows (injected, or Philox-drawn rows of the initial-observation set) and eps
+    if (tid < R) {
+        const int gr = blk * R + tid;
+        long long id = gr;
+        if (!a.injected) {
+            uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE7u, 0u};
+            philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+            id = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)a.n_rows);
+        }
+        rowid[tid] = id;
+    }
+    __syncthreads();
+    for (int t = tid; t < R * D; t += NT) {
+        const int r = t / D, k = t % D;
+        x[k * R + r] = a.obs[rowid[r] * D + k];
+    }
+    for (int t = tid; t < R * L; t += NT) {
+        const int r = t / L, k = t % L;
+        const long long pos = (long long)blk * R + r;
+        eps[k * R + r] = a.eps ? a.eps[pos * L + k]
+                               : nrand(a.seed, (uint32_t)pos, (uint32_t)k, (uint32_t)a.step, 0x1E5u);
+    }
+    __syncthreads();
+
+    // ---- forward
+    const float* P = a.params;
+    for (int i = 0; i < nh; ++i)
+        dense_fwd(P + a.enc[i].w, P + a.enc[i].b, eact[i], a.enc[i].K, a.enc[i].N, eact[i + 1], true);
+    dense_fwd(P + a.mu.w, P + a.mu.b, eact[nh], a.mu.K, L, mu, false);
+    dense_fwd(P + a.lv.w, P + a.lv.b, eact[nh], a.lv.K, L, lv, false);
+    for (int t = tid; t < L * R; t += NT) z[t] = mu[t] + eps[t] * expf(0.5f * lv[t]);
+    __syncthreads();
+    for (int i = 0; i <= nh; ++i)
+        dense_fwd(P + a.dec[i].w, P + a.dec[i].b, dact[i], a.dec[i].K, a.dec[i].N, i < nh ? dact[i + 1] : xhat, i < nh);
+
+    // ---- loss: output gradient (gA [D][R]) and the log sums, one row per thread in a fixed order
+    const float wn = 1.0f / (a.w + 1.0f);
+    const float grec = a.w * wn * 2.0f / ((float)a.B * (float)D);
+    const float gkl = wn / ((float)a.B * (float)L);
+    for (int t = tid; t < D * R; t += NT) gA[t] = grec * (xhat[t] - x[t]);
+    if (tid < R) {
+        float s = 0.f, q = 0.f;
+        for (int k = 0; k < D; ++k) {
+            const float d = xhat[k * R + tid] - x[k * R + tid];
+            s += d * d;
+        }
+        for (int k = 0; k < L; ++k) {
+            const float m = mu[k * R + tid], l = lv[k * R + tid];
+            q += 1.0f + l - m * m - expf(l);
+        }
+        lsum[0][tid] = s;
+        lsum[1][tid] = q;
+    }
+    __syncthreads();
+    if (tid < VLOG) {
+        float s = 0.f;
+        for (int r = 0; r < R; ++r) s += lsum[tid][r];
+        a.logs[(long long)blk * VLOG + tid] = s;
+    }
+    if (!a.train) return;
+
+    // ---- backward: decoder, down to dz
+    float* g = gA;
+    float* gn = gB;
+    for (int i = nh; i >= 0; --i) {
+        const VaeDense& d = a.dec[i];
+        dense_dw(dact[i], g, d.K, d.N, vae_part(a, d.seg, d.w), vae_part(a, d.seg, d.b));
+        dense_dx(a.wt + d.w, g, d.K, d.N, gn, i > 0 ? dact[i] : nullptr);
+        float* tmp = g;
+        g = gn;
+        gn = tmp;
+    }
+    // both heads: dmu = dz + kl', dlogvar = dz eps 0.5 exp(logvar / 2) + kl'
+    g = lds_ptr(g);
+    for (int t = tid; t < L * R; t += NT) {
+        const float l = lv[t];
+        gmu[t] = g[t] + gkl * mu[t];
+        glv[t] = g[t] * eps[t] * 0.5f * expf(0.5f * l) - 0.5f * gkl * (1.0f - expf(l));
+    }
+    __syncthreads();
+    dense_dw(eact[nh], gmu, a.mu.K, L, vae_part(a, a.mu.seg, a.mu.w), vae_part(a, a.mu.seg, a.mu.b));
+    dense_dw(eact[nh], glv, a.lv.K, L, vae_part(a, a.lv.seg, a.lv.w), vae_part(a, a.lv.seg, a.lv.b));
+    dense_dx(a.wt + a.mu.w, gmu, a.mu.K, L, gA, eact[nh]);
+    dense_dx(a.wt + a.lv.w, glv, a.lv.K, L, gB, eact[nh]);
+    for (int t = tid; t < a.mu.K * R; t += NT) gA[t] += gB[t];
+    __syncthreads();
+    // encoder trunk
+    g = gA;
+    gn = gB;
+    for (int i = nh - 1; i >= 0; --i) {
+        const VaeDense& d = a.enc[i];
+        dense_dw(eact[i], g, d.K, d.N, vae_part(a, d.seg, d.w), vae_part(a, d.seg, d.b));
+        if (i > 0) dense_dx(a.wt + d.w, g, d.K, d.N, gn, eact[i]);
+        float* tmp = g;
+        g = gn;
+        gn = tmp;
+    }
+}
+
+// out[r] = decoder(z[r]) for n rows, 16 per block (rows >= n: zero latents, nothing stored)
+__global__ __launch_bounds__(NT) void em_vae_decode_kernel(const VaeDecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, nh = a.nh, D = a.D, L = a.L;
+    const long long row0 = (long long)blockIdx.x * R;
+    // LDS: z [L][R] | d_1..d_nh | out [D][R]
+    float* dact[VMAXH + 2];
+    float* p = lds;
+    dact[0] = p;
+    p += L * R;
+    for (int i = 0; i <= nh; ++i) {
+        dact[i + 1] = p;
+        p += a.dec[i].N * R;
+    }
+    for (int t = tid; t < R * L; t += NT) {
+        const int r = t / L, k = t % L;
+        const long long row = row0 + r;
+        float v = 0.f;
+        if (row < a.n) v = a.z ? a.z[row * L + k] : nrand(a.seed, (uint32_t)row, (uint32_t)k, 0u, 0x5A3u);
+        lds[k * R + r] = v;
+    }
+    __syncthreads();
+    for (int i = 0; i <= nh; ++i)
+        dense_fwd(a.params + a.dec[i].w, a.params + a.dec[i].b, dact[i], a.dec[i].K, a.dec[i].N, dact[i + 1], i < nh);
+    const float* o = lds_ptr(dact[nh + 1]);
+    for (int t = tid; t < R * D; t += NT) {
+        const int r = t / D, k = t % D;
+        if (row0 + r < a.n) a.out[(row0 + r) * D + k] = o[k * R + r];
+    }
+}
+
+}  // namespace em
+}  // namespace fq
+
+struct fqlpop_initobs {
+    fqlpop_initobs_config cfg{};
+    int device = 0;
+    VaeArgs proto{};                     // layer table and segments
+    Net seg_net[3]{};                    // the segments as em_adam_kernel's Dense chains
+    long long P = 0;
+    float *params = nullptr, *wt = nullptr, *m = nullptr, *v = nullptr, *part = nullptr, *logs = nullptr;
+    float *d_obs = nullptr, *i_obs = nullptr, *i_eps = nullptr;
+    float *s_z = nullptr, *s_out = nullptr;  // fqlpop_initobs_sample buffers (grown on demand)
+    long long s_cap = 0;
+    long long n_rows = 0, count = 0;
+    int blocks = 0, lds_bytes = 0, dec_lds = 0;
+    hipStream_t s = nullptr;
+};
+
+namespace {
+// the layer table in flat (flax path-sorted) order; throws E_ARG on a bad shape
+void vae_layout(const fqlpop_initobs_config* c, VaeArgs* a, long long* P) {
+    EMARG(c->obs_dim >= 1 && c->obs_dim <= 4096, "obs_dim must be in 1..4096");
+    EMARG(c->latent_dim >= 1 && c->latent_dim <= 64, "latent_dim must be in 1..64");
+    EMARG(c->num_hidden >= 1 && c->num_hidden <= VMAXH, "num_hidden must be in 1..6");
+    for (int i = 0; i < c->num_hidden; ++i)
+        EMARG(c->hidden_dims[i] >= 1 && c->hidden_dims[i] <= 512, "hidden widths must be in 1..512");
+    const int nh = c->num_hidden, D = c->obs_dim, L = c->latent_dim;
+    *a = VaeArgs{};
+    a->nh = nh; a->D = D; a->L = L;
+    long long o = 0;
+    auto put = [&](VaeDense& d, int K, int N, int seg) {
+        d.K = K; d.N = N; d.seg = seg;
+        d.b = o; o += N;
+        d.w = o; o += (long long)K * N;
+    };
+    a->segoff[0] = 0;
+    int k = L;
+    for (int i = 0; i < nh; ++i) {  // decoder: hidden_dims reversed
+        put(a->dec[i], k, c->hidden_dims[nh - 1 - i], 0);
+        k = c->hidden_dims[nh - 1 - i];
+    }
+    put(a->dec[nh], k, D, 0);
+    a->segP[0] = o;
+    a->segoff[1] = o;
+    k = D;
+    for (int i = 0; i < nh; ++i) {
+        put(a->enc[i], k, c->hidden_dims[i], 1);
+        k = c->hidden_dims[i];
+    }
+    put(a->mu, k, L, 1);
+    a->segP[1] = o - a->segoff[1];
+    a->segoff[2] = o;
+    put(a->lv, k, L, 2);
+    a->segP[2] = o - a->segoff[2];
+    int maxd = std::max(D, L);
+    for (int i = 0; i < nh; ++i) maxd = std::max(maxd, c->hidden_dims[i]);
+    a->maxd = maxd;
+    *P = o;
+}
+
+Net vae_chain(const VaeDense* const* ds, int n, long long base) {
+    Net net{};
+    net.n = n;
+    net.ln_scale = net.ln_bias = -1;
+    for (int i = 0; i < n; ++i) {
+        net.dims[i] = ds[i]->K;
+        net.dims[i + 1] = ds[i]->N;
+        net.w[i] = ds[i]->w - base;
+        net.b[i] = ds[i]->b - base;
+    }
+    return net;
+}
+
+void vae_free(fqlpop_initobs* h) {
+    for (void* p : {(void*)h->params, (void*)h->wt, (void*)h->m, (void*)h->v, (void*)h->part, (void*)h->logs,
+                    (void*)h->d_obs, (void*)h->i_obs, (void*)h->i_eps, (void*)h->s_z, (void*)h->s_out})
+        if (p) (void)hipFree(p);
+    if (h->s) (void)hipStreamDestroy(h->s);
+}
+
+VaeArgs vae_args(fqlpop_initobs* h, bool train, bool injected, const float* eps) {
+    VaeArgs a = h->proto;
+    a.train = train ? 1 : 0;
+    a.B = h->cfg.batch_size;
+    a.params = h->params;
+    a.wt = h->wt;
+    for (int s = 0; s < 3; ++s) a.part[s] = h->part + (long long)h->blocks * a.segoff[s];
+    a.logs = h->logs;
+    a.injected = injected ? 1 : 0;
+    a.obs = injected ? h->i_obs : h->d_obs;
+    a.n_rows = injected ? h->cfg.batch_size : h->n_rows;
+    a.eps = eps;
+    a.seed = h->cfg.seed;
+    a.step = h->count;
+    a.w = h->cfg.reconstruction_weight;
+    return a;
+}
+
+void vae_launch(fqlpop_initobs* h, const VaeArgs& a) {
+    hipLaunchKernelGGL(em_vae_grad_kernel, dim3(h->blocks), dim3(NT), h->lds_bytes, h->s, a);
+    EMCHK(hipGetLastError());
+    if (!a.train) return;
+    // optax.cosine_decay_schedule(init, steps)(count), adam bias correction with count + 1
+    const auto& c = h->cfg;
+    const double cc = (double)std::min<long long>(h->count, c.steps);
+    const float lr = (float)(c.init_lr * 0.5 * (1.0 + std::cos(3.14159265358979323846 * cc / c.steps)));
+    const float bc1 = (float)(1.0 - std::pow(0.9, (double)(h->count + 1)));
+    const float bc2 = (float)(1.0 - std::pow(0.999, (double)(h->count + 1)));
+    for (int s = 0; s < 3; ++s) {
+        const long long off = a.segoff[s];
+        AdamArgsEm ad{};
+        ad.params = h->params + off; ad.wt = h->wt + off; ad.net = h->seg_net[s];
+        ad.m = h->m + off; ad.v = h->v + off; ad.part = a.part[s];
+        ad.P = a.segP[s]; ad.blocks = h->blocks;
+        ad.lr = lr; ad.bc1 = bc1; ad.bc2 = bc2;
+        hipLaunchKernelGGL(em_adam_kernel, dim3((unsigned)((ad.P + 255) / 256)), dim3(256), 0, h->s, ad);
+        EMCHK(hipGetLastError());
+    }
+    ++h->count;
+}
+
+// logs [FQLPOP_INITOBS_LOG_STRIDE] = reconstruction_loss, kl, loss (vae_loss's logs)
+void vae_logs(fqlpop_initobs* h, float* out) {
+    std::vector<float> lg((size_t)VLOG * h->blocks);
+    EMCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
+    EMCHK(hipStreamSynchronize(h->s));
+    double s[VLOG] = {0};
+    for (int b = 0; b < h->blocks; ++b)
+        for (int k = 0; k < VLOG; ++k) s[k] += lg[(size_t)b * VLOG + k];
+    const double B = h->cfg.batch_size, w = h->cfg.reconstruction_weight;
+    const double rec = s[0] / (B * h->cfg.obs_dim), kl = -0.5 * s[1] / (B * h->cfg.latent_dim);
+    for (int k = 0; k < FQLPOP_INITOBS_LOG_STRIDE; ++k) out[k] = 0.f;
+    out[0] = (float)rec;
+    out[1] = (float)kl;
+    out[2] = (float)((w * rec + kl) / (w + 1.0));
+}
+
+void vae_upload(fqlpop_initobs* h, const float* obs, const float* eps) {
+    const long long B = h->cfg.batch_size;
+    EMCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * h->cfg.obs_dim, hipMemcpyHostToDevice, h->s));
+    if (eps) EMCHK(hipMemcpyAsync(h->i_eps, eps, 4 * B * h->cfg.latent_dim, hipMemcpyHostToDevice, h->s));
+}
+}  // namespace
+
+extern "C" {
+
+int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_params) {
+    return em_guard([&] {
+        EMARG(cfg && n_params, "null argument");
+        VaeArgs a;
+        long long P;
+        vae_layout(cfg, &a, &P);
+        *n_params = P;
+    });
+}
+
+int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params, int64_t n_params, int device,
+                          fqlpop_initobs_t** out) {
+    return em_guard([&] {
+        EMARG(cfg && params && out, "null argument");
+        auto h = std::make_unique<fqlpop_initobs>();
+        h->cfg = *cfg;
+        h->device = device;
+        vae_layout(cfg, &h->proto, &h->P);
+        EMARG(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
+        EMARG(cfg->steps > 0, "steps must be > 0");
+        EMARG(cfg->reconstruction_weight >= 0.f, "reconstruction_weight must be >= 0");
+        EMARG(n_params == h->P, "params size mismatch");
+        const VaeArgs& a = h->proto;
+        const int nh = a.nh, D = a.D, L = a.L;
+        // dynamic + static LDS of em_vae_grad_kernel (its layout comment), before any GPU call
+        long long sumh = 0;
+        for (int i = 0; i < nh; ++i) sumh += cfg->hidden_dims[i];
+        const long long fl = (long long)R * (2 * D + 2 * sumh + 6 * L + 2 * a.maxd);
+        if (fl * 4 + VAE_STATIC_LDS > 160 * 1024)
+            throw EmErr{FQLPOP_E_UNSUPPORTED,
+                        "initial-observation VAE: layer widths need " + std::to_string(fl * 4 + VAE_STATIC_LDS) +
+                            " bytes of LDS, the fused step has 163840"};
+        h->lds_bytes = (int)(fl * 4);
+        h->dec_lds = (int)(4LL * R * (L + sumh + D));
+        h->blocks = cfg->batch_size / R;
+        {
+            const VaeDense* ch[VMAXH + 1];
+            for (int i = 0; i <= nh; ++i) ch[i] = &a.dec[i];
+            h->seg_net[0] = vae_chain(ch, nh + 1, a.segoff[0]);
+            for (int i = 0; i < nh; ++i) ch[i] = &a.enc[i];
+            ch[nh] = &a.mu;
+            h->seg_net[1] = vae_chain(ch, nh + 1, a.segoff[1]);
+            ch[0] = &a.lv;
+            h->seg_net[2] = vae_chain(ch, 1, a.segoff[2]);
+        }
+        EMCHK(hipSetDevice(device));
+        const long long P = h->P, B = cfg->batch_size;
+        EMCHK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+        EMCHK(hipMalloc(&h->params, 4 * P));
+        EMCHK(hipMalloc(&h->wt, 4 * P));
+        EMCHK(hipMalloc(&h->m, 4 * P));
+        EMCHK(hipMalloc(&h->v, 4 * P));
+        EMCHK(hipMalloc(&h->part, 4 * P * h->blocks));
+        EMCHK(hipMalloc(&h->logs, 4 * (long long)VLOG * h->blocks));
+        EMCHK(hipMalloc(&h->i_obs, 4 * B * D));
+        EMCHK(hipMalloc(&h->i_eps, 4 * B * L));
+        std::vector<float> wt(params, params + P);
+        auto tr = [&](const VaeDense& d) {
+            for (int k = 0; k < d.K; ++k)
+                for (int f = 0; f < d.N; ++f) wt[d.w + (long long)f * d.K + k] = params[d.w + (long long)k * d.N + f];
+        };
+        for (int i = 0; i <= nh; ++i) tr(a.dec[i]);
+        for (int i = 0; i < nh; ++i) tr(a.enc[i]);
+        tr(a.mu);
+        tr(a.lv);
+        EMCHK(hipMemcpy(h->params, params, 4 * P, hipMemcpyHostToDevice));
+        EMCHK(hipMemcpy(h->wt, wt.data(), 4 * P, hipMemcpyHostToDevice));
+        EMCHK(hipMemset(h->m, 0, 4 * P));
+        EMCHK(hipMemset(h->v, 0, 4 * P));
+        EMCHK(hipMemset(h->logs, 0, 4 * (long long)VLOG * h->blocks));
+        // the limit is the kernel's, not the handle's: the largest any live handle may need
+        static int grad_lds_max = 0, dec_lds_max = 0;
+        grad_lds_max = std::max(grad_lds_max, h->lds_bytes);
+        dec_lds_max = std::max(dec_lds_max, h->dec_lds);
+        EMCHK(hipFuncSetAttribute((const void*)em_vae_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  grad_lds_max));
+        EMCHK(hipFuncSetAttribute((const void*)em_vae_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  dec_lds_max));
+        *out = h.release();
+    });
+}
+
+int fqlpop_initobs_destroy(fqlpop_initobs_t* h) {
+    return em_guard([&] {
+        if (!h) return;
+        (void)hipSetDevice(h->device);
+        if (h->s) (void)hipStreamSynchronize(h->s);
+        vae_free(h);
+        delete h;
+    });
+}
+
+int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_rows) {
+    return em_guard([&] {
+        EMARG(h && obs, "null argument");
+        EMARG(n_rows > 0, "n_rows must be > 0");
+        EMCHK(hipSetDevice(h->device));
+        EMCHK(hipStreamSynchronize(h->s));
+        if (h->d_obs) EMCHK(hipFree(h->d_obs));
+        h->d_obs = nullptr;
+        h->n_rows = 0;
+        EMCHK(hipMalloc(&h->d_obs, 4 * n_rows * h->cfg.obs_dim));
+        EMCHK(hipMemcpy(h->d_obs, obs, 4 * n_rows * h->cfg.obs_dim, hipMemcpyHostToDevice));
+        h->n_rows = n_rows;
+    });
+}
+
+int fqlpop_initobs_step(fqlpop_initobs_t* h, int n_steps) {
+    return em_guard([&] {
+        EMARG(h && n_steps >= 0, "bad argument");
+        if (h->n_rows <= 0) throw EmErr{FQLPOP_E_STATE, "no dataset: call fqlpop_initobs_set_dataset first"};
+        EMCHK(hipSetDevice(h->device));
+        for (int i = 0; i < n_steps; ++i) vae_launch(h, vae_args(h, true, false, nullptr));
+    });
+}
+
+int fqlpop_initobs_step_injected(fqlpop_initobs_t* h, const float* obs, const float* eps) {
+    return em_guard([&] {
+        EMARG(h && obs, "null argument");
+        EMCHK(hipSetDevice(h->device));
+        vae_upload(h, obs, eps);
+        vae_launch(h, vae_args(h, true, true, eps ? h->i_eps : nullptr));
+        EMCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
+    });
+}
+
+int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps, float* logs) {
+    return em_guard([&] {
+        EMARG(h && obs && logs, "null argument");
+        EMARG(eps, "fqlpop_initobs_eval needs eps (an evaluation is a function of its inputs)");
+        EMCHK(hipSetDevice(h->device));
+        vae_upload(h, obs, eps);
+        vae_launch(h, vae_args(h, false, true, h->i_eps));
+        vae_logs(h, logs);
+    });
+}
+
+int fqlpop_initobs_read_logs(fqlpop_initobs_t* h, float* logs) {
+    return em_guard([&] {
+        EMARG(h && logs, "null argument");
+        EMCHK(hipSetDevice(h->device));
+        vae_logs(h, logs);
+    });
+}
+
+int fqlpop_initobs_get_params(fqlpop_initobs_t* h, int which, float* out, int64_t n) {
+    return em_guard([&] {
+        EMARG(h && out, "null argument");
+        EMARG(n == h->P, "params size mismatch");
+        EMARG(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
+        EMCHK(hipSetDevice(h->device));
+        const float* src = which == 0 ? h->params : which == 1 ? h->m : h->v;
+        EMCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
+        EMCHK(hipStreamSynchronize(h->s));
+    });
+}
+
+int fqlpop_initobs_get_count(fqlpop_initobs_t* h, int64_t* count) {
+    return em_guard([&] {
+        EMARG(h && count, "null argument");
+        *count = h->count;
+    });
+}
+
+int fqlpop_initobs_sync(fqlpop_initobs_t* h) {
+    return em_guard([&] {
+        EMARG(h, "null handle");
+        EMCHK(hipSetDevice(h->device));
+        EMCHK(hipStreamSynchronize(h->s));
+    });
+}
+
+int fqlpop_initobs_sample(fqlpop_initobs_t* h, int64_t n, uint64_t seed, const float* z, float* out) {
+    return em_guard([&] {
+        EMARG(h && out, "null argument");
+        EMARG(n >= 1 && n <= (1LL << 31) - R, "n must be in 1..2^31 - 16");
+        EMCHK(hipSetDevice(h->device));
+        const long long D = h->cfg.obs_dim, L = h->cfg.latent_dim;
+        if (n > h->s_cap) {
+            EMCHK(hipStreamSynchronize(h->s));
+            for (float** p : {&h->s_z, &h->s_out}) {
+                if (*p) EMCHK(hipFree(*p));
+                *p = nullptr;
+            }
+            h->s_cap = 0;
+            EMCHK(hipMalloc(&h->s_z, 4 * n * L));
+            EMCHK(hipMalloc(&h->s_out, 4 * n * D));
+            h->s_cap = n;
+        }
+        if (z) EMCHK(hipMemcpyAsync(h->s_z, z, 4 * n * L, hipMemcpyHostToDevice, h->s));
+        VaeDecArgs a{};
+        a.nh = h->proto.nh; a.D = (int)D; a.L = (int)L;
+        for (int i = 0; i <= a.nh; ++i) a.dec[i] = h->proto.dec[i];
+        a.params = h->params;
+        a.z = z ? h->s_z : nullptr;
+        a.out = h->s_out;
+        a.n = n;
+        a.seed = seed;
+        hipLaunchKernelGGL(em_vae_decode_kernel, dim3((unsigned)((n + R - 1) / R)), dim3(NT), h->dec_lds, h->s, a);
+        EMCHK(hipGetLastError());
+        EMCHK(hipMemcpyAsync(out, h->s_out, 4 * n * D, hipMemcpyDeviceToHost, h->s));
+        EMCHK(hipStreamSynchronize(h->s));
+    });
+}
+
+}  // extern "C"

@@ -96,8 +96,19 @@ class EnvModelEvaluator:
         self.episode_length = episode_length
         self.result = None
 
-    def evaluate(self, horizon: int, n_episodes: int = 50, anchor_every: int = 0, seed: int = 0) -> dict:
+    def evaluate(self, horizon: int, n_episodes: int = 50, anchor_every: int = 0, seed: int = 0,
+                 initial_observations: np.ndarray | None = None) -> dict:
+        """``initial_observations`` [n_episodes][obs] (generated starts, e.g. an
+        ``InitialObservationSampler``'s) replace the recorded first observations: the
+        recorded actions are then replayed open loop from starts the recording never saw,
+        so the termination statistics stay meaningful and the MSE / MAE columns measure
+        the distance to the recorded episode, not a model error."""
         ep = episodes_from_dataset(self.dataset, n_episodes, horizon, self.episode_length, seed=seed)
+        if initial_observations is not None:
+            init = np.ascontiguousarray(np.asarray(initial_observations, np.float32))
+            if init.shape != ep["init_obs"].shape:
+                raise ValueError(f"initial_observations have shape {init.shape}, expected {ep['init_obs'].shape}")
+            ep["init_obs"] = init
         r = self.population.envmodel_replay(ep["init_obs"], ep["actions"], next_obs=ep["next_obs"],
                                             anchor_obs=ep["anchor_obs"], lengths=ep["lengths"],
                                             anchor_every=anchor_every)

@@ -72,8 +72,21 @@ class EmTrainConfig(ctypes.Structure):
     ]
 
 
+class InitObsConfig(ctypes.Structure):
+    """Mirror of ``fqlpop_initobs_config`` (include/fqlpop.h)."""
+    _fields_ = [
+        ("obs_dim", ctypes.c_int), ("latent_dim", ctypes.c_int),
+        ("num_hidden", ctypes.c_int), ("hidden_dims", ctypes.c_int * 8),
+        ("batch_size", ctypes.c_int), ("steps", ctypes.c_int),
+        ("init_lr", ctypes.c_float), ("reconstruction_weight", ctypes.c_float),
+        ("seed", ctypes.c_uint64),
+    ]
+
+
 EM_STATE_PREDICTOR, EM_TERMINATION, EM_MULTISTEP = 0, 1, 2
 EM_LOG_STRIDE = 8
+INITOBS_LOG_STRIDE = 4
+INITOBS_LOG_KEYS = ("reconstruction_loss", "kl", "loss")
 _P = ctypes.c_void_p
 _F = ctypes.POINTER(ctypes.c_float)
 _U8 = ctypes.POINTER(ctypes.c_uint8)
@@ -152,6 +165,19 @@ _SIGS = {
     "fqlpop_emtrain_get_params": (ctypes.c_int, [_P, ctypes.c_int, _F, ctypes.c_int64]),
     "fqlpop_emtrain_get_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_sync": (ctypes.c_int, [_P]),
+    "fqlpop_initobs_param_count": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_initobs_create": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), _F, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.POINTER(_P)]),
+    "fqlpop_initobs_destroy": (ctypes.c_int, [_P]),
+    "fqlpop_initobs_set_dataset": (ctypes.c_int, [_P, _F, ctypes.c_int64]),
+    "fqlpop_initobs_step": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fqlpop_initobs_step_injected": (ctypes.c_int, [_P, _F, _F]),
+    "fqlpop_initobs_eval": (ctypes.c_int, [_P, _F, _F, _F]),
+    "fqlpop_initobs_read_logs": (ctypes.c_int, [_P, _F]),
+    "fqlpop_initobs_get_params": (ctypes.c_int, [_P, ctypes.c_int, _F, ctypes.c_int64]),
+    "fqlpop_initobs_get_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_initobs_sync": (ctypes.c_int, [_P]),
+    "fqlpop_initobs_sample": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_uint64, _F, _F]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

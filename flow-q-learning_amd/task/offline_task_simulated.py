@@ -16,7 +16,11 @@ step (evaluator/evaluation.py:75-114).  Here
 
 Initial observations: the reference resets MuJoCo envs (absent here); this
 task draws episode starts of the training dataset, rows 0, 1000, 2000, ...
-as utils/data_loader.py:14-19 (InitialObservationLoader) does.
+as utils/data_loader.py:14-19 (InitialObservationLoader) does, by default; with
+``initial_observations="model"`` it decodes them from the trained initial-observation
+VAE (envmodel/initial_observation.py; explicit ``initial_observation_model=(spec,
+params)`` or ``initial_observation.pt`` + ``initial_observation_config.yaml`` under
+``<save_directory>/<env_name>/env_models``), one seeded GPU launch per reset.
 
 Env model source, in order: explicit ``env_model=(sp_tree, tp_tree)``; the
 reference's files ``<save_directory>/<env_name>/env_models/{model}.pt`` +
@@ -56,7 +60,11 @@ class OfflineTaskWithSimulatedEvaluations(Task):
     def __init__(self, env_name: str = "cube-single-play-singletask-task2-v0", model: str = "multistep",
                  save_directory: Path | None = None, dataset: dict | None = None, val_dataset: dict | None = None,
                  n_rows: int = 100_000, n_val_rows: int = 10_000, num_evaluation_envs: int = 50,
-                 max_episode_steps: int = 1000, env_model=None, seed: int = 0):
+                 max_episode_steps: int = 1000, env_model=None, seed: int = 0,
+                 initial_observations: Literal["dataset", "model"] = "dataset", initial_observation_model=None,
+                 device: int = 0):
+        if initial_observations not in ("dataset", "model"):
+            raise ValueError(f"initial_observations must be 'dataset' or 'model', got {initial_observations!r}")
         self.env_name = env_name
         self.model = model
         self.max_episode_steps = int(max_episode_steps)
@@ -77,6 +85,20 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         self.sp_tree, self.tp_tree = env_model
         self.spec = em.spec_from_trees(self.sp_tree, self.tp_tree)
         self.initial_observations = self.train_dataset["observations"][::1000]
+        self.initial_observation_source = initial_observations
+        self._sampler = None
+        if initial_observations == "model":
+            from envmodel.initial_observation import InitialObservationSampler, load_initial_observation_model
+            if initial_observation_model is None:
+                if save_directory is None:
+                    raise FileNotFoundError("initial_observations='model' needs initial_observation_model=(spec, "
+                                            "params) or save_directory with a trained initial_observation model")
+                initial_observation_model = load_initial_observation_model(
+                    Path(save_directory) / env_name / "env_models")
+            io_spec, io_params = initial_observation_model
+            if io_spec.obs_dim != self.obs_dim:
+                raise ValueError(f"initial-observation model has obs_dim {io_spec.obs_dim}, the task {self.obs_dim}")
+            self._sampler = InitialObservationSampler(io_spec, io_params, device=device)
         self._population = None
         self.current_observations = None
         self.episode_steps = 0
@@ -104,6 +126,10 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         self._population = population
 
     def reset_observations(self, seed: int | None = None) -> np.ndarray:
+        if self._sampler is not None:
+            # decoder(z), z ~ N(0, 1) keyed by the seed (no seed: a fresh one, as default_rng(None))
+            s = int(np.random.SeedSequence().entropy & 0xFFFFFFFFFFFFFFFF) if seed is None else int(seed)
+            return self._sampler.sample(self.num_envs, seed=s)
         rng = np.random.default_rng(seed)
         idx = rng.integers(0, self.initial_observations.shape[0], size=self.num_envs)
         return self.initial_observations[idx].astype(np.float32)
@@ -158,3 +184,6 @@ class OfflineTaskWithSimulatedEvaluations(Task):
 
     def close(self):
         self._population = None
+        if self._sampler is not None:
+            self._sampler.close()
+            self._sampler = None

@@ -8,6 +8,10 @@ Saves ``<save_directory>/<env_name>/env_models/<model>.pt`` (flax
 ``<model>_config.yaml``, as train_env_model.py:127-137 does.  ``multistep`` trains
 the baseline cell through a ``--sequence_length`` scan (BPTT on the GPU) and saves
 it under ``params/ScanCell_0/cell`` like flax's ``nn.scan`` tree.
+``initial_observation`` trains the VAE of envmodel/initial_observation.py on the episode
+starts (InitialObservationLoader), honouring ``--model.hidden_dims``, ``--model.latent_dim``
+and ``--reconstruction_weight``, and saves ``{"params": {"encoder", "decoder"}}`` with
+``hidden_dims`` and ``latent_dim`` in the yaml: the files distribution_visualizer.py:62-99 reads.
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ if HERE not in sys.path:
 
 import envmodel as em  # noqa: E402
 from argparser import build_env_model_config_from_args, get_env_model_argparser  # noqa: E402
+from envmodel import initial_observation as iobs  # noqa: E402
 from envmodel.flax_msgpack import msgpack_serialize  # noqa: E402
 from envmodel.trainer import StatePredictorTrainer, TerminationPredictorTrainer  # noqa: E402
 from task.offline_task_npz import load_npz_dataset  # noqa: E402
@@ -62,6 +67,21 @@ class MultistepLoader:
         start = np.random.randint(0, self.episode_length - self.sequence_length, size=batch_size)
         idx = start[:, None] + np.arange(self.sequence_length)
         return {k: v[ep[:, None], idx] for k, v in self.dataset.items()}
+
+
+class InitialObservationLoader:
+    """utils/data_loader.py:14-22: the episode starts, rows 0, 1000, 2000, ... of every array."""
+
+    episode_length = 1000
+
+    def __init__(self, dataset: dict):
+        idx = np.arange(0, len(dataset["observations"]), self.episode_length)
+        self.indices = idx
+        self.dataset = {k: np.asarray(v)[idx] for k, v in dataset.items() if len(v) == len(dataset["observations"])}
+
+    def sample(self, batch_size: int) -> dict:
+        idx = np.random.randint(len(self.dataset["observations"]), size=batch_size)
+        return {k: v[idx] for k, v in self.dataset.items()}
 
 
 class _CsvRunLogger:
@@ -107,8 +127,18 @@ def main(argv=None):
         spec = em.EnvModelSpec(D, A, em.DEFAULT_HIDDEN, hidden)
         trainer = TerminationPredictorTrainer(spec, em.init_termination_predictor(spec, config.seed),
                                               StepLoader(train), StepLoader(val), config, logger=logger)
+    elif config.model == "initial_observation":
+        io_spec = iobs.InitialObservationSpec(D, int(config.model_config.get("latent_dim", 4)), hidden)
+        trainer = iobs.InitialObservationTrainer(io_spec, iobs.init_initial_observation(io_spec, config.seed),
+                                                 InitialObservationLoader(train), InitialObservationLoader(val),
+                                                 config, logger=logger)
+        trainer.train()
+        iobs.save_initial_observation_model(save_dir, io_spec, trainer.params)
+        trainer.close()
+        return save_dir
     else:
-        raise ValueError(f"unknown model {config.model!r} (baseline, multistep, termination_predictor)")
+        raise ValueError(f"unknown model {config.model!r} (baseline, multistep, termination_predictor, "
+                         "initial_observation)")
     trainer.train()
     with open(save_dir / f"{config.model}_config.yaml", "w") as f:
         yaml.safe_dump({k: list(v) if isinstance(v, tuple) else v for k, v in config.model_config.items()}, f)

@@ -49,7 +49,8 @@ def make_task(args, config):
         return OfflineTaskWithSimulatedEvaluations(
             config.env_name, model=args.env_model, save_directory=config.save_directory if env_dir.exists() else None,
             n_rows=args.synthetic_rows, num_evaluation_envs=config.eval_episodes,
-            max_episode_steps=args.max_episode_steps, seed=config.seed)
+            max_episode_steps=args.max_episode_steps, seed=config.seed,
+            initial_observations=args.initial_observations)
     if args.task == "npz":
         from task.offline_task_npz import OfflineTaskNpz
         return OfflineTaskNpz(config.env_name, config.data_directory)
@@ -65,6 +66,9 @@ def main(argv=None):
     parser.add_argument("--number_of_alphas", type=int, default=1)
     parser.add_argument("--task", choices=("synthetic", "npz", "simulated"), default="synthetic")
     parser.add_argument("--env_model", choices=("baseline", "multistep"), default="multistep")
+    # --task simulated: episode starts from the dataset (rows 0, 1000, ...) or decoded from the
+    # initial-observation VAE saved by train_env_model.py --model initial_observation
+    parser.add_argument("--initial_observations", choices=("dataset", "model"), default="dataset")
     parser.add_argument("--max_episode_steps", type=int, default=1000)
     parser.add_argument("--synthetic_rows", type=int, default=100_000)
     parser.add_argument("--strategy", choices=("identity", "successive_halving", "pbt"), default="identity")

@@ -410,6 +410,72 @@ int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_
 int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count);
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h);
 
+/* ---------------------------------------------------------------------------
+ * Initial-observation VAE (the decoder as a source of episode
+ * starts): InitialObservationEnvModel and vae_loss (envmodel/initial_observation.py:8-78).
+ *   encoder  x -> relu(Dense(h)) for h in hidden_dims -> mu = Dense(latent), logvar =
+ *            Dense(latent), both from the last hidden activation (:8-18)
+ *   decoder  z -> relu(Dense(h)) for h in hidden_dims[::-1] -> Dense(obs_dim) (:21-29, :39)
+ *   forward  z = mu + eps exp(logvar / 2), eps ~ N(0, 1) fresh on every step (:41-52, :62)
+ *   loss     (w mean((x - xhat)^2) + kl) / (w + 1), kl = -0.5 mean(1 + logvar - mu^2 -
+ *            exp(logvar)), w = reconstruction_weight (:65-70)
+ *   optimiser  the reference ships no trainer for this model; the one of its other
+ *            env-model trainers: optax.adam(optax.cosine_decay_schedule(init_lr, steps))
+ *            (envmodel/state_predictor_trainer.py:57-61)
+ * Parameters are one flat vector in flax leaf order (path-sorted): decoder/Dense_i/bias,
+ * decoder/Dense_i/kernel ([in][out]), i = 0..num_hidden, then encoder/Dense_i/..., i =
+ * 0..num_hidden + 1 (Dense_{num_hidden} = mu, Dense_{num_hidden + 1} = logvar).
+ * A step is one fused launch (forward, loss, backward of 16-row blocks) and the Adam
+ * launches, on the handle's one stream.  Random draws: csrc/emtrain.hip, VAE section. */
+#define FQLPOP_INITOBS_LOG_STRIDE 4
+/* logs: [reconstruction_loss, kl, loss] (initial_observation.py:72-76) */
+typedef struct fqlpop_initobs_config {
+    int obs_dim;
+    int latent_dim;                /* --model.latent_dim, 1..64 */
+    int num_hidden;                /* 1..6 */
+    int hidden_dims[8];            /* --model.hidden_dims, each 1..512 (initial_observation.py:35: (128,)) */
+    int batch_size;                /* multiple of 16 */
+    int steps;                     /* cosine decay horizon */
+    float init_lr;
+    float reconstruction_weight;   /* --reconstruction_weight */
+    uint64_t seed;                 /* device row sampling and eps */
+} fqlpop_initobs_config;
+typedef struct fqlpop_initobs fqlpop_initobs_t;
+
+/* FQLPOP_E_ARG on a shape outside the ranges above. */
+int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_params);
+/* model.init + TrainState.create as the other trainers' __init__
+ * (state_predictor_trainer.py:50-61); params: initial flat parameters (host, copied).
+ * FQLPOP_E_UNSUPPORTED, before any GPU call, when the widths do not fit the fused
+ * step's 160 KB of LDS. */
+int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params, int64_t n_params, int device,
+                          fqlpop_initobs_t** out);
+int fqlpop_initobs_destroy(fqlpop_initobs_t* h);
+/* InitialObservationLoader's rows (utils/data_loader.py:14-22), [n_rows][obs_dim], copied:
+ * minibatches are drawn from them on the device, uniform with replacement. */
+int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_rows);
+/* n_steps updates on device-drawn rows and device-drawn eps (vae_loss + adam;
+ * asynchronous).  FQLPOP_E_STATE before fqlpop_initobs_set_dataset. */
+int fqlpop_initobs_step(fqlpop_initobs_t* h, int n_steps);
+/* One update on a host batch obs [batch_size][obs_dim]; eps [batch_size][latent_dim], or
+ * NULL for the device draw of the current update count (initial_observation.py:62: a new
+ * key per call).  Synchronises. */
+int fqlpop_initobs_step_injected(fqlpop_initobs_t* h, const float* obs, const float* eps);
+/* vae_loss's logs of the current parameters on a host batch, no update
+ * (initial_observation.py:55-78); eps is required (FQLPOP_E_ARG if NULL). */
+int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps, float* logs);
+/* Logs of the last step [FQLPOP_INITOBS_LOG_STRIDE]; synchronises. */
+int fqlpop_initobs_read_logs(fqlpop_initobs_t* h, float* logs);
+/* which = FQLPOP_STATE_PARAMS / _ADAM_M / _ADAM_V; the source of initial_observation.pt
+ * (distribution_visualizer.py:62-99 reads params/decoder from it).  Synchronises. */
+int fqlpop_initobs_get_params(fqlpop_initobs_t* h, int which, float* out, int64_t n);
+int fqlpop_initobs_get_count(fqlpop_initobs_t* h, int64_t* count);
+int fqlpop_initobs_sync(fqlpop_initobs_t* h);
+/* out [n][obs_dim] = decoder(z) (distribution_visualizer.py:84-99: decoder.apply on
+ * N(0, 1) latents); z: host [n][latent_dim], or NULL for normals drawn on the device
+ * from (seed, row, latent index).  n >= 1.  Synchronises. */
+int fqlpop_initobs_sample(fqlpop_initobs_t* h, int64_t n, uint64_t seed, const float* z, float* out);
+
 /* Algorithmic GEMM FLOPs of one member-update at the handle's config
  * (SURVEY.md 8d formula). */
 double fqlpop_flops_per_member_step(const fqlpop_config* cfg);
