@@ -475,6 +475,26 @@ struct RolloutArgs : EnvModelNet {
 bool rollout_supported(int H, int L, int D, int A);
 void launch_rollout(const RolloutArgs& a, hipStream_t s);
 
+// fqlpop_rollout_ensemble: the rollout above under n_models resident env models of one
+// config (one leaf layout; nets[k] is that layout with model k's parameter pointers).
+//   mode 0 (FQLPOP_ENS_PER_MODEL): grid (member, model, env tile); the block of (z, k) is
+//     rollout_kernel's block of member z under model k, statement for statement.
+//   mode 1 (FQLPOP_ENS_MIXED): grid (member, env tile); at step t env e steps under model
+//     choice[t - 1][e], or (choice null) under (w0 * n_models) >> 32 of Philox4x32-10 with
+//     counter (e, t, 0x5E12, 0) and the key of the call seed alone.  A step runs the chain
+//     of every model some live column chose and keeps each live column's own s' and
+//     logit; a column that is done keeps its observation.
+// base: sp / tp are null, every other field as for launch_rollout (actions, out_logit and
+// the trace outputs null).
+constexpr int ENS_MAX_MODELS = 16;
+struct RolloutEnsArgs {
+    RolloutArgs base;
+    const EnvModelNet* nets;       // device [n_models]: base's layout with model k's sp / tp
+    int n_models, mode;
+    const int* choice;             // mode 1: null or device [max_steps][n_envs], each in [0, n_models)
+};
+void launch_rollout_ens(const RolloutEnsArgs& a, hipStream_t s);
+
 // Open-loop replay of recorded actions through the env model (fqlpop_envmodel_replay):
 // for every episode x = init_obs, then per step t < length: x = anchor_obs[t] when
 // anchor_every > 0, t > 0 and t % anchor_every == 0; x' = StatePredictor(x, actions[t]);

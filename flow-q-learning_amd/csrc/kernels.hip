@@ -4185,6 +4185,236 @@ void launch_rollout(const RolloutArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(rollout_kernel, grid, dim3(EF_NW * 64), 0, s, a);
 }
 
+// ====================================================== ensemble rollout ==
+// (RolloutEnsArgs, kernels.h)  rollout_kernel's block under several resident env models.
+// The actor part is rollout_kernel's, statement for statement (a change to either goes
+// into both); the env-model step is em_chain, bitwise the rollout's inline copy.
+//   per-model: block (z, k, tile) steps under nets[k] alone, so its results are those of
+//     rollout_kernel's block (z, tile) with model k set.
+//   mixed: block (z, tile); ch_s[c] is column c's model of this step.  The chain runs once
+//     per model that a live column chose (need: a block-uniform mask built from LDS, so
+//     every barrier stays uniform) and each live column keeps the s' and the logit of its
+//     own model in sel_obs / sel_logit.  A done column is never merged: its observation
+//     and result stay, whatever its tile-mates do, so an env's episode does not depend on
+//     n_envs or on its tile.
+// LDS: the rollout's plus sel_obs [64][16], a logit row and a choice row.
+__global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const RolloutEnsArgs ga) {
+    constexpr int H = EF_H, NC = EF_NC, NT = EF_NW * 64, PF = EF_PF;
+    __shared__ __attribute__((aligned(16))) float slab[H * NC + 64];
+    __shared__ __attribute__((aligned(16))) float in0[EF_K0MAX * NC + 64];   // actor input [s; z]
+    __shared__ __attribute__((aligned(16))) float bufA[RO_MAX_W * NC];
+    __shared__ __attribute__((aligned(16))) float bufB[RO_MAX_W * NC];
+    __shared__ float obs_s[64 * NC], obs_n[64 * NC], sel_obs[64 * NC], act_s[8 * NC];
+    __shared__ float hred[EF_NW * 8 * NC];
+    __shared__ float lnp[2][NC];
+    __shared__ float sel_logit[NC];
+    __shared__ int ch_s[NC];
+    __shared__ int done_s[NC];
+    __shared__ float res_s[NC][2];
+    __shared__ int all_done;
+
+    const RolloutArgs& g = ga.base;
+    const EnvModelNet* __restrict__ nets = ga.nets;
+    const bool mixed = ga.mode == 1;
+    const int K = ga.n_models;
+    const int ntile = (g.n_envs + NC - 1) / NC;
+    const int bid = blockIdx.x;
+    const int zk = bid / ntile, e0 = (bid % ntile) * NC;
+    const int z = mixed ? zk : zk / K, km = mixed ? 0 : zk % K;
+    const int slot = g.slots[z];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lk = lane >> 4;
+    const int D = g.D, A = g.A, L = g.L, K0 = D + A;
+    const bool tail0 = K0 > 4 * PF && K0 <= 4 * (PF + 1);  // layer 0 as in euler_flow_kernel
+    const int NS0 = tail0 ? PF : (K0 + 4 * PF - 1) / (4 * PF) * PF;
+    const float* __restrict__ P = g.params + (long long)slot * g.P + g.os_off;
+    const uint64_t key = g.seed ^ (g.member_seeds[slot] * 0x9E3779B97F4A7C15ull);
+
+    for (int e = tid; e < EF_K0MAX * NC + 64; e += NT) in0[e] = 0.f;
+    for (int e = tid; e < 64 * NC; e += NT) {
+        const int k = e / NC, c = e % NC;
+        const float v = (k < D && e0 + c < g.n_envs) ? g.init_obs[(long long)(e0 + c) * D + k] : 0.f;
+        obs_s[e] = v;
+        sel_obs[e] = v;
+    }
+    if (tid < NC) {
+        done_s[tid] = e0 + tid >= g.n_envs;  // padding columns are done from the start
+        res_s[tid][0] = 0.f;
+        res_s[tid][1] = 0.f;
+        sel_logit[tid] = 0.f;
+        ch_s[tid] = 0;
+    }
+    const rsrc_t rW = make_rsrc(P, g.P - g.os_off);
+    const int lo = lk * H + 64 * w + 4 * li;
+    float4 ring[PF];
+#pragma unroll
+    for (int p = 0; p < PF; ++p) ring[p] = bload4(rW, (int)g.w_off[0] + 4 * p * H + lo);
+    float w5r[16];  // head A fragments: W_L[64w + 4s + lk][li], li < A
+#pragma unroll
+    for (int s = 0; s < 16; ++s) w5r[s] = li < A ? P[g.w_off[L] + (64 * w + 4 * s + lk) * A + li] : 0.f;
+    __syncthreads();
+
+    for (int t = 1; t <= g.max_steps; ++t) {
+        // ---- actor input [s; z_t] ----------------------------------------
+        for (int e = tid; e < K0 * NC; e += NT) {
+            const int k = e / NC;
+            if (k < D) in0[e] = obs_s[e];
+        }
+        if (tid < NC * ((A + 1) / 2)) {
+            const int c = tid % NC, q = tid / NC;  // normal pair q: actions 2q, 2q+1
+            float n0, n1;
+            if (g.noise) {
+                const float* nz = g.noise + (((long long)z * g.max_steps + (t - 1)) * g.n_envs + e0 + c) * A;
+                const bool ok = e0 + c < g.n_envs;
+                n0 = ok ? nz[2 * q] : 0.f;
+                n1 = (ok && 2 * q + 1 < A) ? nz[2 * q + 1] : 0.f;
+            } else {
+                uint32_t cc[4] = {(uint32_t)(e0 + c), (uint32_t)t, 0x5E11u, (uint32_t)q};
+                philox4x32_10(cc, (uint32_t)key, (uint32_t)(key >> 32));
+                const float r = sqrtf(-2.0f * logf(u01_open_closed(cc[0])));
+                float sv, cv;
+                sincosf(6.283185307179586f * u01(cc[1]), &sv, &cv);
+                n0 = r * cv;
+                n1 = r * sv;
+            }
+            in0[(D + 2 * q) * NC + c] = n0;
+            if (2 * q + 1 < A) in0[(D + 2 * q + 1) * NC + c] = n1;
+        }
+        if (mixed && tid >= NT - NC) {  // this step's model of each column (the last wave: the first draws the noise)
+            const int c = tid - (NT - NC);
+            int k = 0;
+            if (e0 + c < g.n_envs) {
+                if (ga.choice) {
+                    k = ga.choice[(long long)(t - 1) * g.n_envs + e0 + c];
+                } else {  // the call seed alone: every member meets the same model sequence
+                    uint32_t cc[4] = {(uint32_t)(e0 + c), (uint32_t)t, 0x5E12u, 0u};
+                    philox4x32_10(cc, (uint32_t)g.seed, (uint32_t)(g.seed >> 32));
+                    k = (int)__umulhi(cc[0], (uint32_t)K);
+                }
+            }
+            ch_s[c] = min(max(k, 0), K - 1);
+        }
+        __syncthreads();
+        // ---- actor hidden layers (streamed weights, GELU) -----------------
+        for (int l = 0; l < L; ++l) {
+            const int NS = l == 0 ? NS0 : H / 4;
+            const float* xs = l == 0 ? in0 : slab;
+            const int nl = l + 1 < L ? l + 1 : 0;
+            f32x4 acc[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            float4 bias4[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bias4[r] = bload4(rW, (int)g.b_off[l] + 64 * w + 16 * lk + 4 * r);
+            const bool tl = l == 0 && tail0;
+            __builtin_amdgcn_s_waitcnt(0x0F74);  // vmcnt(4): as euler_flow_kernel (the bias loads in flight)
+            ef_kloop(acc, ring, rW, xs, NS, (int)g.w_off[l], (int)g.w_off[nl], lo, lk, li,
+                     tl ? (int)g.w_off[0] + 4 * PF * H : -1);
+            if (tl) {
+                ef_tail(acc, ring[0], xs, lk, li);
+                __builtin_amdgcn_sched_barrier(0);
+                ring[0] = bload4(rW, (int)g.w_off[nl] + lo);
+            }
+            __syncthreads();  // every wave done reading the slab
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float bb[4] = {bias4[r].x, bias4[r].y, bias4[r].z, bias4[r].w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    slab[(64 * w + 16 * lk + 4 * r + c) * NC + li] = gelu_fast(acc[c][r] + bb[c]);
+            }
+            __syncthreads();
+        }
+        // ---- head: a = clip(W_L^T h + b_L) ---------------------------------
+        {
+            f32x4 hacc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(w5r[s], slab[(64 * w + 4 * s + lk) * NC + li], hacc, 0, 0, 0);
+            if (lk < 2) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) hred[w * 8 * NC + (4 * lk + r) * NC + li] = hacc[r];
+            }
+            __syncthreads();
+            if (tid < A * NC) {
+                const int j = tid / NC;
+                float v = hred[tid];
+#pragma unroll
+                for (int q = 1; q < EF_NW; ++q) v += hred[q * 8 * NC + tid];
+                act_s[tid] = clip1(v + P[g.b_off[L] + j]);
+            }
+            __syncthreads();
+        }
+        // ---- env-model step under every model this step needs --------------
+        unsigned need = 1u << km;
+        if (mixed) {
+            need = 0u;
+            for (int c = 0; c < NC; ++c)
+                if (!done_s[c]) need |= 1u << ch_s[c];
+            need = (unsigned)__builtin_amdgcn_readfirstlane((int)need);
+        }
+        const float* cur = sel_logit;
+        for (int kk = 0; kk < K; ++kk) {
+            if (!((need >> kk) & 1u)) continue;  // a model no live column chose is skipped
+            const float* logit = em_chain<32>(nets[kk], D, A, obs_s, act_s, obs_n, bufA, bufB, lnp, tid, w, li, lk);
+            if (mixed) {
+                for (int e = tid; e < D * NC; e += NT) {
+                    const int c = e % NC;
+                    if (!done_s[c] && ch_s[c] == kk) sel_obs[e] = obs_n[e];
+                }
+                if (tid < NC && !done_s[tid] && ch_s[tid] == kk) sel_logit[tid] = logit[tid];
+                __syncthreads();
+            } else {
+                cur = logit;
+            }
+        }
+        // ---- bookkeeping (evaluate_actor_fn: first terminated / truncated step)
+        if (tid < NC) {
+            if (!done_s[tid]) {
+                if (cur[tid] > 0.f) {
+                    res_s[tid][0] = 1.f;
+                    res_s[tid][1] = (float)t;
+                    done_s[tid] = 1;
+                } else if (t >= g.max_steps) {
+                    res_s[tid][1] = (float)t;
+                    done_s[tid] = 1;
+                }
+            }
+        }
+        {
+            const float* nxt = mixed ? sel_obs : obs_n;
+            for (int e = tid; e < 64 * NC; e += NT) obs_s[e] = nxt[e];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int a = 1;
+            for (int c = 0; c < NC; ++c) a &= done_s[c];
+            all_done = a;
+        }
+        __syncthreads();
+        if (all_done) break;
+    }
+    const long long row = (mixed ? (long long)z : (long long)z * K + km) * g.n_envs + e0;
+    if (tid < NC && e0 + tid < g.n_envs) {
+        float* o = g.out + (row + tid) * 2;
+        o[0] = res_s[tid][0];
+        o[1] = res_s[tid][1];
+    }
+    if (g.out_obs) {
+        for (int e = tid; e < D * NC; e += NT) {
+            const int k = e / NC, c = e % NC;
+            if (e0 + c < g.n_envs) g.out_obs[(row + c) * D + k] = obs_s[e];
+        }
+    }
+}
+
+void launch_rollout_ens(const RolloutEnsArgs& a, hipStream_t s) {
+    const int ntile = (a.base.n_envs + EF_NC - 1) / EF_NC;
+    const dim3 grid((unsigned)(ntile * a.base.nz * (a.mode == 1 ? 1 : a.n_models)));
+    hipLaunchKernelGGL(rollout_ens_kernel, grid, dim3(EF_NW * 64), 0, s, a);
+}
+
 // ================================================== recorded-action replay ==
 // (ReplayArgs, kernels.h)  One block = 16 episodes (columns) for all T steps; the state
 // stays in LDS and every step is em_chain, the rollout's env-model arithmetic.  Per step a

@@ -337,6 +337,13 @@ struct fqlpop {
     RolloutArgs em_args{};
     bool em_set = false;
     double replay_kernel_us = -1.0;  // replay_kernel's time in the last fqlpop_envmodel_replay (HIP events)
+    // env-model ensemble (fqlpop_set_env_model_ensemble / fqlpop_rollout_ensemble): its own
+    // storage, apart from the single model's above
+    float *ens_sp = nullptr, *ens_tp = nullptr;   // [ens_n][n_sp], [ens_n][n_tp]
+    EnvModelNet* ens_nets = nullptr;              // device [ens_n]: the layout with model k's pointers
+    RolloutArgs ens_args{};                       // the shared leaf layout
+    int ens_n = 0;
+    double ens_kernel_us = -1.0;   // rollout_ens_kernel's time in the last fqlpop_rollout_ensemble (HIP events)
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
@@ -2076,7 +2083,7 @@ int fqlpop_destroy(fqlpop_t* h) {
         for (void* p : {(void*)h->params_buf[0], (void*)h->params_buf[1], (void*)h->res_ids, (void*)h->grads, (void*)h->adam_m, (void*)h->adam_v, (void*)h->target,
                         (void*)h->count, (void*)h->seeds, (void*)h->skeys, (void*)h->alpha, (void*)h->slots, (void*)h->stats,
                         (void*)h->chunks, (void*)h->chunk_leaf, (void*)h->leaf_first, (void*)h->sp_params,
-                        (void*)h->tp_params})
+                        (void*)h->tp_params, (void*)h->ens_sp, (void*)h->ens_tp, (void*)h->ens_nets})
             if (p) (void)hipFree(p);
         for (auto& d : h->ds)
             for (float* p : {d.obs, d.act, d.rew, d.mask, d.nobs})
@@ -2885,5 +2892,117 @@ int fqlpop_envmodel_replay_time(fqlpop_t* h, double* kernel_us) {
         ARGCHK(h && kernel_us, "null argument");
         if (h->replay_kernel_us < 0) throw FqErr{FQLPOP_E_STATE, "no fqlpop_envmodel_replay call yet"};
         *kernel_us = h->replay_kernel_us;
+    });
+}
+
+/* ---- env-model ensemble ---------------------------------------------------------------- */
+int fqlpop_set_env_model_ensemble(fqlpop_t* h, const fqlpop_envmodel_config* cfg, int n_models,
+                                  const float* sp_params, int64_t n_sp, const float* tp_params, int64_t n_tp) {
+    return guard([&] {
+        ARGCHK(h && cfg && sp_params && tp_params, "null argument");
+        ARGCHK(n_models >= 1 && n_models <= FQLPOP_ENS_MAX_MODELS, "n_models must be in 1..16");
+        ARGCHK(cfg->obs_dim == h->D && cfg->action_dim == h->A, "env-model obs/action dims differ from the agent's");
+        std::vector<int> sp, tp;
+        envmodel_dims(cfg, sp, tp);
+        RolloutArgs r{};
+        const long long nsp = envmodel_layout(sp, true, r.sp_w, r.sp_b, &r.sp_ln_bias, &r.sp_ln_scale);
+        long long lb = 0, ls = 0;
+        const long long ntp = envmodel_layout(tp, false, r.tp_w, r.tp_b, &lb, &ls);
+        ARGCHK(n_sp == nsp && n_tp == ntp, "env-model parameter count mismatch (fqlpop_envmodel_param_count)");
+        r.sp_n = (int)sp.size() - 1;
+        r.tp_n = (int)tp.size() - 1;
+        for (size_t i = 0; i < sp.size(); ++i) r.sp_dims[i] = sp[i];
+        for (size_t i = 0; i < tp.size(); ++i) r.tp_dims[i] = tp[i];
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipDeviceSynchronize());
+        for (void* p : {(void*)h->ens_sp, (void*)h->ens_tp, (void*)h->ens_nets})
+            if (p) (void)hipFree(p);
+        h->ens_sp = h->ens_tp = nullptr;
+        h->ens_nets = nullptr;
+        h->ens_n = 0;
+        HIPCHK(hipMalloc(&h->ens_sp, sizeof(float) * nsp * n_models));
+        HIPCHK(hipMalloc(&h->ens_tp, sizeof(float) * ntp * n_models));
+        HIPCHK(hipMalloc(&h->ens_nets, sizeof(EnvModelNet) * n_models));
+        HIPCHK(hipMemcpy(h->ens_sp, sp_params, sizeof(float) * nsp * n_models, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->ens_tp, tp_params, sizeof(float) * ntp * n_models, hipMemcpyHostToDevice));
+        std::vector<EnvModelNet> nets((size_t)n_models, static_cast<const EnvModelNet&>(r));
+        for (int k = 0; k < n_models; ++k) {
+            nets[k].sp = h->ens_sp + (long long)k * nsp;
+            nets[k].tp = h->ens_tp + (long long)k * ntp;
+        }
+        HIPCHK(hipMemcpy(h->ens_nets, nets.data(), sizeof(EnvModelNet) * n_models, hipMemcpyHostToDevice));
+        h->ens_args = r;
+        h->ens_n = n_models;
+    });
+}
+
+int fqlpop_rollout_ensemble(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                            const float* noise, int mode, const int32_t* choice, float* out, float* out_obs) {
+    return guard([&] {
+        ARGCHK(h && init_obs && out, "null argument");
+        ARGCHK(n_envs > 0 && max_steps > 0, "n_envs and max_steps must be positive");
+        ARGCHK(mode == FQLPOP_ENS_PER_MODEL || mode == FQLPOP_ENS_MIXED, "mode must be FQLPOP_ENS_PER_MODEL or FQLPOP_ENS_MIXED");
+        ARGCHK(!(choice && mode == FQLPOP_ENS_PER_MODEL), "choice is for FQLPOP_ENS_MIXED only");
+        if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
+        const int K = h->ens_n;
+        const size_t n_choice = (size_t)max_steps * n_envs;
+        if (choice)
+            for (size_t i = 0; i < n_choice; ++i)
+                ARGCHK(choice[i] >= 0 && choice[i] < K, "choice entries must be in [0, n_models)");
+        if (!rollout_supported(h->H, h->L, h->D, h->A))
+            throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+        if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        const int nz = h->nz, D = h->D, A = h->A;
+        if (nz == 0) return;
+        RolloutEnsArgs e{};
+        RolloutArgs& r = e.base;
+        r = h->ens_args;
+        r.params = h->params; r.P = h->P; r.os_off = h->os.off;
+        for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
+        r.D = D; r.A = A; r.L = h->L;
+        r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
+        r.nz = nz; r.slots = h->slots;
+        e.nets = h->ens_nets; e.n_models = K; e.mode = mode;
+        const size_t rows = (size_t)nz * (mode == FQLPOP_ENS_PER_MODEL ? K : 1) * n_envs;
+        const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
+        float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr;
+        int* d_choice = nullptr;
+        HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
+        HIPCHK(hipMalloc(&d_out, sizeof(float) * rows * 2));
+        HIPCHK(hipMemcpy(d_obs, init_obs, sizeof(float) * n_envs * D, hipMemcpyHostToDevice));
+        if (noise) {
+            HIPCHK(hipMalloc(&d_noise, sizeof(float) * n_noise));
+            HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
+        }
+        if (choice) {
+            HIPCHK(hipMalloc(&d_choice, sizeof(int) * n_choice));
+            HIPCHK(hipMemcpy(d_choice, choice, sizeof(int) * n_choice, hipMemcpyHostToDevice));
+        }
+        if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * rows * D));
+        r.init_obs = d_obs; r.noise = d_noise; r.out = d_out; r.out_obs = d_oobs;
+        e.choice = d_choice;
+        HIPCHK(hipEventRecord(h->ev_t0, h->sM));
+        launch_rollout_ens(e, h->sM);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev_t1, h->sM));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+        h->ens_kernel_us = 1000.0 * ms;
+        HIPCHK(hipMemcpy(out, d_out, sizeof(float) * rows * 2, hipMemcpyDeviceToHost));
+        if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * rows * D, hipMemcpyDeviceToHost));
+        for (float* p : {d_obs, d_noise, d_out, d_oobs})
+            if (p) (void)hipFree(p);
+        if (d_choice) (void)hipFree(d_choice);
+    });
+}
+
+int fqlpop_rollout_ensemble_time(fqlpop_t* h, double* kernel_us) {
+    return guard([&] {
+        ARGCHK(h && kernel_us, "null argument");
+        if (h->ens_kernel_us < 0) throw FqErr{FQLPOP_E_STATE, "no fqlpop_rollout_ensemble call yet"};
+        *kernel_us = h->ens_kernel_us;
     });
 }

@@ -84,6 +84,8 @@ class InitObsConfig(ctypes.Structure):
 
 
 EM_STATE_PREDICTOR, EM_TERMINATION, EM_MULTISTEP = 0, 1, 2
+ENS_PER_MODEL, ENS_MIXED = 0, 1
+ENS_MAX_MODELS = 16
 EM_LOG_STRIDE = 8
 INITOBS_LOG_STRIDE = 4
 INITOBS_LOG_KEYS = ("reconstruction_loss", "kl", "loss")
@@ -152,6 +154,11 @@ _SIGS = {
     "fqlpop_envmodel_replay": (ctypes.c_int, [_P, _F, _F, _F, _F, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, _F, _F, _F]),
     "fqlpop_envmodel_replay_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "fqlpop_set_env_model_ensemble": (ctypes.c_int, [_P, ctypes.POINTER(EnvModelConfig), ctypes.c_int, _F,
+                                                     ctypes.c_int64, _F, ctypes.c_int64]),
+    "fqlpop_rollout_ensemble": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int32), _F, _F]),
+    "fqlpop_rollout_ensemble_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "fqlpop_emtrain_param_count": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_create": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

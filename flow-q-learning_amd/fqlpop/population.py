@@ -386,6 +386,77 @@ class Population:
         check(self.lib.fqlpop_envmodel_replay_time(self._h, ctypes.byref(us)))
         return us.value
 
+    # --------------------------------------------------- world-model ensemble
+    def set_env_model_ensemble(self, sp_flats, tp_flats, sp_hidden=(128, 256, 128), tp_hidden=(128, 128)):
+        """Upload K env models of one shape (fqlpop_set_env_model_ensemble): sp_flats a
+        sequence of K flat state-predictor vectors, tp_flats K flat termination-predictor
+        vectors or a single one, repeated K times.  Stored apart from set_env_model's model."""
+        c = _lib.EnvModelConfig()
+        c.obs_dim, c.action_dim = self.cfg.obs_dim, self.cfg.action_dim
+        c.sp_num_hidden = len(sp_hidden)
+        c.tp_num_hidden = len(tp_hidden)
+        for i, d in enumerate(sp_hidden):
+            c.sp_hidden[i] = int(d)
+        for i, d in enumerate(tp_hidden):
+            c.tp_hidden[i] = int(d)
+        sps = [_f32(s).reshape(-1) for s in sp_flats]
+        k = len(sps)
+        if isinstance(tp_flats, np.ndarray) and tp_flats.ndim == 1:
+            tp_flats = [tp_flats]
+        tps = [_f32(t).reshape(-1) for t in tp_flats]
+        if len(tps) == 1 and k > 1:
+            tps = tps * k
+        if len(tps) != k:
+            raise ValueError(f"{k} state predictors but {len(tps)} termination predictors")
+        n_sp = sps[0].shape[0] if sps else 0
+        n_tp = tps[0].shape[0] if tps else 0
+        if any(s.shape[0] != n_sp for s in sps) or any(t.shape[0] != n_tp for t in tps):
+            raise ValueError("the models of an ensemble must share one shape")
+        sp = _f32(np.stack(sps)) if sps else np.zeros((1, 1), np.float32)
+        tp = _f32(np.stack(tps)) if tps else np.zeros((1, 1), np.float32)
+        check(self.lib.fqlpop_set_env_model_ensemble(self._h, ctypes.byref(c), k, fptr(sp), n_sp, fptr(tp), n_tp))
+        self._ens_n = k
+
+    def rollout_ensemble(self, init_obs, max_steps: int, seed: int = 0, mode: str = "per_model", noise=None,
+                         choice=None, return_obs: bool = False):
+        """World-model evaluation of every ACTIVE member under the ensemble in one launch
+        (fqlpop_rollout_ensemble).  noise None or [n_active, max_steps, n_envs, act], shared
+        by all models.
+
+        mode "per_model": every member under every model; returns (success, lengths), each
+        [n_active, K, n_envs], slice k bit for bit ``rollout`` after ``set_env_model(k)``.
+        mode "mixed" (trajectory sampling): at step t env e steps under model
+        choice[t - 1, e] (int [max_steps, n_envs]; None: drawn on the device from ``seed``,
+        the same sequence for every member); returns (success, lengths) [n_active, n_envs].
+        With return_obs the observations after the last step follow."""
+        modes = {"per_model": _lib.ENS_PER_MODEL, "mixed": _lib.ENS_MIXED}
+        if mode not in modes:
+            raise ValueError(f"mode must be 'per_model' or 'mixed', got {mode!r}")
+        obs = _f32(init_obs).reshape(-1, self.cfg.obs_dim)
+        n_envs = obs.shape[0]
+        na = len(self.active_ids)
+        nz = None
+        if noise is not None:
+            nz = _f32(noise).reshape(na, int(max_steps), n_envs, self.cfg.action_dim)
+        ch = None
+        if choice is not None:
+            ch = np.ascontiguousarray(np.asarray(choice), dtype=np.int32).reshape(int(max_steps), n_envs)
+        lead = (na, getattr(self, "_ens_n", 1)) if mode == "per_model" else (na,)
+        out = np.zeros(lead + (n_envs, 2), dtype=np.float32)
+        oobs = np.zeros(lead + (n_envs, self.cfg.obs_dim), dtype=np.float32) if return_obs else None
+        check(self.lib.fqlpop_rollout_ensemble(
+            self._h, fptr(obs), n_envs, int(max_steps), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+            None if nz is None else fptr(nz), modes[mode],
+            None if ch is None else ch.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            fptr(out), None if oobs is None else fptr(oobs)))
+        return (out[..., 0], out[..., 1]) + ((oobs,) if return_obs else ())
+
+    def ensemble_kernel_us(self) -> float:
+        """GPU time of the kernel of the last rollout_ensemble call (HIP events)."""
+        us = ctypes.c_double()
+        check(self.lib.fqlpop_rollout_ensemble_time(self._h, ctypes.byref(us)))
+        return us.value
+
     # ----------------------------------------------------------------- state
     def get_flat(self, member: int, which: int = STATE_PARAMS) -> np.ndarray:
         flat = np.zeros(self.state_size, dtype=np.float32)

@@ -27,6 +27,15 @@ reference's files ``<save_directory>/<env_name>/env_models/{model}.pt`` +
 ``{model}_config.yaml`` and ``termination_predictor.*`` (utils/envmodel.py:10-49;
 flax msgpack read by envmodel.flax_msgpack, yaml with SafeLoader); otherwise
 a seeded synthetic model of the default shape.
+
+Ensembles: ``env_models=[(sp_tree, tp_tree), ...]`` (or ``ensemble_size=K`` with
+``save_directory``: the files ``{model}_ens<k>.pt`` written by ``train_env_model.py
+--ensemble_size K``) scores every member under K models of one shape in one launch
+(``Population.rollout_ensemble``).  ``ensemble_score`` picks the score that the
+strategies see: the ``mean`` or the ``min`` of the per-model success rates, or the
+success rate of ``mixed`` episodes that draw a model afresh at every step; the spread
+over the models goes next to it (``success_std`` / ``success_min`` / ``success_max``).
+``reset`` / ``step`` keep using model 0.
 """
 from __future__ import annotations
 
@@ -56,13 +65,64 @@ def load_reference_env_model(save_directory: Path, env_name: str, model: str):
     return trees[0], trees[1]
 
 
+ENSEMBLE_SCORES = ("mean", "min", "mixed")
+
+
+def ensemble_model_names(directory: Path, model: str, ensemble_size: int):
+    """[(state predictor name, termination predictor name)] of the K members saved by
+    ``train_env_model.py --ensemble_size K`` under ``directory``: ``{model}_ens<k>`` with
+    ``termination_predictor_ens<k>`` if all K of those exist, else the shared
+    ``termination_predictor``.  FileNotFoundError names the first missing file."""
+    d = Path(directory)
+    own_tp = all((d / f"termination_predictor_ens{k}.pt").exists() for k in range(ensemble_size))
+    names = [(f"{model}_ens{k}", f"termination_predictor_ens{k}" if own_tp else "termination_predictor")
+             for k in range(ensemble_size)]
+    for pair in names:
+        for name in pair:
+            if not (d / f"{name}.pt").exists():
+                raise FileNotFoundError(f"env model ensemble member {name}.pt not found under {d}")
+    return names
+
+
+def load_env_model_ensemble(save_directory: Path, env_name: str, model: str, ensemble_size: int):
+    """[(sp_tree, tp_tree)] * K from ``<save_directory>/<env_name>/env_models`` (ensemble_model_names)."""
+    d = Path(save_directory) / env_name / "env_models"
+    return [(em.load_flax_msgpack(d / f"{sp}.pt"), em.load_flax_msgpack(d / f"{tp}.pt"))
+            for sp, tp in ensemble_model_names(d, model, ensemble_size)]
+
+
+def ensemble_scores(per_model_success, per_model_length, score: str = "mean", mixed=None) -> dict:
+    """One member's evaluation entry from its per-model success rates and mean episode
+    lengths ([K] each): ``success`` is their mean, their minimum, or (``mixed``: a
+    (success rate, mean length) pair) the mixed-mode rate; ``success_std`` (population
+    std), ``success_min`` and ``success_max`` are over the K per-model rates.  Scalars only."""
+    if score not in ENSEMBLE_SCORES:
+        raise ValueError(f"ensemble_score must be one of {ENSEMBLE_SCORES}, got {score!r}")
+    rates = [float(v) for v in per_model_success]
+    lens = [float(v) for v in per_model_length]
+    if score == "mixed":
+        if mixed is None:
+            raise ValueError("ensemble_score 'mixed' needs the mixed-mode result")
+        success, length = float(mixed[0]), float(mixed[1])
+    elif score == "min":
+        k = int(np.argmin(rates))
+        success, length = rates[k], lens[k]
+    else:
+        success, length = float(np.mean(rates)), float(np.mean(lens))
+    return {"success": success, "episode_length": length, "success_std": float(np.std(rates)),
+            "success_min": float(np.min(rates)), "success_max": float(np.max(rates))}
+
+
 class OfflineTaskWithSimulatedEvaluations(Task):
     def __init__(self, env_name: str = "cube-single-play-singletask-task2-v0", model: str = "multistep",
                  save_directory: Path | None = None, dataset: dict | None = None, val_dataset: dict | None = None,
                  n_rows: int = 100_000, n_val_rows: int = 10_000, num_evaluation_envs: int = 50,
                  max_episode_steps: int = 1000, env_model=None, seed: int = 0,
                  initial_observations: Literal["dataset", "model"] = "dataset", initial_observation_model=None,
-                 device: int = 0):
+                 device: int = 0, env_models=None, ensemble_size: int = 0,
+                 ensemble_score: Literal["mean", "min", "mixed"] = "mean"):
+        if ensemble_score not in ENSEMBLE_SCORES:
+            raise ValueError(f"ensemble_score must be one of {ENSEMBLE_SCORES}, got {ensemble_score!r}")
         if initial_observations not in ("dataset", "model"):
             raise ValueError(f"initial_observations must be 'dataset' or 'model', got {initial_observations!r}")
         self.env_name = env_name
@@ -77,6 +137,18 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         self.val_dataset = val_dataset if val_dataset is not None else dataset
         self.obs_dim = self.train_dataset["observations"].shape[-1]
         self.action_dim = self.train_dataset["actions"].shape[-1]
+        self.ensemble_score = ensemble_score
+        if env_models is None and ensemble_size > 0:
+            if save_directory is None:
+                raise FileNotFoundError("ensemble_size needs save_directory with the trained ensemble "
+                                        "(train_env_model.py --ensemble_size)")
+            env_models = load_env_model_ensemble(save_directory, env_name, model, int(ensemble_size))
+        self.env_models = None if env_models is None else [tuple(m) for m in env_models]
+        if self.env_models is not None:
+            if not self.env_models:
+                raise ValueError("env_models is empty")
+            if env_model is None:
+                env_model = self.env_models[0]  # reset / step and the plain rollout: model 0
         if env_model is None and save_directory is not None:
             env_model = load_reference_env_model(save_directory, env_name, model)
         if env_model is None:
@@ -84,6 +156,10 @@ class OfflineTaskWithSimulatedEvaluations(Task):
             env_model = (em.init_state_predictor(spec, seed), em.init_termination_predictor(spec, seed + 1))
         self.sp_tree, self.tp_tree = env_model
         self.spec = em.spec_from_trees(self.sp_tree, self.tp_tree)
+        if self.env_models is not None:
+            for sp, tp in self.env_models:
+                if em.spec_from_trees(sp, tp) != self.spec:
+                    raise ValueError("the models of an ensemble must share one shape")
         self.initial_observations = self.train_dataset["observations"][::1000]
         self.initial_observation_source = initial_observations
         self._sampler = None
@@ -123,6 +199,11 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         population.set_env_model(em.flatten_state_predictor(self.spec, self.sp_tree),
                                  em.flatten_termination_predictor(self.spec, self.tp_tree),
                                  self.spec.sp_hidden, self.spec.tp_hidden)
+        if self.env_models is not None:
+            population.set_env_model_ensemble(
+                [em.flatten_state_predictor(self.spec, sp) for sp, _ in self.env_models],
+                [em.flatten_termination_predictor(self.spec, tp) for _, tp in self.env_models],
+                self.spec.sp_hidden, self.spec.tp_hidden)
         self._population = population
 
     def reset_observations(self, seed: int | None = None) -> np.ndarray:
@@ -140,6 +221,8 @@ class OfflineTaskWithSimulatedEvaluations(Task):
         ``record`` each member's entry also holds its ``transitions`` (the reference's
         evaluate_agent second result): (observations [max_steps, n_envs, obs], clipped
         actions [max_steps, n_envs, act]), 0 from an env's episode length on."""
+        if self.env_models is not None and not record:
+            return self._evaluate_members_ensemble(population, members, seed)
         self.attach(population)
         saved = population.active.copy()
         mask = np.zeros(population.n, dtype=bool)
@@ -157,6 +240,28 @@ class OfflineTaskWithSimulatedEvaluations(Task):
             for k, m in enumerate(ids):
                 out[m]["transitions"] = (res[2][k], res[3][k])
         return out
+
+    def _evaluate_members_ensemble(self, population, members, seed: int) -> dict:
+        """evaluate_members under the ensemble: one per-model launch (and one mixed launch
+        for ensemble_score 'mixed'), scalars per member (ensemble_scores)."""
+        self.attach(population)
+        saved = population.active.copy()
+        mask = np.zeros(population.n, dtype=bool)
+        mask[list(members)] = True
+        population.set_active(mask)
+        try:
+            obs0 = self.reset_observations(seed)
+            success, lengths = population.rollout_ensemble(obs0, self.max_episode_steps, seed=seed, mode="per_model")
+            mixed = None
+            if self.ensemble_score == "mixed":
+                mixed = population.rollout_ensemble(obs0, self.max_episode_steps, seed=seed, mode="mixed")
+        finally:
+            population.set_active(saved)
+        ids = [int(i) for i in np.nonzero(mask)[0]]
+        return {m: ensemble_scores([success[k, j].mean() for j in range(success.shape[1])],
+                                   [lengths[k, j].mean() for j in range(lengths.shape[1])], self.ensemble_score,
+                                   None if mixed is None else (mixed[0][k].mean(), mixed[1][k].mean()))
+                for k, m in enumerate(ids)}
 
     # ------------------------------------------- reference per-step contract
     def reset(self, seed: int | None = None):

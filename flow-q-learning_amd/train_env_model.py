@@ -12,6 +12,11 @@ it under ``params/ScanCell_0/cell`` like flax's ``nn.scan`` tree.
 starts (InitialObservationLoader), honouring ``--model.hidden_dims``, ``--model.latent_dim``
 and ``--reconstruction_weight``, and saves ``{"params": {"encoder", "decoder"}}`` with
 ``hidden_dims`` and ``latent_dim`` in the yaml: the files distribution_visualizer.py:62-99 reads.
+
+``--ensemble_size K`` trains K models one after the other, member k with seed
+``--seed + k``, and saves them as ``<model>_ens<k>.pt`` / ``<model>_ens<k>_config.yaml`` /
+``<model>_ens<k>_log.csv``: the files task/offline_task_simulated.py loads with
+``ensemble_size=K``.  Without the flag names and behaviour are the reference's.
 """
 from __future__ import annotations
 
@@ -96,8 +101,37 @@ class _CsvRunLogger:
             self.csv.log({"key": k, "value": v}, step=step)
 
 
+def build_parser():
+    """The reference's flags (argparser.py) plus --ensemble_size."""
+    parser = get_env_model_argparser()
+    parser.add_argument("--ensemble_size", type=int, default=0)
+    return parser
+
+
+def member_config(args, k: int | None):
+    """(trainer config, saved name) of ensemble member k; k None: the plain run."""
+    config = build_env_model_config_from_args(args)
+    if k is None:
+        return config, config.model
+    config.seed = args.seed + k
+    return config, f"{config.model}_ens{k}"
+
+
 def main(argv=None):
-    config = build_env_model_config_from_args(get_env_model_argparser().parse_args(argv))
+    args = build_parser().parse_args(argv)
+    if args.ensemble_size < 0:
+        raise ValueError("--ensemble_size must be >= 0")
+    if args.ensemble_size > 0 and args.model == "initial_observation":
+        raise ValueError("--ensemble_size is for baseline, multistep and termination_predictor")
+    if args.ensemble_size == 0:
+        return train_one(*member_config(args, None))
+    for k in range(args.ensemble_size):
+        save_dir = train_one(*member_config(args, k))
+    return save_dir
+
+
+def train_one(config, name: str):
+    """One training run of config.model, saved under ``name``."""
     base = config.env_name.replace("-singletask", "").rsplit("-task", 1)[0]
     d = Path(config.data_directory)
     train = load_npz_dataset(d / f"{base}.npz")
@@ -107,7 +141,7 @@ def main(argv=None):
     hidden = tuple(config.model_config.get("hidden_dims", em.DEFAULT_HIDDEN))
     save_dir = Path(config.save_directory) / config.env_name / "env_models"
     save_dir.mkdir(parents=True, exist_ok=True)
-    logger = _CsvRunLogger(save_dir / f"{config.model}_log.csv")
+    logger = _CsvRunLogger(save_dir / f"{name}_log.csv")
     np.random.seed(config.seed)
     if config.model in ("baseline", "multistep"):
         spec = em.EnvModelSpec(D, A, hidden, em.DEFAULT_HIDDEN)
@@ -140,9 +174,9 @@ def main(argv=None):
         raise ValueError(f"unknown model {config.model!r} (baseline, multistep, termination_predictor, "
                          "initial_observation)")
     trainer.train()
-    with open(save_dir / f"{config.model}_config.yaml", "w") as f:
+    with open(save_dir / f"{name}_config.yaml", "w") as f:
         yaml.safe_dump({k: list(v) if isinstance(v, tuple) else v for k, v in config.model_config.items()}, f)
-    with open(save_dir / f"{config.model}.pt", "wb") as f:
+    with open(save_dir / f"{name}.pt", "wb") as f:
         params = trainer.params
         if config.model == "multistep":  # nn.scan(Cell) tree (envmodel/multistep.py:41-52)
             params = {"ScanCell_0": {"cell": params}}

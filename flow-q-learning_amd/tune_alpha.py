@@ -50,7 +50,8 @@ def make_task(args, config):
             config.env_name, model=args.env_model, save_directory=config.save_directory if env_dir.exists() else None,
             n_rows=args.synthetic_rows, num_evaluation_envs=config.eval_episodes,
             max_episode_steps=args.max_episode_steps, seed=config.seed,
-            initial_observations=args.initial_observations)
+            initial_observations=args.initial_observations,
+            ensemble_size=args.env_model_ensemble, ensemble_score=args.ensemble_score)
     if args.task == "npz":
         from task.offline_task_npz import OfflineTaskNpz
         return OfflineTaskNpz(config.env_name, config.data_directory)
@@ -59,7 +60,8 @@ def make_task(args, config):
                                 num_evaluation_envs=min(config.eval_episodes, 64), seed=config.seed)
 
 
-def main(argv=None):
+def build_parser():
+    """The reference's flags (argparser.py) plus this driver's own."""
     parser = get_argparser()
     parser.add_argument("--max_evaluations", type=int, default=200)
     parser.add_argument("--number_of_seeds", type=int, default=1)
@@ -86,7 +88,16 @@ def main(argv=None):
     parser.add_argument("--pbt_truncation", type=float, default=0.25)
     parser.add_argument("--pbt_alpha_min", type=float, default=None)
     parser.add_argument("--pbt_alpha_max", type=float, default=None)
-    args = parser.parse_args(argv)
+    # --task simulated: score under the K env models saved by train_env_model.py --ensemble_size K
+    # (0: the single model); --ensemble_score: the mean or the min of the per-model success rates,
+    # or mixed episodes that draw a model afresh at every step (task/offline_task_simulated.py)
+    parser.add_argument("--env_model_ensemble", type=int, default=0)
+    parser.add_argument("--ensemble_score", choices=("mean", "min", "mixed"), default="mean")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     config = build_config_from_args(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     device = 0

@@ -331,6 +331,48 @@ int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* acti
  * allocations and copies).  FQLPOP_E_STATE before the first call.  [no reference counterpart] */
 int fqlpop_envmodel_replay_time(fqlpop_t* h, double* kernel_us);
 
+/* ---------------------------------------------------------------------
+ * World-model ensembles: the rollout above under n_models env models of ONE config
+ * (models trained from different seeds), all resident, in one launch.  The ensemble is
+ * stored apart from fqlpop_set_env_model's model: setting either never changes what the
+ * other's calls return. */
+enum { FQLPOP_ENS_PER_MODEL = 0, FQLPOP_ENS_MIXED = 1 };
+#define FQLPOP_ENS_MAX_MODELS 16
+
+/* Upload n_models (1..16) state predictor / termination predictor pairs: host
+ * sp_params [n_models][n_sp] and tp_params [n_models][n_tp], each row a flat vector as for
+ * fqlpop_set_env_model (counts from fqlpop_envmodel_param_count); copied.  Replaces an
+ * earlier ensemble.  FQLPOP_E_ARG, with the earlier ensemble kept, for n_models out of
+ * range or a count mismatch.  Synchronises.  [no reference counterpart] */
+int fqlpop_set_env_model_ensemble(fqlpop_t* h, const fqlpop_envmodel_config* cfg, int n_models,
+                                  const float* sp_params, int64_t n_sp, const float* tp_params, int64_t n_tp);
+
+/* fqlpop_rollout of every ACTIVE member under the ensemble; init_obs, noise
+ * ([n_active][max_steps][n_envs][action_dim], shared by all models, or NULL: fqlpop_rollout's
+ * Philox draw for that seed and member) and the shape limits as there.
+ *   FQLPOP_ENS_PER_MODEL: every (member, model) pair runs n_envs episodes under that model.
+ *     out host [n_active][n_models][n_envs][2], out_obs NULL or [n_active][n_models][n_envs]
+ *     [obs_dim]; slice k is bit for bit fqlpop_rollout's result after
+ *     fqlpop_set_env_model(model k).  choice must be NULL.
+ *   FQLPOP_ENS_MIXED (trajectory sampling): at step t (from 1) env e steps under model
+ *     choice[t - 1][e] (host int32 [max_steps][n_envs], each in [0, n_models)) for both
+ *     predictors, or, with choice NULL, under k = (w0 * n_models) >> 32 with w0 the first
+ *     word of Philox4x32-10 at counter (e, t, 0x5E12, 0) under the key (low, high 32 bits
+ *     of seed): the call seed alone, so every member meets the same model sequence.  The
+ *     choice is per env: an episode does not depend on n_envs.  out host
+ *     [n_active][n_envs][2], out_obs NULL or [n_active][n_envs][obs_dim]: the observation
+ *     after the env's own last step.
+ * FQLPOP_E_STATE "no env model ensemble set"; FQLPOP_E_ARG for a bad mode, choice in
+ * PER_MODEL mode or a choice entry out of range; FQLPOP_E_UNSUPPORTED as fqlpop_rollout;
+ * all before any launch.  Synchronises.  [no reference counterpart] */
+int fqlpop_rollout_ensemble(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                            const float* noise, int mode, const int32_t* choice, float* out, float* out_obs);
+
+/* GPU time of the kernel of the last successful fqlpop_rollout_ensemble call on this
+ * handle, in microseconds (HIP events around the launch, as fqlpop_envmodel_replay_time).
+ * FQLPOP_E_STATE before the first call.  [no reference counterpart] */
+int fqlpop_rollout_ensemble_time(fqlpop_t* h, double* kernel_us);
+
 /* ---------------------------------------------------------------------------
  * Env-model trainer: the reference's world-model
  * trainers, one fused GPU step per train_step.
