@@ -51,10 +51,58 @@ struct Net {
     long long ln_scale, ln_bias;        // state predictor LayerNorm_0 (-1: none)
 };
 
+// The model axis of an ensemble launch (fqlpop_emtrain_create_ensemble): K models that share
+// the dataset, the frozen termination predictor, the config and the update count, each with
+// its own parameters, moments, partials, logs, record store, seed and (when injected per
+// model) batch, at a fixed stride from model 0's.  A single-model handle is n_models = 1,
+// xcd = 0: block == blockIdx.x and every offset 0.
+constexpr int ENS_MAX = FQLPOP_EM_ENS_MAX_MODELS;
+constexpr int ENS_XCDS = 8;
+struct EnsAxis {
+    int n_models, bpm, xcd;             // models, blocks per model, placement (ens_block_map)
+    long long par;                      // floats between two models' params / wt / m / v
+    long long part, logs, seq;          // ... partial sets, block log sums, record stores
+    long long obs, act, rew, keep;      // ... injected batches ([B][D], [B][A], [B], mask bytes); 0: one
+                                        // shared batch, or the dataset
+    uint64_t seeds[ENS_MAX];            // sampling / dropout seed of each model
+};
+
+// Linear block id -> (model, block within the model) of a launch of n_models x bpm blocks.
+//   xcd = 0: model-major, grid = n_models bpm, no padding.
+//   xcd = 1: blocks are dealt round-robin over the 8 XCDs (ids l and l + 8 share one; observed,
+//   not promised), so id l sits on XCD x = l % 8 in slot j = l / 8.  With K >= 8 models XCD x
+//   holds the models x, x + 8, .. (at most ceil(K / 8)), one after the other in its slots;
+//   with K < 8 a model owns S = 8 / K neighbouring XCDs and deals its blocks over them.
+//   Either way an XCD's L2 sees the W and W^T of at most ceil(K / 8) models.  Ids that fall
+//   outside (model >= K, block >= bpm) are padding: *model = -1, the block exits at once.
+// Returns the grid size.  The results of a launch do not depend on the mapping: every
+// per-block quantity (sampling index, dropout position, partial slot) uses the block within
+// the model.
+__host__ __device__ inline int ens_block_map(int n_models, int bpm, int xcd, int lin, int* model, int* block) {
+    if (!xcd) {
+        *model = lin / bpm;
+        *block = lin - *model * bpm;
+        return n_models * bpm;
+    }
+    const int S = n_models >= ENS_XCDS ? 1 : ENS_XCDS / n_models;  // XCDs per model
+    const int G = (n_models + ENS_XCDS - 1) / ENS_XCDS;            // models per XCD
+    const int cb = (bpm + S - 1) / S;                              // slots of one model on one XCD
+    const int x = lin % ENS_XCDS, j = lin / ENS_XCDS;
+    const int g = j / cb, r = j - g * cb;
+    const int mdl = x / S + ENS_XCDS * g, blk = r * S + x % S;
+    const bool pad = mdl >= n_models || blk >= bpm || g >= G;
+    *model = pad ? -1 : mdl;
+    *block = pad ? -1 : blk;
+    return ENS_XCDS * G * cb;
+}
+
 struct StepArgs {
+    EnsAxis ens;
     int kind;                           // FQLPOP_EM_STATE_PREDICTOR / FQLPOP_EM_TERMINATION
     int train;                          // 1: grads + dropout; 0: eval logs only
     Net net, tpn;                       // trained net; frozen termination predictor (kind 0, tw > 0)
+    // params, wt, part, logs, seq (and an injected batch) are model 0's: a block reads its own
+    // model's through ModelView (ens_enter); tp / tpt and the dataset are shared
     const float* params;
     const float* tp;
     const float *wt, *tpt;              // W^T copies of params / tp (Dense kernels [out][in], same offsets)
@@ -66,8 +114,7 @@ struct StepArgs {
     long long n_rows;
     int injected;
     const unsigned char* keep;          // injected dropout keep mask [B][obs] or null
-    uint64_t seed;
-    long long step;                     // update count (sampling counter)
+    long long step;                   // update count (sampling counter)
     int B, D, A;
     float tw, ttw, alpha, gamma, rate;
     // multistep (FQLPOP_EM_MULTISTEP): sequence length, rows per dataset episode, and the
@@ -276,12 +323,89 @@ DEV void tp_score(const StepArgs& a, float* const* tacts, float* gA, float* gB, 
     __syncthreads();
 }
 
+// Squared-error log sums of the block's R rows over the D features, in a fixed order: the
+// block's last wave, lane = r + 16 g, sums d^2 of row r over the features k = g (mod 4) in
+// ascending k, then (s0 + s1) + (s2 + s3), and adds that to lsum0[r].  (An LDS atomicAdd per
+// element left the order of the sum, and with it the last bit of the logged loss, to the wave
+// scheduling: a model's logs must not depend on what runs beside it.)  d is computed as the
+// loss does, (out + x0) - nobs; out, x0 and nobs are final on entry and the barrier that
+// follows the caller's own loop over the elements publishes lsum0.
+template <int NTHREADS>
+DEV void sq_err_rows(const float* out, const float* x0, const float* nobs, int D, float* lsum0) {
+    const int l = (int)threadIdx.x - (NTHREADS - 64);
+    if (l < 0) return;
+    const int r = l & 15, g = l >> 4;
+    float s = 0.f;
+    for (int k = g; k < D; k += 4) {
+        const float p = out[k * R + r] + x0[k * R + r];
+        const float d = p - nobs[k * R + r];
+        s += d * d;
+    }
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (g == 0) lsum0[r] += s;
+}
+
+// A block's model: the per-model pointers and seed of StepArgs moved to the block's model, and
+// the block's index within it.  Derived once at kernel entry; the model index and every offset
+// are wave-uniform (blockIdx and kernel arguments only; readfirstlane pins the quotients of
+// the block map, whose division expands to vector instructions, back into scalar registers,
+// so that no buffer resource built from these pointers ends up in a waterfall loop).
+struct ModelView {
+    const float *params, *wt;
+    float *part, *logs, *seq;
+    const float *obs, *act, *rew, *nobs;
+    const unsigned char* keep;
+    uint64_t seed;
+    int blk;
+};
+DEV bool ens_enter(const StepArgs& a, ModelView& m) {
+    const EnsAxis& e = a.ens;
+    {
+        // One word of every 64-byte line of the kernel arguments, requested together ahead of the
+        // branches below.  The arguments of a launch are cold, and the loads behind a branch that
+        // itself waits for arguments start only once it is taken: a second round trip to memory
+        // (measured: + 0.5 us per single-model launch without this).
+        // (Separate operands of one empty asm: an OR over the words was scheduled as two rounds.)
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(&a);
+        constexpr int LAST = (int)(sizeof(StepArgs) / 4) - 1;
+        static_assert(LAST < 16 * 16, "StepArgs outgrew the 16 lines touched here");
+#define EM_W(i) "s"(w[(i) * 16 < LAST ? (i) * 16 : LAST])
+        asm volatile("" ::EM_W(0), EM_W(1), EM_W(2), EM_W(3), EM_W(4), EM_W(5), EM_W(6), EM_W(7), EM_W(8), EM_W(9),
+                     EM_W(10), EM_W(11), EM_W(12), EM_W(13), EM_W(14), EM_W(15));
+#undef EM_W
+    }
+    int model = 0, blk = (int)blockIdx.x;
+    if (e.n_models > 1 || e.xcd) {  // (one model, no remap: the single-model launch as it was)
+        ens_block_map(e.n_models, e.bpm, e.xcd, (int)blockIdx.x, &model, &blk);
+        model = __builtin_amdgcn_readfirstlane(model);
+        blk = __builtin_amdgcn_readfirstlane(blk);
+        if (model < 0) return false;  // padding of the XCD placement
+    }
+    m.blk = blk;
+    m.params = a.params + model * e.par;
+    m.wt = a.wt + model * e.par;
+    m.part = a.part + model * e.part;
+    m.logs = a.logs + model * e.logs;
+    m.seq = a.seq + model * e.seq;
+    m.obs = a.obs + model * e.obs;
+    m.act = a.act + model * e.act;
+    m.rew = a.rew + model * e.rew;
+    m.nobs = a.nobs + model * e.obs;
+    m.keep = a.keep ? a.keep + model * e.keep : nullptr;
+    m.seed = e.seeds[0];  // (with the other arguments; a later model's is one more scalar load)
+    if (model > 0) m.seed = e.seeds[model];
+    return true;
+}
+
 __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float lsum[NLOG][R];
     __shared__ float lab[R];
     __shared__ long long rowid[R];
-    const int tid = threadIdx.x, blk = blockIdx.x;
+    ModelView mv;
+    if (!ens_enter(a, mv)) return;
+    const int tid = threadIdx.x, blk = mv.blk;
     const Net& N = a.net;
     const int D = a.D, A = a.A;
     const int K0 = N.dims[0];
@@ -309,33 +433,33 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
         long long id = gr;
         if (!a.injected) {
             uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE7u, 0u};
-            philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
             id = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)a.n_rows);
         }
         rowid[tid] = id;
-        lab[tid] = a.rew[id] == 0.f ? 1.f : 0.f;
+        lab[tid] = mv.rew[id] == 0.f ? 1.f : 0.f;
     }
     for (int q = tid; q < NLOG * R; q += NT) lsum[q / R][q % R] = 0.f;
     __syncthreads();
     for (int t = tid; t < D * R; t += NT) {
         const int k = t / R, r = t % R;
-        nobs[t] = a.nobs[rowid[r] * D + k];
+        nobs[t] = mv.nobs[rowid[r] * D + k];
     }
     if (a.kind == FQLPOP_EM_STATE_PREDICTOR) {
         for (int t = tid; t < K0 * R; t += NT) {
             const int k = t / R, r = t % R;
-            x0[t] = k < D ? a.obs[rowid[r] * D + k] : a.act[rowid[r] * A + (k - D)];
+            x0[t] = k < D ? mv.obs[rowid[r] * D + k] : mv.act[rowid[r] * A + (k - D)];
         }
     } else {
         // termination predictor: dropout on the input while training; the keep mask is fixed
         // per (batch position, feature), as the reference's constant dropout rng
         for (int t = tid; t < K0 * R; t += NT) {
             const int k = t / R, r = t % R;
-            float v = a.nobs[rowid[r] * D + k];
+            float v = mv.nobs[rowid[r] * D + k];
             if (a.train) {
                 const int pos = blk * R + r;
-                const bool keep = a.keep ? a.keep[(long long)pos * D + k] != 0
-                                         : urand(a.seed, (uint32_t)pos, (uint32_t)k, 0xD20u) >= a.rate;
+                const bool keep = mv.keep ? mv.keep[(long long)pos * D + k] != 0
+                                          : urand(mv.seed, (uint32_t)pos, (uint32_t)k, 0xD20u) >= a.rate;
                 v = keep ? v / (1.0f - a.rate) : 0.f;
             }
             x0[t] = v;
@@ -344,7 +468,7 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     __syncthreads();
 
     // ---- forward
-    const float* P = a.params;
+    const float* P = mv.params;
     if (N.ln_scale >= 0) {
         // flax LayerNorm over the K0 input features of each row (eps 1e-6, E[x^2] - mu^2 clipped)
         __shared__ float mu_s[R], rs_s[R];
@@ -386,8 +510,8 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
             const float d = p - nobs[t];
             pred[t] = p;
             gA[t] = gscale * d;
-            atomicAdd(&lsum[0][t % R], d * d);
         }
+        sq_err_rows<NT>(out, x0, nobs, D, lsum[0]);
         __syncthreads();
         if (a.tw > 0.f) tp_score(a, tacts, gA, gB, gC, lab, lsum, invB, norm);
     } else {
@@ -420,17 +544,17 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     if (tid < NLOG) {
         float s = 0.f;
         for (int r = 0; r < R; ++r) s += lsum[tid][r];
-        a.logs[(long long)blk * NLOG + tid] = s;
+        mv.logs[(long long)blk * NLOG + tid] = s;
     }
     if (!a.train) return;
 
     // ---- backward: partial grads of every Dense (and LayerNorm_0)
-    float* pg = a.part + (long long)blk * a.P;
+    float* pg = mv.part + (long long)blk * a.P;
     float* g = gA;
     float* gn = gB;
     for (int i = N.n - 1; i >= 0; --i) {
         dense_dw(acts[i], g, N.dims[i], N.dims[i + 1], pg + N.w[i], pg + N.b[i]);
-        if (i > 0 || N.ln_scale >= 0) dense_dx(a.wt + N.w[i], g, N.dims[i], N.dims[i + 1], gn, i > 0 ? acts[i] : nullptr);
+        if (i > 0 || N.ln_scale >= 0) dense_dx(mv.wt + N.w[i], g, N.dims[i], N.dims[i + 1], gn, i > 0 ? acts[i] : nullptr);
         else __syncthreads();
         float* tmp = g;
         g = gn;
@@ -467,7 +591,9 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
     __shared__ float lab[R];
     __shared__ long long rowbase[R];
     __shared__ float mu_s[R], rs_s[R], cs[2][R];
-    const int tid = threadIdx.x, blk = blockIdx.x;
+    ModelView mv;
+    if (!ens_enter(a, mv)) return;
+    const int tid = threadIdx.x, blk = mv.blk;
     const Net& N = a.net;
     const int D = a.D, A = a.A, T = a.T;
     const int K0 = N.dims[0];
@@ -495,7 +621,7 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
         long long base = (long long)gr * T;
         if (!a.injected) {
             uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE5u, 0u};
-            philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
             const long long n_ep = a.n_rows / a.ep_len;
             const long long ep = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)n_ep);
             const long long st = (long long)(c[2] % (uint32_t)(a.ep_len - T));
@@ -506,11 +632,11 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
     for (int q = tid; q < NLOG * R; q += NT) lsum[q / R][q % R] = 0.f;
     __syncthreads();
 
-    const float* P = a.params;
+    const float* P = mv.params;
     const float norm = 1.0f + a.tw;
     const float inv_n = 1.0f / ((float)a.B * (float)T);
     const float gscale = 2.0f / ((float)a.B * (float)T * D) / norm;
-    float* const sq = a.seq + (long long)blk * T * a.seq_stride;  // this block's store
+    float* const sq = mv.seq + (long long)blk * T * a.seq_stride;  // this block's store
     // store layout per step: xhat [K0][R] | rstd [R] | acts[0..n-1] | direct output grad [D][R]
     int act_floats = 0;
     for (int i = 0; i < N.n; ++i) act_floats += N.dims[i] * R;
@@ -520,14 +646,14 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
         for (int q = tid; q < K0 * R; q += NT) {
             const int k = q / R, r = q % R;
             const long long row = rowbase[r] + t;
-            if (k >= D) x0[q] = a.act[row * A + (k - D)];
-            else if (t == 0) x0[q] = a.obs[row * D + k];  // later steps: the previous prediction
+            if (k >= D) x0[q] = mv.act[row * A + (k - D)];
+            else if (t == 0) x0[q] = mv.obs[row * D + k];  // later steps: the previous prediction
         }
         for (int q = tid; q < D * R; q += NT) {
             const int k = q / R, r = q % R;
-            nobs[q] = a.nobs[(rowbase[r] + t) * D + k];
+            nobs[q] = mv.nobs[(rowbase[r] + t) * D + k];
         }
-        if (tid < R) lab[tid] = a.rew[rowbase[tid] + t] == 0.f ? 1.f : 0.f;
+        if (tid < R) lab[tid] = mv.rew[rowbase[tid] + t] == 0.f ? 1.f : 0.f;
         __syncthreads();
         if (tid < R) {
             float s1 = 0.f, s2 = 0.f;
@@ -557,8 +683,8 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
             const float d = p - nobs[q];
             pred[q] = p;
             gA[q] = gscale * d;
-            atomicAdd(&lsum[0][q % R], d * d);
         }
+        sq_err_rows<NT>(out, x0, nobs, D, lsum[0]);
         __syncthreads();
         if (a.tw > 0.f) tp_score<EM_SEQ_KS>(a, tacts, gA, gB, gC, lab, lsum, inv_n, norm);
         if (a.train) {
@@ -576,12 +702,12 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
     if (tid < NLOG) {
         float s = 0.f;
         for (int r = 0; r < R; ++r) s += lsum[tid][r];
-        a.logs[(long long)blk * NLOG + tid] = s;
+        mv.logs[(long long)blk * NLOG + tid] = s;
     }
     if (!a.train) return;
 
     // ---- backward through time
-    float* pg = a.part + (long long)blk * a.P;
+    float* pg = mv.part + (long long)blk * a.P;
     for (int t = T - 1; t >= 0; --t) {
         const bool acc = t < T - 1;
         const float* st = sq + (long long)t * a.seq_stride;
@@ -616,7 +742,7 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
         float* gn = gB;
         for (int i = N.n - 1; i >= 0; --i) {
             dense_dw(acts[i], g, N.dims[i], N.dims[i + 1], pg + N.w[i], pg + N.b[i], acc);
-            dense_dx<EM_SEQ_KS>(a.wt + N.w[i], g, N.dims[i], N.dims[i + 1], gn, i > 0 ? acts[i] : nullptr);
+            dense_dx<EM_SEQ_KS>(mv.wt + N.w[i], g, N.dims[i], N.dims[i + 1], gn, i > 0 ? acts[i] : nullptr);
             float* tmp = g;
             g = gn;
             gn = tmp;
@@ -872,11 +998,13 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     __shared__ float lab[R];
     __shared__ long long rowbase[R];
     __shared__ float mu_s[R], rs_s[R], cs[2][R];
-    const int tid = threadIdx.x, blk = blockIdx.x;
+    ModelView mv;
+    if (!ens_enter(a, mv)) return;
+    const int tid = threadIdx.x, blk = mv.blk;
 #ifdef FQ_DIAG  // phase times of block 0 (s_memrealtime, 100 MHz), summed over the steps
     __shared__ unsigned long long ph[EM_PH_N];
     unsigned long long ph_prev = 0;
-    const bool ph_on = a.probe != nullptr && blk == 0;
+    const bool ph_on = a.probe != nullptr && blockIdx.x == 0;
     if (ph_on && tid < EM_PH_N) ph[tid] = 0;
     auto stamp = [&](int i) {
         if (ph_on && threadIdx.x == 0) {
@@ -926,7 +1054,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         long long base = (long long)gr * T;
         if (!a.injected) {  // MultistepLoader windows, as em_seq_grad_kernel
             uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE5u, 0u};
-            philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
             const long long n_ep = a.n_rows / a.ep_len;
             const long long ep = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)n_ep);
             const long long st = (long long)(c[2] % (uint32_t)(a.ep_len - T));
@@ -939,15 +1067,15 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     for (int q = tid; q < NLOG * R; q += SW_NT) lsum[q / R][q % R] = 0.f;
     for (int q = tid; q < 2 * K0; q += SW_NT) {
         lnacc[q] = 0.f;
-        lnp[q] = q < K0 ? a.params[a.net.ln_scale + q] : a.params[a.net.ln_bias + q - K0];
+        lnp[q] = q < K0 ? mv.params[a.net.ln_scale + q] : mv.params[a.net.ln_bias + q - K0];
     }
     __syncthreads();
 
-    const float* P = a.params;
+    const float* P = mv.params;
     const float norm = 1.0f + a.tw;
     const float inv_n = 1.0f / ((float)a.B * (float)T);
     const float gscale = 2.0f / ((float)a.B * (float)T * D) / norm;
-    float* const sq = a.seq + (long long)blk * T * a.seq_stride;
+    float* const sq = mv.seq + (long long)blk * T * a.seq_stride;
     int act_floats = 0;
     for (int i = 0; i < n; ++i) act_floats += N.dims[i] * R;
     const int off_g0 = K0 * R + R + act_floats + D * R;  // g_i from here (g_{n-1} first)
@@ -970,12 +1098,12 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         if (tid >= nin || t >= T) return 0.f;
         const int r = tid % R, f = tid / R;
         const long long row = rowbase[r] + t;
-        if (f < A) return a.act[row * A + f];
-        if (f < A + D) return a.nobs[row * D + (f - A)];
-        return a.rew[row];
+        if (f < A) return mv.act[row * A + f];
+        if (f < A + D) return mv.nobs[row * D + (f - A)];
+        return mv.rew[row];
     };
     float inx = in_load(0, tid);
-    for (int q = tid; q < D * R; q += SW_NT) x0[q] = a.obs[rowbase[q % R] * D + q / R];  // observations[:, 0]
+    for (int q = tid; q < D * R; q += SW_NT) x0[q] = mv.obs[rowbase[q % R] * D + q / R];  // observations[:, 0]
 
     stamp(-1);
     for (int t = 0; t < T; ++t) {
@@ -1025,8 +1153,8 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
                         const float d = p - nobs[q];
                         pred[q] = p;
                         gA[q] = gscale * d;
-                        atomicAdd(&lsum[0][q % R], d * d);
                     }
+                    sq_err_rows<SW_NT>(out, x0, nobs, D, lsum[0]);
                     __syncthreads();
                 }
             } else if (j < n + m) {
@@ -1078,7 +1206,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     if (tid < NLOG) {
         float s = 0.f;
         for (int r = 0; r < R; ++r) s += lsum[tid][r];
-        a.logs[(long long)blk * NLOG + tid] = s;
+        mv.logs[(long long)blk * NLOG + tid] = s;
     }
     if (!a.train) return;
     // the backward reads records other threads stored (the last one just now): every store of
@@ -1089,7 +1217,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     // ---- the backward sweep: dX chain, LayerNorm backward and carry, t = T-1 .. 0
     auto bw_op = [&](int j) -> SwOp {  // j = 0..n-1: layer n-1-j's dX from W^T
         const int i = n - 1 - j;
-        return SwOp{a.wt + N.w[i], N.dims[i + 1], N.dims[i]};
+        return SwOp{mv.wt + N.w[i], N.dims[i + 1], N.dims[i]};
     };
     sw_load(bw_op(0), fr);
     // the step's record (xhat | rstd | acts[1..n-1] for the masks | own output gradient), a step
@@ -1180,7 +1308,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     // LayerNorm grads into T chunk 0's partials (the other chunks' are zero: em_seq_dw_kernel
     // writes the Dense leaves of every chunk)
     for (int c = 0; c < a.tchunks; ++c) {
-        float* pg = a.part + (long long)(blk * a.tchunks + c) * a.P;
+        float* pg = mv.part + (long long)(blk * a.tchunks + c) * a.P;
         for (int k = tid; k < K0; k += SW_NT) {
             pg[N.ln_scale + k] = c == 0 ? lnacc[k] : 0.f;
             pg[N.ln_bias + k] = c == 0 ? lnacc[K0 + k] : 0.f;
@@ -1200,9 +1328,13 @@ struct SeqDwArgs {
     Net net;
     int T, tchunks, K0, D;
     int first[MAXL + 1];  // prefix of per-layer tile counts
+    long long ens_seq, ens_part;  // floats between two models' record stores / partial sets
 };
+// grid: (blocks x tchunks x tiles, models); the model is blockIdx.y (wave-uniform by construction)
 __global__ __launch_bounds__(256) void em_seq_dw_kernel(const SeqDwArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][64 * R], Bs[2][64 * R];
+    const float* const mseq = a.seq + blockIdx.y * a.ens_seq;
+    float* const mpart = a.part + blockIdx.y * a.ens_part;
     const int per = a.first[a.net.n];
     const int bc = blockIdx.x / per, tl = blockIdx.x % per;  // bc = b tchunks + c
     const int b = bc / a.tchunks, c = bc % a.tchunks;
@@ -1219,7 +1351,7 @@ __global__ __launch_bounds__(256) void em_seq_dw_kernel(const SeqDwArgs a) {
     og = a.K0 * R + R + act_floats + a.D * R;
     for (int j = a.net.n - 1; j > i; --j) og += a.net.dims[j + 1] * R;  // g_{n-1} first
     const int t0 = a.T * c / a.tchunks, t1 = a.T * (c + 1) / a.tchunks;
-    const float* sq = a.seq + (long long)b * a.T * a.seq_stride;
+    const float* sq = mseq + (long long)b * a.T * a.seq_stride;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
     const int wk = (w >> 1) * 32, wf = (w & 1) * 32;
     // staging: thread -> one float4 of each slice ([64][R] = 256 float4); rows past K / N read as 0
@@ -1270,7 +1402,7 @@ __global__ __launch_bounds__(256) void em_seq_dw_kernel(const SeqDwArgs a) {
         }
         __syncthreads();
     }
-    float* pg = a.part + (long long)bc * a.P;
+    float* pg = mpart + (long long)bc * a.P;
     // acc[x][y][r]: k = k0 + wk + 16 x + 4 lk + r, f = f0 + wf + 16 y + li
 #pragma unroll
     for (int x = 0; x < 2; ++x)
@@ -1293,24 +1425,32 @@ struct AdamArgsEm {
     long long P;
     int blocks;
     float lr, bc1, bc2;
+    long long ens_par, ens_part;        // floats between two models' params / wt / m / v, partial sets
 };
 
-// Fixed-order sum of the block partials + optax.adam
+// Fixed-order sum of the block partials + optax.adam.  grid: (P / 256, models); the model is
+// blockIdx.y, and a model's partials fold in the same block order whatever runs beside it.
 __global__ __launch_bounds__(256) void em_adam_kernel(const AdamArgsEm a) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.P) return;
+    const long long mo = blockIdx.y * a.ens_par;
+    const float* part = a.part + blockIdx.y * a.ens_part;
+    float* params = a.params + mo;
+    float* wt = a.wt + mo;
+    float* am = a.m + mo;
+    float* av = a.v + mo;
     float g = 0.f;
-    for (int b = 0; b < a.blocks; ++b) g += a.part[(long long)b * a.P + p];
-    const float m = 0.1f * g + 0.9f * a.m[p];
-    const float v = 0.001f * (g * g) + 0.999f * a.v[p];
-    a.m[p] = m;
-    a.v[p] = v;
-    const float np = a.params[p] + (-a.lr) * ((m / a.bc1) / (sqrtf(v / a.bc2) + 1e-8f));
-    a.params[p] = np;
+    for (int b = 0; b < a.blocks; ++b) g += part[(long long)b * a.P + p];
+    const float m = 0.1f * g + 0.9f * am[p];
+    const float v = 0.001f * (g * g) + 0.999f * av[p];
+    am[p] = m;
+    av[p] = v;
+    const float np = params[p] + (-a.lr) * ((m / a.bc1) / (sqrtf(v / a.bc2) + 1e-8f));
+    params[p] = np;
     for (int i = 0; i < a.net.n; ++i) {
         const long long o = p - a.net.w[i];
         const int K = a.net.dims[i], N = a.net.dims[i + 1];
-        if (o >= 0 && o < (long long)K * N) a.wt[a.net.w[i] + (o % N) * K + o / N] = np;
+        if (o >= 0 && o < (long long)K * N) wt[a.net.w[i] + (o % N) * K + o / N] = np;
     }
 }
 
@@ -1408,6 +1548,12 @@ struct fqlpop_emtrain {
     bool sweep = false;          // multistep through em_sweep_kernel + em_seq_dw_kernel (sw_fits)
     int tchunks = 1;             // sweep: T chunks of the dW GEMM (partial sets per block)
     int sweep_lds = 0;
+    // the model axis (fqlpop_emtrain_create_ensemble; 1 model, no remap for fqlpop_emtrain_create):
+    // every per-model buffer above is [K] slices at these strides (floats; keep: bytes)
+    int K = 1;
+    int xcd = 0;                 // engine option em_ens_xcd at creation
+    uint64_t seeds[ENS_MAX] = {};
+    long long s_par = 0, s_part = 0, s_logs = 0, s_seq = 0, s_obs = 0, s_act = 0, s_rew = 0, s_keep = 0;
     hipStream_t s = nullptr;
 };
 
@@ -1469,18 +1615,24 @@ int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_para
     });
 }
 
-int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params, int64_t n_params, int device,
-                          fqlpop_emtrain_t** out) {
-    return em_guard([&] {
-        EMARG(cfg && params && out, "null argument");
+}  // extern "C"
+
+// K models ([K][P] params, K seeds) behind one handle; K = 1, xcd = 0 is fqlpop_emtrain_create.
+// Every refusal comes before the first GPU call.
+static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* params, int64_t n_params,
+                      const uint64_t* seeds, int xcd, int device, fqlpop_emtrain_t** out) {
+    {
         EMARG(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
         EMARG(cfg->steps > 0, "steps must be > 0");
         auto h = std::make_unique<fqlpop_emtrain>();
         h->cfg = *cfg;
         h->device = device;
+        h->K = K;
+        h->xcd = xcd;
+        for (int k = 0; k < K; ++k) h->seeds[k] = seeds[k];
+        h->cfg.seed = seeds[0];
         em_layouts(cfg, &h->net, &h->P, &h->tpn, &h->PT);
-        EMARG(n_params == h->P, "params size mismatch");
-        EMCHK(hipSetDevice(device));
+        EMARG(n_params == h->P * K, "params size mismatch");
         // LDS: x0, xhat [K0][R], acts [sum dims][R], gA, gB [maxd][R], nobs [D][R], tp acts
         int maxd = 0, sum = 0, tsum = 0;
         for (int i = 0; i <= h->net.n; ++i) { maxd = std::max(maxd, h->net.dims[i]); sum += h->net.dims[i]; }
@@ -1508,20 +1660,15 @@ int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params,
             }
         }
         const long long P = h->P;
-        EMCHK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
-        EMCHK(hipMalloc(&h->params, 4 * P));
-        EMCHK(hipMalloc(&h->m, 4 * P));
-        EMCHK(hipMalloc(&h->v, 4 * P));
-        EMCHK(hipMalloc(&h->part, 4 * P * h->blocks * h->tchunks));
-        EMCHK(hipMalloc(&h->logs, 4 * (long long)NLOG * h->blocks));
-        EMCHK(hipMemcpy(h->params, params, 4 * P, hipMemcpyHostToDevice));
-        EMCHK(hipMalloc(&h->wt, 4 * P));
-        const std::vector<float> wt = transposed(h->net, params, P);
-        EMCHK(hipMemcpy(h->wt, wt.data(), 4 * P, hipMemcpyHostToDevice));
-        EMCHK(hipMemset(h->m, 0, 4 * P));
-        EMCHK(hipMemset(h->v, 0, 4 * P));
-        EMCHK(hipMemset(h->logs, 0, 4 * (long long)NLOG * h->blocks));
         const long long B = cfg->batch_size * (long long)h->T, D = cfg->obs_dim, A = cfg->action_dim;
+        // per-model strides (a model's parameter block starts on a 256-byte boundary)
+        h->s_par = K > 1 ? (P + 63) / 64 * 64 : P;
+        h->s_part = P * h->blocks * h->tchunks;
+        h->s_logs = (long long)NLOG * h->blocks;
+        h->s_obs = B * D;
+        h->s_act = B * A;
+        h->s_rew = B;
+        h->s_keep = B * D;
         if (ms) {
             long long act = 0;
             for (int i = 0; i < h->net.n; ++i) act += h->net.dims[i];
@@ -1529,26 +1676,106 @@ int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params,
             if (h->sweep)
                 for (int i = 0; i < h->net.n; ++i) gfl += h->net.dims[i + 1];
             h->seq_stride = (long long)R * (h->net.dims[0] + 1 + act + D + gfl);
-            EMCHK(hipMalloc(&h->seq, 4 * h->seq_stride * h->T * h->blocks));
+            h->s_seq = h->seq_stride * h->T * h->blocks;
         }
-        EMCHK(hipMalloc(&h->i_obs, 4 * B * D));
-        EMCHK(hipMalloc(&h->i_act, 4 * std::max(1LL, B * A)));
-        EMCHK(hipMalloc(&h->i_rew, 4 * B));
-        EMCHK(hipMalloc(&h->i_nobs, 4 * B * D));
-        EMCHK(hipMalloc(&h->i_keep, B * D));
-        EMCHK(hipFuncSetAttribute((const void*)em_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-        EMCHK(hipFuncSetAttribute((const void*)em_seq_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  h->lds_bytes));
-        if (h->sweep)
-            EMCHK(hipFuncSetAttribute((const void*)em_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      h->sweep_lds));
+        try {
+            EMCHK(hipSetDevice(device));
+            EMCHK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+            const long long PK = h->s_par * K;
+            EMCHK(hipMalloc(&h->params, 4 * PK));
+            EMCHK(hipMalloc(&h->m, 4 * PK));
+            EMCHK(hipMalloc(&h->v, 4 * PK));
+            EMCHK(hipMalloc(&h->part, 4 * h->s_part * K));
+            EMCHK(hipMalloc(&h->logs, 4 * h->s_logs * K));
+            EMCHK(hipMalloc(&h->wt, 4 * PK));
+            EMCHK(hipMemset(h->params, 0, 4 * PK));
+            EMCHK(hipMemset(h->wt, 0, 4 * PK));
+            for (int k = 0; k < K; ++k) {
+                const float* pk = params + (long long)k * P;
+                EMCHK(hipMemcpy(h->params + k * h->s_par, pk, 4 * P, hipMemcpyHostToDevice));
+                const std::vector<float> wt = transposed(h->net, pk, P);
+                EMCHK(hipMemcpy(h->wt + k * h->s_par, wt.data(), 4 * P, hipMemcpyHostToDevice));
+            }
+            EMCHK(hipMemset(h->m, 0, 4 * PK));
+            EMCHK(hipMemset(h->v, 0, 4 * PK));
+            EMCHK(hipMemset(h->logs, 0, 4 * h->s_logs * K));
+            if (ms) {
+                // the record store of every model (about 300 MB per model at B = T = 256, default widths)
+                const long long bytes = 4 * h->s_seq * K;
+                const hipError_t e = hipMalloc(&h->seq, bytes);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    throw EmErr{FQLPOP_E_HIP, "multistep record store: hipMalloc of " + std::to_string(bytes) + " bytes (" +
+                                                  std::to_string(K) + " models x " + std::to_string(4 * h->s_seq) +
+                                                  ") failed: " + hipGetErrorString(e)};
+                }
+            }
+            EMCHK(hipMalloc(&h->i_obs, 4 * h->s_obs * K));
+            EMCHK(hipMalloc(&h->i_act, 4 * std::max(1LL, h->s_act * K)));
+            EMCHK(hipMalloc(&h->i_rew, 4 * h->s_rew * K));
+            EMCHK(hipMalloc(&h->i_nobs, 4 * h->s_obs * K));
+            EMCHK(hipMalloc(&h->i_keep, h->s_keep * K));
+            EMCHK(hipFuncSetAttribute((const void*)em_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+            EMCHK(hipFuncSetAttribute((const void*)em_seq_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      h->lds_bytes));
+            if (h->sweep)
+                EMCHK(hipFuncSetAttribute((const void*)em_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          h->sweep_lds));
 #ifdef FQ_DIAG
-        if (h->sweep && std::getenv("FQLPOP_EM_PROBE")) {
-            EMCHK(hipHostMalloc((void**)&h->probe, 8 * EM_PH_N, hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(h->probe, 0, 8 * EM_PH_N);
-        }
+            if (h->sweep && std::getenv("FQLPOP_EM_PROBE")) {
+                EMCHK(hipHostMalloc((void**)&h->probe, 8 * EM_PH_N, hipHostMallocMapped | hipHostMallocCoherent));
+                std::memset(h->probe, 0, 8 * EM_PH_N);
+            }
 #endif
+        } catch (...) {
+            em_free(h.get());
+            throw;
+        }
         *out = h.release();
+    }
+}
+
+extern "C" {
+
+int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params, int64_t n_params, int device,
+                          fqlpop_emtrain_t** out) {
+    return em_guard([&] {
+        EMARG(cfg && params && out, "null argument");
+        em_create(cfg, 1, params, n_params, &cfg->seed, 0, device, out);
+    });
+}
+
+int fqlpop_emtrain_create_ensemble(const fqlpop_emtrain_config* cfg, int n_models, const float* params,
+                                   int64_t n_params, const uint64_t* seeds, int device, fqlpop_emtrain_t** out) {
+    return em_guard([&] {
+        EMARG(cfg && params && out, "null argument");
+        EMARG(seeds, "null seeds: an ensemble takes one seed per model");
+        EMARG(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
+        em_create(cfg, n_models, params, n_params, seeds, fq::engine_option_em_ens_xcd(), device, out);
+    });
+}
+
+int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models) {
+    return em_guard([&] {
+        EMARG(h && n_models, "null argument");
+        *n_models = h->K;
+    });
+}
+
+int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xcd_mode, int linear_block,
+                                      int* grid_blocks, int* model, int* block) {
+    return em_guard([&] {
+        EMARG(grid_blocks && model && block, "null argument");
+        EMARG(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
+        EMARG(blocks_per_model >= 1 && blocks_per_model <= (1 << 20), "blocks_per_model must be 1..2^20");
+        EMARG(xcd_mode == 0 || xcd_mode == 1, "xcd_mode must be 0 or 1");
+        int m = -1, b = -1;
+        const int grid = ens_block_map(n_models, blocks_per_model, xcd_mode, 0, &m, &b);
+        EMARG(linear_block >= 0 && linear_block < grid, "linear_block outside the grid");
+        ens_block_map(n_models, blocks_per_model, xcd_mode, linear_block, &m, &b);
+        *grid_blocks = grid;
+        *model = m;
+        *block = b;
     });
 }
 
@@ -1607,9 +1834,18 @@ int fqlpop_emtrain_set_dataset(fqlpop_emtrain_t* h, const float* obs, const floa
     });
 }
 
-static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected) {
+// shared: an injected batch is one [B..] batch for every model (model stride 0)
+static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected, bool shared = false) {
     const auto& c = h->cfg;
     StepArgs a{};
+    a.ens.n_models = h->K;
+    a.ens.bpm = h->blocks;
+    a.ens.xcd = h->xcd;
+    a.ens.par = h->s_par; a.ens.part = h->s_part; a.ens.logs = h->s_logs; a.ens.seq = h->s_seq;
+    if (injected && !shared && h->K > 1) {
+        a.ens.obs = h->s_obs; a.ens.act = h->s_act; a.ens.rew = h->s_rew; a.ens.keep = h->s_keep;
+    }
+    for (int k = 0; k < h->K; ++k) a.ens.seeds[k] = h->seeds[k];
     a.kind = c.kind;
     a.train = train ? 1 : 0;
     a.net = h->net;
@@ -1629,7 +1865,6 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected) {
         a.obs = h->d_obs; a.act = h->d_act; a.rew = h->d_rew; a.nobs = h->d_nobs;
         a.n_rows = h->n_rows;
     }
-    a.seed = c.seed;
     a.step = h->count;
     a.B = c.batch_size; a.D = c.obs_dim; a.A = c.action_dim;
     a.tw = c.kind != FQLPOP_EM_TERMINATION ? c.termination_weight : 0.f;
@@ -1650,25 +1885,30 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected) {
 }
 
 static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
+    // K x blocks blocks through the block map (one model, no remap: the blocks themselves)
+    int m0, b0;
+    const unsigned grid = (unsigned)ens_block_map(h->K, h->blocks, h->xcd, 0, &m0, &b0);
+    const unsigned K = (unsigned)h->K;
     if (h->sweep) {
-        hipLaunchKernelGGL(em_sweep_kernel, dim3(h->blocks), dim3(SW_NT), h->sweep_lds, h->s, a);
+        hipLaunchKernelGGL(em_sweep_kernel, dim3(grid), dim3(SW_NT), h->sweep_lds, h->s, a);
         EMCHK(hipGetLastError());
         if (a.train) {
             SeqDwArgs d{};
             d.seq = h->seq; d.seq_stride = h->seq_stride; d.part = h->part; d.P = h->P; d.net = h->net;
             d.T = h->T; d.tchunks = h->tchunks; d.K0 = h->net.dims[0]; d.D = h->cfg.obs_dim;
+            d.ens_seq = h->s_seq; d.ens_part = h->s_part;
             int tot = 0;
             for (int i = 0; i < h->net.n; ++i) {
                 d.first[i] = tot;
                 tot += ((h->net.dims[i] + 63) / 64) * ((h->net.dims[i + 1] + 63) / 64);
             }
             d.first[h->net.n] = tot;
-            hipLaunchKernelGGL(em_seq_dw_kernel, dim3(h->blocks * h->tchunks * tot), dim3(256), 0, h->s, d);
+            hipLaunchKernelGGL(em_seq_dw_kernel, dim3(h->blocks * h->tchunks * tot, K), dim3(256), 0, h->s, d);
         }
     } else if (h->cfg.kind == FQLPOP_EM_MULTISTEP) {
-        hipLaunchKernelGGL(em_seq_grad_kernel, dim3(h->blocks), dim3(NT), h->lds_bytes, h->s, a);
+        hipLaunchKernelGGL(em_seq_grad_kernel, dim3(grid), dim3(NT), h->lds_bytes, h->s, a);
     } else {
-        hipLaunchKernelGGL(em_grad_kernel, dim3(h->blocks), dim3(NT), h->lds_bytes, h->s, a);
+        hipLaunchKernelGGL(em_grad_kernel, dim3(grid), dim3(NT), h->lds_bytes, h->s, a);
     }
     EMCHK(hipGetLastError());
     if (!a.train) return;
@@ -1678,10 +1918,11 @@ static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
     AdamArgsEm ad{};
     ad.params = h->params; ad.wt = h->wt; ad.net = h->net; ad.m = h->m; ad.v = h->v; ad.part = h->part;
     ad.P = h->P; ad.blocks = h->blocks * h->tchunks;
+    ad.ens_par = h->s_par; ad.ens_part = h->s_part;
     ad.lr = (float)(c.init_lr * 0.5 * (1.0 + std::cos(3.14159265358979323846 * cc / c.steps)));
     ad.bc1 = (float)(1.0 - std::pow(0.9, (double)(h->count + 1)));
     ad.bc2 = (float)(1.0 - std::pow(0.999, (double)(h->count + 1)));
-    hipLaunchKernelGGL(em_adam_kernel, dim3((unsigned)((h->P + 255) / 256)), dim3(256), 0, h->s, ad);
+    hipLaunchKernelGGL(em_adam_kernel, dim3((unsigned)((h->P + 255) / 256), K), dim3(256), 0, h->s, ad);
     EMCHK(hipGetLastError());
     ++h->count;
 }
@@ -1701,10 +1942,16 @@ int fqlpop_emtrain_step(fqlpop_emtrain_t* h, int n_steps) {
     });
 }
 
+// the single-model entry points refuse an ensemble handle, naming the call that serves it
+#define EM_SINGLE(h, call) \
+    EMARG((h)->K == 1, "this handle holds an ensemble of models: use " call)
+
+// nb batches ([nb][B..] host arrays; 1: the one batch of a single model or a shared one) into
+// the injected slots 0..nb-1
 static void em_upload_batch(fqlpop_emtrain* h, const float* obs, const float* act, const float* rew,
-                            const float* next_obs) {
+                            const float* next_obs, int nb = 1) {
     EMARG(obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null batch array");
-    const long long B = (long long)h->cfg.batch_size * h->T, D = h->cfg.obs_dim, A = h->cfg.action_dim;
+    const long long B = (long long)h->cfg.batch_size * h->T * nb, D = h->cfg.obs_dim, A = h->cfg.action_dim;
     EMCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * D, hipMemcpyHostToDevice, h->s));
     if (A) EMCHK(hipMemcpyAsync(h->i_act, act, 4 * B * A, hipMemcpyHostToDevice, h->s));
     EMCHK(hipMemcpyAsync(h->i_rew, rew, 4 * B, hipMemcpyHostToDevice, h->s));
@@ -1715,6 +1962,7 @@ int fqlpop_emtrain_step_injected(fqlpop_emtrain_t* h, const float* obs, const fl
                                  const float* next_obs, const uint8_t* keep_mask) {
     return em_guard([&] {
         EMARG(h, "null handle");
+        EM_SINGLE(h, "fqlpop_emtrain_step_injected_ensemble");
         em_check_ready(h);
         EMCHK(hipSetDevice(h->device));
         em_upload_batch(h, obs, act, rew, next_obs);
@@ -1729,11 +1977,28 @@ int fqlpop_emtrain_step_injected(fqlpop_emtrain_t* h, const float* obs, const fl
     });
 }
 
-// logs [FQLPOP_EM_LOG_STRIDE] from the per-block sums (layout: include/fqlpop.h)
-static void em_logs(fqlpop_emtrain* h, float* out) {
-    std::vector<float> lg((size_t)NLOG * h->blocks);
-    EMCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
-    EMCHK(hipStreamSynchronize(h->s));
+int fqlpop_emtrain_step_injected_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
+                                          const float* next_obs, const uint8_t* keep_mask, int shared) {
+    return em_guard([&] {
+        EMARG(h, "null handle");
+        EMARG(shared == 0 || shared == 1, "shared must be 0 or 1");
+        em_check_ready(h);
+        EMCHK(hipSetDevice(h->device));
+        const int nb = shared ? 1 : h->K;
+        em_upload_batch(h, obs, act, rew, next_obs, nb);
+        StepArgs a = em_args(h, true, true, shared != 0);
+        if (keep_mask) {
+            EMCHK(hipMemcpyAsync(h->i_keep, keep_mask, (size_t)h->cfg.batch_size * h->cfg.obs_dim * nb,
+                                 hipMemcpyHostToDevice, h->s));
+            a.keep = h->i_keep;
+        }
+        em_launch_step(h, a);
+        EMCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
+    });
+}
+
+// one model's logs [FQLPOP_EM_LOG_STRIDE] from its per-block sums lg (layout: include/fqlpop.h)
+static void em_logs_model(const fqlpop_emtrain* h, const float* lg, float* out) {
     double s[NLOG] = {0};
     for (int b = 0; b < h->blocks; ++b)
         for (int k = 0; k < NLOG; ++k) s[k] += lg[(size_t)b * NLOG + k];
@@ -1756,8 +2021,25 @@ static void em_logs(fqlpop_emtrain* h, float* out) {
         out[5] = (float)(s[4] > 0 ? s[7] / s[4] : 1.0);
     }
 }
+// logs [K][FQLPOP_EM_LOG_STRIDE]: one copy and one synchronisation for all K models
+static void em_logs(fqlpop_emtrain* h, float* out) {
+    std::vector<float> lg((size_t)h->s_logs * h->K);
+    EMCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
+    EMCHK(hipStreamSynchronize(h->s));
+    for (int k = 0; k < h->K; ++k)
+        em_logs_model(h, lg.data() + (size_t)k * h->s_logs, out + (size_t)k * FQLPOP_EM_LOG_STRIDE);
+}
 
 int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs) {
+    return em_guard([&] {
+        EMARG(h && logs, "null argument");
+        EM_SINGLE(h, "fqlpop_emtrain_read_logs_ensemble");
+        EMCHK(hipSetDevice(h->device));
+        em_logs(h, logs);
+    });
+}
+
+int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs) {
     return em_guard([&] {
         EMARG(h && logs, "null argument");
         EMCHK(hipSetDevice(h->device));
@@ -1769,6 +2051,7 @@ int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act,
                         const float* next_obs, float* logs) {
     return em_guard([&] {
         EMARG(h && logs, "null argument");
+        EM_SINGLE(h, "fqlpop_emtrain_eval_ensemble");
         em_check_ready(h);
         EMCHK(hipSetDevice(h->device));
         em_upload_batch(h, obs, act, rew, next_obs);
@@ -1777,15 +2060,41 @@ int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act,
     });
 }
 
+int fqlpop_emtrain_eval_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
+                                 const float* next_obs, int shared, float* logs) {
+    return em_guard([&] {
+        EMARG(h && logs, "null argument");
+        EMARG(shared == 0 || shared == 1, "shared must be 0 or 1");
+        em_check_ready(h);
+        EMCHK(hipSetDevice(h->device));
+        em_upload_batch(h, obs, act, rew, next_obs, shared ? 1 : h->K);
+        em_launch_step(h, em_args(h, false, true, shared != 0));
+        em_logs(h, logs);
+    });
+}
+
+static void em_get_params(fqlpop_emtrain* h, int model, int which, float* out, int64_t n) {
+    EMARG(n == h->P, "params size mismatch");
+    EMARG(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
+    EMCHK(hipSetDevice(h->device));
+    const float* src = (which == 0 ? h->params : which == 1 ? h->m : h->v) + model * h->s_par;
+    EMCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
+    EMCHK(hipStreamSynchronize(h->s));
+}
+
 int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_t n) {
     return em_guard([&] {
         EMARG(h && out, "null argument");
-        EMARG(n == h->P, "params size mismatch");
-        EMARG(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
-        EMCHK(hipSetDevice(h->device));
-        const float* src = which == 0 ? h->params : which == 1 ? h->m : h->v;
-        EMCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
-        EMCHK(hipStreamSynchronize(h->s));
+        EM_SINGLE(h, "fqlpop_emtrain_get_params_model");
+        em_get_params(h, 0, which, out, n);
+    });
+}
+
+int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, float* out, int64_t n) {
+    return em_guard([&] {
+        EMARG(h && out, "null argument");
+        EMARG(model >= 0 && model < h->K, "model index out of range");
+        em_get_params(h, model, which, out, n);
     });
 }
 

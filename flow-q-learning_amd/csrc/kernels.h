@@ -520,5 +520,7 @@ void launch_replay(const ReplayArgs& a, hipStream_t s);
 void set_last_error(const char* msg);
 // engine option em_seq_sweep (runtime.cpp), read by fqlpop_emtrain_create
 int engine_option_em_seq_sweep();
+// engine option em_ens_xcd (runtime.cpp), read by fqlpop_emtrain_create_ensemble
+int engine_option_em_ens_xcd();
 
 }  // namespace fq

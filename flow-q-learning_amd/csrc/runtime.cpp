@@ -87,6 +87,9 @@ struct EngineOptions {
                            // one stream (graph launch and hardware queues)
     int em_seq_sweep = 1;  // env-model multistep training: the 1024-thread BPTT sweep with dW as a separate
                            // GEMM (emtrain.hip); 0 = the round-5 kernel (dW inside the time loop)
+    int em_ens_xcd = 0;    // env-model ensemble training: 1 = deal the K models' blocks so that the block
+                           // ids sharing an XCD hold at most ceil(K / 8) models (emtrain.hip,
+                           // ens_block_map); 0 = model-major.  Same results either way.
 };
 // (Schedule experiments that measured slower were removed in round 4 and stay in git history
 // and DESIGN.md section 5: a 4th stream, stream priorities, the critic optimiser on the main
@@ -123,6 +126,7 @@ const EngineOptionRef kEngineOptions[] = {
     {"split_sites", &EngineOptions::split_sites, 0, (1 << 24) - 1},
     {"split_blocks", &EngineOptions::split_blocks, 64, 1024},
     {"em_seq_sweep", &EngineOptions::em_seq_sweep, 0, 1},
+    {"em_ens_xcd", &EngineOptions::em_ens_xcd, 0, 1},
 };
 
 // ---------------------------------------------------------------- host Philox
@@ -1751,6 +1755,7 @@ void check_member(fqlpop* h, int member) {
 
 void fq::set_last_error(const char* msg) { g_err = msg ? msg : ""; }
 int fq::engine_option_em_seq_sweep() { return g_engine_opts.em_seq_sweep; }
+int fq::engine_option_em_ens_xcd() { return g_engine_opts.em_ens_xcd; }
 
 // =================================================================== C ABI ==
 extern "C" {

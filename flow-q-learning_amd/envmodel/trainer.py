@@ -9,6 +9,11 @@ itself is ``fqlpop_emtrain_*`` (include/fqlpop.h): one fused HIP launch for
 forward + loss + backward of the 16-row blocks and one for the Adam update.
 There is no CPU path: a missing libfqlpop.so raises.
 
+``StatePredictorEnsembleTrainer`` / ``TerminationPredictorEnsembleTrainer`` train K models
+that differ only in seed behind one handle (``fqlpop_emtrain_create_ensemble``): the same
+launches with a model axis, model k bitwise the single trainer of seed k [no reference
+counterpart: the reference loops over its trainer].
+
 Differences to the reference, by necessity:
 
 * models are specified by ``EnvModelSpec`` + a parameter tree (flax is absent);
@@ -87,9 +92,20 @@ class _GpuEnvModelTrainer:
     def __init__(self, spec: em.EnvModelSpec, params: dict, train_loader, val_loader, config: EnvModelTrainerConfig,
                  logger=None, device: int = 0, tp_params: dict | None = None, focal_alpha=DEFAULT_FOCAL_ALPHA,
                  focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT):
+        flat = self._setup(spec, [params], train_loader, val_loader, config, focal_alpha, focal_gamma, dropout_rate)
+        self.logger = logger
+        h = ctypes.c_void_p()
+        self._check(self._lib.fqlpop_emtrain_create(ctypes.byref(self._cfg), self._fptr(flat), flat.size, int(device),
+                                                    ctypes.byref(h)))
+        self._h = h
+        self._finish_setup(tp_params)
+
+    # ------------------------------------------------------------- plumbing
+    def _setup(self, spec, params_list, train_loader, val_loader, config, focal_alpha, focal_gamma, dropout_rate):
+        """The C config (self._cfg), the leaf layout, and the flat [len(params_list)][P] parameters."""
         from fqlpop._lib import EM_MULTISTEP, EmTrainConfig, check, fptr, load_library
         self._lib, self._check, self._fptr = load_library(), check, fptr
-        self.spec, self.config, self.logger = spec, config, logger
+        self.spec, self.config = spec, config
         self.train_loader, self.val_loader = train_loader, val_loader
         # the multistep model (train_env_model.py:46-66) trains the same cell through a scan
         self._ms = self.kind == 0 and getattr(config, "model", "baseline") == "multistep"
@@ -116,31 +132,31 @@ class _GpuEnvModelTrainer:
         if self.kind == 0:
             self._names = em.sp_leaf_names(spec)
             self._shapes = _leaf_shapes(self._names, spec.sp_dims(), spec.obs_dim + spec.action_dim)
-            flat = em.flatten_state_predictor(spec, params)
+            flats = [em.flatten_state_predictor(spec, p) for p in params_list]
         else:
             self._names = em.tp_leaf_names(spec)
             self._shapes = _leaf_shapes(self._names, spec.tp_dims())
-            flat = em.flatten_termination_predictor(spec, params)
+            flats = [em.flatten_termination_predictor(spec, p) for p in params_list]
         n = ctypes.c_int64()
         check(self._lib.fqlpop_emtrain_param_count(ctypes.byref(c), ctypes.byref(n)))
-        if n.value != flat.size:
-            raise ValueError(f"parameter count {flat.size} != {n.value}")
+        for flat in flats:
+            if n.value != flat.size:
+                raise ValueError(f"parameter count {flat.size} != {n.value}")
         self.n_params = n.value
-        h = ctypes.c_void_p()
-        flat = _f32(flat)
-        check(self._lib.fqlpop_emtrain_create(ctypes.byref(c), fptr(flat), flat.size, int(device), ctypes.byref(h)))
-        self._h = h
-        if self.kind == 0 and c.termination_weight > 0:
+        return _f32(np.concatenate([np.asarray(f, np.float32).reshape(-1) for f in flats]))
+
+    def _finish_setup(self, tp_params):
+        """The shared frozen termination predictor and the device-resident dataset."""
+        if self.kind == 0 and self._cfg.termination_weight > 0:
             if tp_params is None:
                 raise ValueError("termination_weight > 0 needs the trained termination predictor (tp_params)")
-            tflat = _f32(em.flatten_termination_predictor(spec, tp_params))
-            check(self._lib.fqlpop_emtrain_set_frozen_termination(h, fptr(tflat), tflat.size))
-        ds = getattr(train_loader, "dataset", None) if train_loader is not None else None
+            tflat = _f32(em.flatten_termination_predictor(self.spec, tp_params))
+            self._check(self._lib.fqlpop_emtrain_set_frozen_termination(self._h, self._fptr(tflat), tflat.size))
+        ds = getattr(self.train_loader, "dataset", None) if self.train_loader is not None else None
         self._device_sampling = isinstance(ds, dict) and "observations" in ds
         if self._device_sampling:
             self._set_dataset(ds)
 
-    # ------------------------------------------------------------- plumbing
     def _set_dataset(self, ds: dict):
         # rows (a multistep loader holds [episodes][episode_length][..]: flattened back to rows)
         D, A = self.spec.obs_dim, self.spec.action_dim
@@ -276,3 +292,136 @@ class TerminationPredictorTrainer(_GpuEnvModelTrainer):
 
     def _eval_keys(self):
         return TP_EVAL_LOG_KEYS
+
+
+class _GpuEnvModelEnsembleTrainer(_GpuEnvModelTrainer):
+    """K models of one kind behind one handle (fqlpop_emtrain_create_ensemble): every train
+    step is one launch chain for all K.  The models share the spec, the config (schedule, step
+    count, batch size), the dataset and the frozen termination predictor; model k has its own
+    initial tree, seed (minibatch draw, dropout mask), logger and val sampling stream.  Model
+    k is bitwise the single trainer built with ``config.seed = seeds[k]`` and
+    ``params_list[k]``."""
+
+    def __init__(self, spec: em.EnvModelSpec, params_list, train_loader, val_loader, config: EnvModelTrainerConfig,
+                 seeds, loggers=None, device: int = 0, tp_params: dict | None = None, val_rngs=None,
+                 focal_alpha=DEFAULT_FOCAL_ALPHA, focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT):
+        self.K = len(params_list)
+        self.seeds = [int(s) for s in seeds]
+        if len(self.seeds) != self.K:
+            raise ValueError(f"{self.K} parameter trees but {len(self.seeds)} seeds")
+        self.loggers = list(loggers) if loggers is not None else None
+        if self.loggers is not None and len(self.loggers) != self.K:
+            raise ValueError(f"{self.K} models but {len(self.loggers)} loggers")
+        # per-model val sampling: model k's host batches come from its own stream (the sequential
+        # runs draw them from the global stream after np.random.seed(seed_k): the same draws)
+        self.val_rngs = list(val_rngs) if val_rngs is not None else [np.random.RandomState(s) for s in self.seeds]
+        if len(self.val_rngs) != self.K:
+            raise ValueError(f"{self.K} models but {len(self.val_rngs)} val streams")
+        flat = self._setup(spec, list(params_list), train_loader, val_loader, config, focal_alpha, focal_gamma,
+                           dropout_rate)
+        sd = (ctypes.c_uint64 * self.K)(*[s & 0xFFFFFFFFFFFFFFFF for s in self.seeds])
+        h = ctypes.c_void_p()
+        self._check(self._lib.fqlpop_emtrain_create_ensemble(ctypes.byref(self._cfg), self.K, self._fptr(flat),
+                                                             flat.size, sd, int(device), ctypes.byref(h)))
+        self._h = h
+        self._finish_setup(tp_params)
+
+    @property
+    def logger(self):
+        return self.loggers
+
+    # --------------------------------------------------------------- batches
+    def _ens_batch(self, batches):
+        """One batch dict (shared by all models) or K of them -> (stacked arrays, shared flag)."""
+        if isinstance(batches, dict):
+            return self._batch_ptrs(batches), 1
+        if len(batches) != self.K:
+            raise ValueError(f"{self.K} models but {len(batches)} batches")
+        per = [self._batch_ptrs(b) for b in batches]
+        return [np.ascontiguousarray(np.stack([p[i] for p in per])) for i in range(4)], 0
+
+    def train_step(self, state=None, batches=None, keep_masks=None):
+        """One update of every model on host batches (a dict: one batch for all; a list: one per
+        model); keep_masks likewise one [B][D] mask or K of them.  Returns (self, K log dicts)."""
+        arrs, shared = self._ens_batch(batches)
+        km = None
+        if keep_masks is not None:
+            km = np.ascontiguousarray(np.asarray(keep_masks, np.uint8))
+            want = 2 if shared else 3
+            if km.ndim != want:
+                raise ValueError("keep_masks must be one [B][D] mask with a shared batch, K of them otherwise")
+        self._check(self._lib.fqlpop_emtrain_step_injected_ensemble(
+            self._h, *[self._fptr(a) for a in arrs],
+            km.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if km is not None else None, shared))
+        return self, self.read_logs()
+
+    def eval_step(self, state=None, batches=None) -> list:
+        arrs, shared = self._ens_batch(batches)
+        out = np.zeros((self.K, 8), np.float32)
+        self._check(self._lib.fqlpop_emtrain_eval_ensemble(self._h, *[self._fptr(a) for a in arrs], shared,
+                                                           self._fptr(out)))
+        return [self._logs(out[k], self._eval_keys()) for k in range(self.K)]
+
+    def read_logs_raw(self) -> np.ndarray:
+        out = np.zeros((self.K, 8), np.float32)
+        self._check(self._lib.fqlpop_emtrain_read_logs_ensemble(self._h, self._fptr(out)))
+        return out
+
+    def read_logs(self) -> list:
+        out = self.read_logs_raw()
+        return [self._logs(out[k], self._train_keys()) for k in range(self.K)]
+
+    def flat(self, k: int, which: int = 0) -> np.ndarray:
+        out = np.zeros(self.n_params, np.float32)
+        self._check(self._lib.fqlpop_emtrain_get_params_model(self._h, int(k), int(which), self._fptr(out),
+                                                              self.n_params))
+        return out
+
+    @property
+    def params(self) -> list:
+        return [unflatten(self._names, self._shapes, self.flat(k, 0)) for k in range(self.K)]
+
+    def _sample(self, loader, k: int) -> dict:
+        return loader.sample(self.config.batch_size, rng=self.val_rngs[k])
+
+    def _val(self, step: int):
+        if self.val_loader is None:
+            return
+        logs = [self.eval_step(None, [self._sample(self.val_loader, k) for k in range(self.K)])
+                for _ in range(self.config.val_batches)]
+        if self.loggers:
+            for k in range(self.K):
+                for key in logs[0][k]:
+                    self.loggers[k].log({f"val/{key}": float(np.mean([lg[k][key] for lg in logs]))}, step=step)
+
+    def train(self) -> None:
+        """The reference loop once for all K models: val every 100 steps, one update of every
+        model per step, one log read for all K, K log rows, a final val pass."""
+        for step in range(self.config.steps):
+            if step % 100 == 0:
+                self._val(step)
+            if self._device_sampling:
+                self.steps(1)
+                logs = self.read_logs() if self.loggers else None
+            else:
+                _, logs = self.train_step(None, [self._sample(self.train_loader, k) for k in range(self.K)])
+            if self.loggers:
+                lr = self.learning_rate(step)
+                for k in range(self.K):
+                    self.loggers[k].log({"train/learning_rate": lr,
+                                         **{f"train/{key}": v for key, v in logs[k].items()}}, step=step)
+        self._val(self.config.steps - 1)
+
+
+class StatePredictorEnsembleTrainer(_GpuEnvModelEnsembleTrainer):
+    """K StatePredictorTrainer runs (baseline or multistep) as one launch per step."""
+    kind = 0
+    _train_keys = StatePredictorTrainer._train_keys
+    _eval_keys = StatePredictorTrainer._eval_keys
+
+
+class TerminationPredictorEnsembleTrainer(_GpuEnvModelEnsembleTrainer):
+    """K TerminationPredictorTrainer runs as one launch per step."""
+    kind = 1
+    _train_keys = TerminationPredictorTrainer._train_keys
+    _eval_keys = TerminationPredictorTrainer._eval_keys

@@ -172,6 +172,17 @@ _SIGS = {
     "fqlpop_emtrain_get_params": (ctypes.c_int, [_P, ctypes.c_int, _F, ctypes.c_int64]),
     "fqlpop_emtrain_get_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_sync": (ctypes.c_int, [_P]),
+    "fqlpop_emtrain_create_ensemble": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.c_int, _F, ctypes.c_int64,
+                                                      ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
+                                                      ctypes.POINTER(_P)]),
+    "fqlpop_emtrain_num_models": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
+    "fqlpop_emtrain_step_injected_ensemble": (ctypes.c_int, [_P, _F, _F, _F, _F, _U8, ctypes.c_int]),
+    "fqlpop_emtrain_eval_ensemble": (ctypes.c_int, [_P, _F, _F, _F, _F, ctypes.c_int, _F]),
+    "fqlpop_emtrain_read_logs_ensemble": (ctypes.c_int, [_P, _F]),
+    "fqlpop_emtrain_get_params_model": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F, ctypes.c_int64]),
+    "fqlpop_emtrain_ensemble_block_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                         ctypes.POINTER(ctypes.c_int)]),
     "fqlpop_initobs_param_count": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_initobs_create": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

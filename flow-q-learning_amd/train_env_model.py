@@ -13,10 +13,13 @@ starts (InitialObservationLoader), honouring ``--model.hidden_dims``, ``--model.
 and ``--reconstruction_weight``, and saves ``{"params": {"encoder", "decoder"}}`` with
 ``hidden_dims`` and ``latent_dim`` in the yaml: the files distribution_visualizer.py:62-99 reads.
 
-``--ensemble_size K`` trains K models one after the other, member k with seed
-``--seed + k``, and saves them as ``<model>_ens<k>.pt`` / ``<model>_ens<k>_config.yaml`` /
-``<model>_ens<k>_log.csv``: the files task/offline_task_simulated.py loads with
-``ensemble_size=K``.  Without the flag names and behaviour are the reference's.
+``--ensemble_size K`` trains K models, member k with seed ``--seed + k``, and saves them as
+``<model>_ens<k>.pt`` / ``<model>_ens<k>_config.yaml`` / ``<model>_ens<k>_log.csv``: the
+files task/offline_task_simulated.py loads with ``ensemble_size=K``.  With K >= 2 the K
+models of the kinds in ``BATCHED_KINDS`` train as one launch per step
+(envmodel.trainer.*EnsembleTrainer; K <= 16) and the files are byte for byte those of K runs
+one after the other, which ``--ensemble_sequential`` still does.  Without
+``--ensemble_size`` names and behaviour are the reference's.
 """
 from __future__ import annotations
 
@@ -35,7 +38,8 @@ import envmodel as em  # noqa: E402
 from argparser import build_env_model_config_from_args, get_env_model_argparser  # noqa: E402
 from envmodel import initial_observation as iobs  # noqa: E402
 from envmodel.flax_msgpack import msgpack_serialize  # noqa: E402
-from envmodel.trainer import StatePredictorTrainer, TerminationPredictorTrainer  # noqa: E402
+from envmodel.trainer import (StatePredictorEnsembleTrainer, StatePredictorTrainer,  # noqa: E402
+                              TerminationPredictorEnsembleTrainer, TerminationPredictorTrainer)
 from task.offline_task_npz import load_npz_dataset  # noqa: E402
 from utils.logger import CsvLogger  # noqa: E402
 
@@ -43,11 +47,13 @@ from utils.logger import CsvLogger  # noqa: E402
 class StepLoader:
     """utils/data_loader.py:47-52: uniform minibatches of single transitions."""
 
-    def __init__(self, dataset: dict):
+    def __init__(self, dataset: dict, rng=None):
         self.dataset = {k: dataset[k] for k in ("observations", "actions", "rewards", "next_observations")}
+        self.rng = rng  # a np.random.RandomState; None: the global numpy stream
 
-    def sample(self, batch_size: int) -> dict:
-        idx = np.random.randint(len(self.dataset["observations"]), size=batch_size)
+    def sample(self, batch_size: int, rng=None) -> dict:
+        rng = rng or self.rng or np.random
+        idx = rng.randint(len(self.dataset["observations"]), size=batch_size)
         return {k: v[idx] for k, v in self.dataset.items()}
 
 
@@ -58,8 +64,9 @@ class MultistepLoader:
 
     episode_length = 1000
 
-    def __init__(self, dataset: dict, sequence_length: int = 128):
+    def __init__(self, dataset: dict, sequence_length: int = 128, rng=None):
         self.sequence_length = sequence_length
+        self.rng = rng  # as StepLoader
         n = len(dataset["observations"])
         if n % self.episode_length:
             raise ValueError(f"multistep: {n} rows is not a whole number of {self.episode_length}-step episodes")
@@ -67,9 +74,10 @@ class MultistepLoader:
         self.dataset = {k: np.asarray(dataset[k]).reshape(shape + np.shape(dataset[k])[1:])
                         for k in ("observations", "actions", "rewards", "next_observations")}
 
-    def sample(self, batch_size: int) -> dict:
-        ep = np.random.randint(len(self.dataset["observations"]), size=batch_size)
-        start = np.random.randint(0, self.episode_length - self.sequence_length, size=batch_size)
+    def sample(self, batch_size: int, rng=None) -> dict:
+        rng = rng or self.rng or np.random
+        ep = rng.randint(len(self.dataset["observations"]), size=batch_size)
+        start = rng.randint(0, self.episode_length - self.sequence_length, size=batch_size)
         idx = start[:, None] + np.arange(self.sequence_length)
         return {k: v[ep[:, None], idx] for k, v in self.dataset.items()}
 
@@ -79,13 +87,15 @@ class InitialObservationLoader:
 
     episode_length = 1000
 
-    def __init__(self, dataset: dict):
+    def __init__(self, dataset: dict, rng=None):
         idx = np.arange(0, len(dataset["observations"]), self.episode_length)
         self.indices = idx
         self.dataset = {k: np.asarray(v)[idx] for k, v in dataset.items() if len(v) == len(dataset["observations"])}
+        self.rng = rng  # as StepLoader
 
-    def sample(self, batch_size: int) -> dict:
-        idx = np.random.randint(len(self.dataset["observations"]), size=batch_size)
+    def sample(self, batch_size: int, rng=None) -> dict:
+        rng = rng or self.rng or np.random
+        idx = rng.randint(len(self.dataset["observations"]), size=batch_size)
         return {k: v[idx] for k, v in self.dataset.items()}
 
 
@@ -102,9 +112,12 @@ class _CsvRunLogger:
 
 
 def build_parser():
-    """The reference's flags (argparser.py) plus --ensemble_size."""
+    """The reference's flags (argparser.py) plus --ensemble_size and --ensemble_sequential."""
     parser = get_env_model_argparser()
     parser.add_argument("--ensemble_size", type=int, default=0)
+    parser.add_argument("--ensemble_sequential", action="store_true",
+                        help="train the --ensemble_size models one after the other (K runs) instead of "
+                             "as one launch per step; the files are the same")
     return parser
 
 
@@ -125,32 +138,94 @@ def main(argv=None):
         raise ValueError("--ensemble_size is for baseline, multistep and termination_predictor")
     if args.ensemble_size == 0:
         return train_one(*member_config(args, None))
+    if args.ensemble_size >= 2 and not args.ensemble_sequential and args.model in BATCHED_KINDS:
+        return train_ensemble([member_config(args, k) for k in range(args.ensemble_size)])
     for k in range(args.ensemble_size):
         save_dir = train_one(*member_config(args, k))
     return save_dir
 
 
-def train_one(config, name: str):
-    """One training run of config.model, saved under ``name``."""
+# the model kinds whose ensembles train batched by default (the ensemble
+# training table: batched is the default only where it beats the loop at K = 5)
+BATCHED_KINDS = ("baseline", "multistep", "termination_predictor")
+
+
+def _load_data(config):
+    """(train, val, save_dir) of a run."""
     base = config.env_name.replace("-singletask", "").rsplit("-task", 1)[0]
     d = Path(config.data_directory)
     train = load_npz_dataset(d / f"{base}.npz")
     val_path = d / f"{base}-val.npz"
     val = load_npz_dataset(val_path) if val_path.exists() else train
-    D, A = train["observations"].shape[-1], train["actions"].shape[-1]
-    hidden = tuple(config.model_config.get("hidden_dims", em.DEFAULT_HIDDEN))
     save_dir = Path(config.save_directory) / config.env_name / "env_models"
     save_dir.mkdir(parents=True, exist_ok=True)
+    return train, val, save_dir
+
+
+def _state_predictor_spec(config, D, A, hidden, save_dir):
+    """(spec, frozen termination predictor tree or None) of a baseline / multistep run."""
+    spec = em.EnvModelSpec(D, A, hidden, em.DEFAULT_HIDDEN)
+    tp = None
+    if config.termination_weight > 0:  # utils/envmodel.py load_model("termination_predictor")
+        tp = em.load_flax_msgpack(save_dir / "termination_predictor.pt")
+        tp = tp.get("params", tp)
+        n = sum(1 for k in tp if k.startswith("Dense_"))
+        spec.tp_hidden = tuple(int(np.asarray(tp[f"Dense_{i}"]["kernel"]).shape[1]) for i in range(n - 1))
+    return spec, tp
+
+
+def _save(save_dir, name, config, params):
+    with open(save_dir / f"{name}_config.yaml", "w") as f:
+        yaml.safe_dump({k: list(v) if isinstance(v, tuple) else v for k, v in config.model_config.items()}, f)
+    with open(save_dir / f"{name}.pt", "wb") as f:
+        if config.model == "multistep":  # nn.scan(Cell) tree (envmodel/multistep.py:41-52)
+            params = {"ScanCell_0": {"cell": params}}
+        f.write(msgpack_serialize({"params": params}))
+
+
+def train_ensemble(members):
+    """The K runs ``train_one(config_k, name_k)`` as one batched trainer: model k starts from
+    the tree of seed_k, draws its minibatches and dropout mask from seed_k on the device and
+    its val batches from ``RandomState(seed_k)`` (what ``np.random.seed(seed_k)`` gives the
+    sequential run), and logs to its own CSV.  The saved files are those of the K runs."""
+    configs, names = [c for c, _ in members], [n for _, n in members]
+    config = configs[0]
+    train, val, save_dir = _load_data(config)
+    D, A = train["observations"].shape[-1], train["actions"].shape[-1]
+    hidden = tuple(config.model_config.get("hidden_dims", em.DEFAULT_HIDDEN))
+    seeds = [c.seed for c in configs]
+    loggers = [_CsvRunLogger(save_dir / f"{name}_log.csv") for name in names]
+    if config.model in ("baseline", "multistep"):
+        spec, tp = _state_predictor_spec(config, D, A, hidden, save_dir)
+        if config.model == "multistep":
+            loaders = (MultistepLoader(train, config.sequence_length), MultistepLoader(val, config.sequence_length))
+        else:
+            loaders = (StepLoader(train), StepLoader(val))
+        trainer = StatePredictorEnsembleTrainer(spec, [em.init_state_predictor(spec, s) for s in seeds], *loaders,
+                                                config, seeds, loggers=loggers, tp_params=tp)
+    elif config.model == "termination_predictor":
+        spec = em.EnvModelSpec(D, A, em.DEFAULT_HIDDEN, hidden)
+        trainer = TerminationPredictorEnsembleTrainer(spec, [em.init_termination_predictor(spec, s) for s in seeds],
+                                                      StepLoader(train), StepLoader(val), config, seeds,
+                                                      loggers=loggers)
+    else:
+        raise ValueError(f"no batched ensemble trainer for model {config.model!r}")
+    trainer.train()
+    for cfg, name, params in zip(configs, names, trainer.params):
+        _save(save_dir, name, cfg, params)
+    trainer.close()
+    return save_dir
+
+
+def train_one(config, name: str):
+    """One training run of config.model, saved under ``name``."""
+    train, val, save_dir = _load_data(config)
+    D, A = train["observations"].shape[-1], train["actions"].shape[-1]
+    hidden = tuple(config.model_config.get("hidden_dims", em.DEFAULT_HIDDEN))
     logger = _CsvRunLogger(save_dir / f"{name}_log.csv")
     np.random.seed(config.seed)
     if config.model in ("baseline", "multistep"):
-        spec = em.EnvModelSpec(D, A, hidden, em.DEFAULT_HIDDEN)
-        tp = None
-        if config.termination_weight > 0:  # utils/envmodel.py load_model("termination_predictor")
-            tp = em.load_flax_msgpack(save_dir / "termination_predictor.pt")
-            tp = tp.get("params", tp)
-            n = sum(1 for k in tp if k.startswith("Dense_"))
-            spec.tp_hidden = tuple(int(np.asarray(tp[f"Dense_{i}"]["kernel"]).shape[1]) for i in range(n - 1))
+        spec, tp = _state_predictor_spec(config, D, A, hidden, save_dir)
         if config.model == "multistep":
             loaders = (MultistepLoader(train, config.sequence_length), MultistepLoader(val, config.sequence_length))
         else:
@@ -174,13 +249,7 @@ def train_one(config, name: str):
         raise ValueError(f"unknown model {config.model!r} (baseline, multistep, termination_predictor, "
                          "initial_observation)")
     trainer.train()
-    with open(save_dir / f"{name}_config.yaml", "w") as f:
-        yaml.safe_dump({k: list(v) if isinstance(v, tuple) else v for k, v in config.model_config.items()}, f)
-    with open(save_dir / f"{name}.pt", "wb") as f:
-        params = trainer.params
-        if config.model == "multistep":  # nn.scan(Cell) tree (envmodel/multistep.py:41-52)
-            params = {"ScanCell_0": {"cell": params}}
-        f.write(msgpack_serialize({"params": params}))
+    _save(save_dir, name, config, trainer.params)
     trainer.close()
     return save_dir
 

@@ -93,6 +93,10 @@ const char* fqlpop_last_error(void);
  *   em_seq_sweep (0/1, default 1; read by fqlpop_emtrain_create): multistep env-model
  *   training as a forward and a backward sweep per 16 sequences plus a dW GEMM (0: the
  *   round-5 kernel with dW inside the time loop; same oracle tolerance).
+ *   em_ens_xcd (0/1; read by fqlpop_emtrain_create_ensemble): placement of the K models'
+ *   blocks of an ensemble training launch.  0: model-major.  1: the block ids that share an
+ *   XCD (id mod 8) hold at most ceil(K / 8) models, so an XCD's L2 holds those models'
+ *   weights only (fqlpop_emtrain_ensemble_block_map).  Bit-identical results.
  * The defaults are the measured-fastest configuration.  Unknown names or values
  * out of range: FQLPOP_E_ARG.  (Round 3's schedule experiments that measured slower --
  * streams, prio, cdw_sb, dw_stagger, xstep, bc_late, fuse_dq, early_join -- were
@@ -451,6 +455,47 @@ int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs);
 int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_t n);
 int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count);
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h);
+
+/* World-model ensemble training: K models behind one handle, every train step one launch
+ * chain with a model axis (K x batch_size / 16 blocks) instead of K chains (train_env_model.py
+ * --ensemble_size loops train_one).  The models share cfg, the dataset, the frozen termination
+ * predictor and the update count (so the cosine learning rate and Adam's bias corrections);
+ * each has its own parameters, moments and seed (minibatch draw, dropout mask).  cfg->seed is
+ * ignored in favour of seeds[k].  Model k is bitwise the single-model trainer created with
+ * seed seeds[k] and params[k], for every K and either em_ens_xcd placement.
+ * params: [n_models][P] (P = fqlpop_emtrain_param_count), n_params = n_models * P.
+ * n_models outside 1..FQLPOP_EM_ENS_MAX_MODELS, a size mismatch or a null seeds:
+ * FQLPOP_E_ARG before any GPU call.  A multistep handle allocates one record store per model
+ * (about 300 MB each at B = T = 256 and the default widths); a failed allocation is
+ * FQLPOP_E_HIP with the size in the message.
+ * fqlpop_emtrain_set_dataset, _set_frozen_termination, _step, _sync, _get_count and _destroy
+ * serve both kinds of handle.  On a handle with n_models > 1 the single-model calls
+ * _step_injected, _eval, _read_logs and _get_params return FQLPOP_E_ARG and name the call
+ * below that replaces them. */
+#define FQLPOP_EM_ENS_MAX_MODELS 16
+int fqlpop_emtrain_create_ensemble(const fqlpop_emtrain_config* cfg, int n_models, const float* params,
+                                   int64_t n_params, const uint64_t* seeds, int device, fqlpop_emtrain_t** out);
+int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models);
+/* One train_step of every model on host batches.  shared = 1: one [batch_size][..] batch (and
+ * keep mask) for all models; shared = 0: [n_models][batch_size][..] arrays.  keep_mask may be
+ * NULL (each model's Philox dropout mask).  Synchronises. */
+int fqlpop_emtrain_step_injected_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
+                                          const float* next_obs, const uint8_t* keep_mask, int shared);
+/* eval_step of every model (no dropout, no update): logs[n_models][FQLPOP_EM_LOG_STRIDE]. */
+int fqlpop_emtrain_eval_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
+                                 const float* next_obs, int shared, float* logs);
+/* Logs of the last train step of every model, logs[n_models][FQLPOP_EM_LOG_STRIDE]; one
+ * synchronisation for all of them. */
+int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs);
+/* fqlpop_emtrain_get_params of one model; n = P. */
+int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, float* out, int64_t n);
+/* The placement of an ensemble launch of n_models x blocks_per_model blocks (no GPU call):
+ * the grid size, and the (model, block within the model) that linear block id linear_block
+ * runs; model = block = -1 marks a padding block, which exits at once.  xcd_mode as engine
+ * option em_ens_xcd.  n_models outside 1..16, blocks_per_model < 1, xcd_mode outside {0, 1},
+ * linear_block outside the grid: FQLPOP_E_ARG.  [no reference counterpart: introspection] */
+int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xcd_mode, int linear_block,
+                                      int* grid_blocks, int* model, int* block);
 
 /* ---------------------------------------------------------------------------
  * Initial-observation VAE (the decoder as a source of episode
