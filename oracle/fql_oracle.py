@@ -218,30 +218,38 @@ def actor_forward(cfg, pnet, obs, act, t=None):
     return mlp_forward(pnet, np.concatenate(parts, axis=-1), cfg.actor_layer_norm)
 
 
-def compute_flow_actions(cfg, params, obs, noises):
-    """[EXT] FQLAgent.compute_flow_actions: 10 Euler steps of v_theta, then clip."""
+def compute_flow_actions(cfg, params, obs, noises, clip=True):
+    """[EXT] FQLAgent.compute_flow_actions: 10 Euler steps of v_theta, then clip
+    (``clip=False``: the Euler result before the clip, for the tests' state conditions)."""
     x = noises
     B = obs.shape[0]
     for i in range(cfg.flow_steps):
         t = np.full((B, 1), np.float64(np.float32(i / cfg.flow_steps)))
         v, _ = actor_forward(cfg, params["actor_bc_flow"], obs, x, t)
         x = x + v / cfg.flow_steps
-    return np.clip(x, -1.0, 1.0)
+    return np.clip(x, -1.0, 1.0) if clip else x
 
 
-def sample_actions(cfg, params, obs, noises):
+def sample_actions(cfg, params, obs, noises, clip=True):
     """[EXT] FQLAgent.sample_actions with injected noise: clip(mu_omega(s, z))."""
     a, _ = actor_forward(cfg, params["actor_onestep_flow"], obs, noises)
-    return np.clip(a, -1.0, 1.0)
+    return np.clip(a, -1.0, 1.0) if clip else a
 
 
 # ----------------------------------------------------------------------------
 # losses + gradients
 # ----------------------------------------------------------------------------
+# Deliberately wrong variants of ``loss_and_grads`` (its private ``_mutant`` keyword):
+# tests/test_oracle.py uses them to prove that a state can tell a kernel with that
+# mistake from a correct one.  Never set outside that test.
+MUTANTS = ("inside_all_true", "euler_unclipped", "a_next_unclipped", "metric_unclipped")
+
+
 def loss_and_grads(cfg: OracleConfig, params: dict, batch: dict, noise: dict,
-                   want_grads: bool = True):
+                   want_grads: bool = True, _mutant: str | None = None):
     """[EXT] FQLAgent.total_loss = critic_loss + actor_loss, with hand-written
     reverse mode.  ``noise`` keys: z_next, x0, t, z_d, z_metric."""
+    assert _mutant is None or _mutant in MUTANTS, _mutant
     B, A = batch["actions"].shape
     s, a = batch["observations"], batch["actions"]
     s2 = batch["next_observations"]
@@ -249,7 +257,7 @@ def loss_and_grads(cfg: OracleConfig, params: dict, batch: dict, noise: dict,
     grads = {}
 
     # ---- critic loss ------------------------------------------------------
-    a_next = sample_actions(cfg, params, s2, noise["z_next"])
+    a_next = sample_actions(cfg, params, s2, noise["z_next"], clip=_mutant != "a_next_unclipped")
     qt, _ = value_forward(cfg, params["target_critic"], s2, a_next)
     q_next = qt.min(0) if cfg.q_agg == "min" else qt.mean(0)
     y = batch["rewards"] + cfg.discount * batch["masks"] * q_next
@@ -266,7 +274,7 @@ def loss_and_grads(cfg: OracleConfig, params: dict, batch: dict, noise: dict,
     bc_loss = ((pred - vel) ** 2).mean()
 
     # ---- actor: distillation + Q -----------------------------------------
-    a_flow = compute_flow_actions(cfg, params, s, noise["z_d"])
+    a_flow = compute_flow_actions(cfg, params, s, noise["z_d"], clip=_mutant != "euler_unclipped")
     a_pi, os_cache = actor_forward(cfg, params["actor_onestep_flow"], s, noise["z_d"])
     distill = ((a_pi - a_flow) ** 2).mean()
     a_pi_c = np.clip(a_pi, -1.0, 1.0)
@@ -275,7 +283,7 @@ def loss_and_grads(cfg: OracleConfig, params: dict, batch: dict, noise: dict,
     lam = 1.0 / np.abs(qb).mean() if cfg.normalize_q_loss else 1.0
     q_loss = -lam * qb.mean()
     actor_loss = bc_loss + cfg.alpha * distill + q_loss
-    a_met = sample_actions(cfg, params, s, noise["z_metric"])
+    a_met = sample_actions(cfg, params, s, noise["z_metric"], clip=_mutant != "metric_unclipped")
     mse = ((a_met - a) ** 2).mean()
     info.update({"actor/actor_loss": actor_loss, "actor/bc_flow_loss": bc_loss,
                  "actor/distill_loss": distill, "actor/q_loss": q_loss,
@@ -308,6 +316,8 @@ def loss_and_grads(cfg: OracleConfig, params: dict, batch: dict, noise: dict,
                              dqpi[:, None], cfg.layer_norm, need_dx=True)
         da += dx[:, D:]
     inside = (a_pi > -1.0) & (a_pi < 1.0)
+    if _mutant == "inside_all_true":
+        inside = np.ones_like(inside)
     dapi = cfg.alpha * 2.0 * (a_pi - a_flow) / (B * A) + np.where(inside, da, 0.0)
     grads["actor_onestep_flow"], _ = mlp_backward(params["actor_onestep_flow"], os_cache,
                                                   dapi, cfg.actor_layer_norm, need_dx=False)
@@ -325,16 +335,95 @@ def grad_stats(cfg: OracleConfig, grads: dict):
     return gmax, gmin, gnorm
 
 
+def trained_like_params(cfg: OracleConfig, seed: int, q_offset: float = -40.0,
+                        head_scale: float = 3.0) -> dict:
+    """A state that looks like the middle of training rather than its first step, for
+    the parity tests: every term that is 0 or 1 at ``init_params`` (and so could be
+    dropped or mis-indexed unnoticed) is random here.
+
+    * every Dense bias ~ N(0, 0.3), every LayerNorm scale ~ U(0.5, 1.5) and bias
+      ~ N(0, 0.3), each ensemble member's drawn independently;
+    * both actors' head kernels times ``head_scale``, so that a good share of the one-step
+      actor's outputs and of the Euler flow's results lies outside [-1, 1] and every clamp
+      engages (and a good share inside, so that it also does not);
+    * the critic's head bias shifted by ``q_offset`` (about -40: Q of a sparse -1 reward at
+      discount 0.99; 0 keeps Q centred with mixed signs, without which
+      ``normalize_q_loss`` gives q_loss == 1 exactly);
+    * target_critic = critic + noise in every leaf (0.25 of the leaf's mean magnitude
+      times N(0, 1), i.e. a mean difference of 0.2 of it), drawn before ``q_offset``
+      shifts both head biases: a target 0.2 * 40 away from the critic would make the
+      TD error one constant that swamps everything else in the critic loss."""
+    params = init_params(cfg, seed)
+    rng = np.random.default_rng([seed, 0x7A1])
+    for net in TRAINABLE:
+        p = params[net]
+        for k in sorted(p):
+            if k.endswith("/bias") and k.startswith("Dense_"):
+                p[k] = 0.3 * rng.standard_normal(p[k].shape)
+            elif k.endswith("/scale"):
+                p[k] = rng.uniform(0.5, 1.5, p[k].shape)
+            elif k.endswith("/bias"):
+                p[k] = 0.3 * rng.standard_normal(p[k].shape)
+    for net in ("actor_bc_flow", "actor_onestep_flow"):
+        head = f"Dense_{len(cfg.hidden_dims)}/kernel"
+        params[net][head] = params[net][head] * head_scale
+    params["target_critic"] = {
+        k: v + 0.25 * np.abs(v).mean() * rng.standard_normal(v.shape)
+        for k, v in sorted(params["critic"].items())}
+    for net in ("critic", "target_critic"):
+        params[net][f"Dense_{len(cfg.hidden_dims)}/bias"] += q_offset
+    return params
+
+
+def trained_like_opt_state(params: dict, seed: int, count: int, grads: dict | None = None) -> dict:
+    """Adam state of a run ``count`` steps in: m of mixed signs, v = m^2 times U(0.5, 2)
+    (so the step m / sqrt(v) is of order 1, neither vanishing nor huge), both zero for the
+    target critic (its gradient is always zero).  A leaf's m is N(0, 1) times a tenth of
+    the RMS of its gradient in ``grads`` (a tree as ``loss_and_grads`` returns; 1e-4 where
+    not given): then the next step's gradient g and the old moments weigh about the same
+    in 0.9 m + 0.1 g, and g^2 contributes about a tenth of 0.999 v + 0.001 g^2, so a step
+    from this state checks the gradient, the old moments and the accumulation at once."""
+    rng = np.random.default_rng([seed, 0xADA])
+    m, v = {}, {}
+    for net in NETS:
+        m[net], v[net] = {}, {}
+        for k, p in sorted(params[net].items()):
+            if net == "target_critic":
+                m[net][k], v[net][k] = np.zeros_like(p), np.zeros_like(p)
+                continue
+            s = 1e-4
+            if grads is not None:
+                s = max(0.1 * float(np.sqrt(np.mean(grads[net][k] ** 2))), 1e-12)
+            m[net][k] = s * rng.standard_normal(p.shape)
+            v[net][k] = m[net][k] ** 2 * rng.uniform(0.5, 2.0, p.shape)
+    return {"m": m, "v": v, "count": int(count)}
+
+
+def clamp_sites(cfg: OracleConfig, params: dict, batch: dict, noise: dict) -> dict:
+    """What every clamp of one update sees, before it clamps (the tests' conditions on a
+    state: enough entries on both sides of +-1 and none too close to it), and which
+    ensemble member gives the TD target's minimum in each row."""
+    s, s2 = batch["observations"], batch["next_observations"]
+    a_next = sample_actions(cfg, params, s2, noise["z_next"], clip=False)
+    qt, _ = value_forward(cfg, params["target_critic"], s2, np.clip(a_next, -1.0, 1.0))
+    return {"a_pi": sample_actions(cfg, params, s, noise["z_d"], clip=False),
+            "euler": compute_flow_actions(cfg, params, s, noise["z_d"], clip=False),
+            "a_next": a_next,
+            "metric": sample_actions(cfg, params, s, noise["z_metric"], clip=False),
+            "q_target_argmin": qt.argmin(0)}
+
+
 def init_opt_state(params: dict) -> dict:
     return {"m": {n: {k: np.zeros_like(v) for k, v in p.items()} for n, p in params.items()},
             "v": {n: {k: np.zeros_like(v) for k, v in p.items()} for n, p in params.items()},
             "count": 0}
 
 
-def update(cfg: OracleConfig, params: dict, opt: dict, batch: dict, noise: dict):
+def update(cfg: OracleConfig, params: dict, opt: dict, batch: dict, noise: dict,
+           _mutant: str | None = None):
     """[EXT] FQLAgent.update: grads -> optax.adam(lr) over the whole param dict
     -> target EMA from the pre-update critic.  Returns (params', opt', info)."""
-    _, info, grads = loss_and_grads(cfg, params, batch, noise)
+    _, info, grads = loss_and_grads(cfg, params, batch, noise, _mutant=_mutant)
     gmax, gmin, gnorm = grad_stats(cfg, grads)
     info.update({"grad/max": gmax, "grad/min": gmin, "grad/norm": gnorm})
 

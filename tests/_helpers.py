@@ -2,6 +2,8 @@
 from __future__ import annotations
 
 import contextlib
+import functools
+from typing import NamedTuple
 
 import numpy as np
 
@@ -86,3 +88,197 @@ class OptimiserChecker:
             if d.size and float(d.max()) > 2 * self.lr * steps_done + 1e-5:
                 bad.append(f"{name} params: max diff from oracle {float(d.max()):.3g} > 2 lr per step")
         assert not bad, f"{tag}:\n" + "\n".join(bad[:20])
+
+
+# ---------------------------------------------------------------------------
+# trained-like states (oracle.fql_oracle.trained_like_params / trained_like_opt_state)
+# ---------------------------------------------------------------------------
+REL = 1e-4          # info values against the oracle, as tests/test_gpu_parity.py
+TRAINED_COUNT = 1000  # the Adam count the trained-like states start from
+
+
+def f32_tree(tree):
+    """A float64 tree holding float32 values: what the device gets, for the oracle."""
+    from oracle import fql_oracle as O
+    return O.cast_tree(O.cast_tree(tree, np.float32), np.float64)
+
+
+def close(a, b, rel=REL, floor=1e-6):
+    return abs(a - b) <= rel * max(abs(a), abs(b)) + floor
+
+
+def check_info(got, want, keys, tag):
+    bad = []
+    for k in keys:
+        g, w = got[k], float(want[k])
+        if not close(g, w):
+            bad.append(f"{k}: gpu={g:.8g} oracle={w:.8g} rel={abs(g - w) / max(abs(w), 1e-30):.3g}")
+    assert not bad, f"{tag}:\n" + "\n".join(bad)
+
+
+def synthetic_rows(N, D, A, seed):
+    rng = np.random.default_rng(seed)
+    obs = rng.standard_normal((N, D)).astype(np.float32)
+    rew = np.where(rng.uniform(size=N) < 0.05, 0.0, -1.0).astype(np.float32)
+    return {"observations": obs, "actions": rng.uniform(-1 + 1e-5, 1 - 1e-5, (N, A)).astype(np.float32),
+            "rewards": rew, "masks": (1.0 - (rew == 0)).astype(np.float32),
+            "next_observations": (obs + 0.05 * rng.standard_normal((N, D))).astype(np.float32)}
+
+
+class Spec(NamedTuple):
+    """One population member at a trained-like state: its configuration, the seed of its
+    state and of its injected batches, and how many steps the test takes from there."""
+    H: int
+    B: int
+    seed: int
+    alpha: float = 10.0
+    n_steps: int = 1
+    D: int = 28
+    A: int = 5
+    q_offset: float = -40.0
+    kw: tuple = ()          # further OracleConfig / PopulationConfig fields, as sorted items
+    sampled: tuple = ()     # (population seed, dataset rows): the batch and noise are the
+    #                         device sampler's own draws at TRAINED_COUNT, not injected
+
+    def cfg(self):
+        from oracle import fql_oracle as O
+        return O.OracleConfig(obs_dim=self.D, action_dim=self.A, hidden_dims=(self.H,) * 4,
+                              batch_size=self.B, alpha=self.alpha, **dict(self.kw))
+
+
+class TrainedMember:
+    """The float64 oracle's account of one Spec, computed once per process and shared by
+    every test that starts there (read-only): the state, the batches and noises of each
+    step, what every clamp sees in each step, and the oracle's update of each step."""
+
+    def __init__(self, spec: Spec):
+        from oracle import fql_oracle as O
+        self.spec, self.cfg = spec, spec.cfg()
+        cfg, B = self.cfg, spec.B
+        self.params = f32_tree(O.trained_like_params(cfg, spec.seed, q_offset=spec.q_offset))
+        self.batches, self.noises = [], []
+        if spec.sampled:
+            from philox_np import draw, sample_key
+            pop_seed, N = spec.sampled
+            data = O.cast_tree(synthetic_rows(N, spec.D, spec.A, 5), np.float64)
+            for step in range(spec.n_steps):
+                idx, noise = draw(sample_key(pop_seed, spec.alpha), TRAINED_COUNT + step, B, N, spec.A)
+                self.batches.append({k: v[idx] for k, v in data.items()})
+                self.noises.append(noise)
+        else:
+            rng = np.random.default_rng([spec.seed, 1])
+            for _ in range(spec.n_steps):
+                self.batches.append(f32_tree(O.make_batch(cfg, B, rng)))
+                self.noises.append(f32_tree(O.make_noise(cfg, B, rng)))
+        _, _, g = O.loss_and_grads(cfg, self.params, self.batches[0], self.noises[0])
+        self.opt = f32_tree(O.trained_like_opt_state(self.params, spec.seed, TRAINED_COUNT, g))
+        self.sites, self.steps = [], []
+        p, o = self.params, self.opt
+        for b, n in zip(self.batches, self.noises):
+            self.sites.append(O.clamp_sites(cfg, p, b, n))
+            p, o, info = O.update(cfg, p, o, b, n)
+            self.steps.append((p, o, info))
+
+
+@functools.lru_cache(maxsize=None)
+def trained_member(spec: Spec) -> TrainedMember:
+    return TrainedMember(spec)
+
+
+def saturated_share(x):
+    return float((np.abs(x) > 1.0).mean())
+
+
+def check_clamp_conditions(x, tag):
+    """The conditions a trained-like state has to meet at a clamp whose input is ``x``:
+    15-85 % of the entries outside [-1, 1], so that the clamp engages and also does not, and
+    none within 1e-4 of +-1 (100x the float32 error of these values), so that no clamp
+    decision can differ between the device and the float64 oracle."""
+    share = saturated_share(x)
+    assert 0.15 <= share <= 0.85, f"{tag}: {share:.3f} of the entries outside [-1, 1]"
+    margin = float(np.abs(np.abs(x) - 1.0).min())
+    assert margin >= 1e-4, f"{tag}: an entry within {margin:.2e} of +-1"
+
+
+def check_member_conditions(tm: TrainedMember):
+    for step, sites in enumerate(tm.sites):
+        for k in ("a_pi", "euler", "a_next", "metric"):
+            check_clamp_conditions(sites[k], f"{tm.spec} step {step} {k}")
+        if tm.cfg.q_agg == "min":
+            share = np.bincount(sites["q_target_argmin"], minlength=tm.cfg.num_qs) / tm.spec.B
+            assert share.min() >= 0.15, f"{tm.spec} step {step}: min-Q member shares {share}"
+
+
+def _specs(H, B, seeds, alphas=(4.0, 40.0, 400.0), **kw):
+    extra = {k: kw.pop(k) for k in ("n_steps", "D", "A", "q_offset", "sampled") if k in kw}
+    out = []
+    for i, s in enumerate(seeds):
+        e = dict(extra)
+        if "sampled" in e:   # population seeds differ per member, as the states' seeds do
+            e["sampled"] = (e["sampled"][0] + i, e["sampled"][1])
+        out.append(Spec(H, B, s, alphas[i], kw=tuple(sorted(kw.items())), **e))
+    return tuple(out)
+
+
+_MIN = dict(q_agg="min", normalize_q_loss=True, q_offset=0.0)   # mixed-sign Q
+
+# Every state tests/test_gpu_parity_trained.py starts from.  The seeds are chosen so that the
+# float64 oracle alone meets check_member_conditions (tests/test_oracle.py asserts it on the
+# CPU for every entry); nothing here comes from a device's output.
+TRAINED = {
+    "h64": _specs(64, 64, (500, 501), n_steps=2),
+    "h128_no_ln": _specs(128, 64, (501, 502), n_steps=2, layer_norm=False),
+    "h1024": _specs(1024, 64, (500, 503)),
+    "h512": _specs(512, 64, (500, 502, 504)),                # 1, 2 or 3 members: a prefix
+    "h512_d27": _specs(512, 192, (500, 504), D=27, A=5),
+    "h512_d42": _specs(512, 192, (500, 503), D=42, A=8),
+    "h64_min": _specs(64, 64, (500, 502), n_steps=2, **_MIN),
+    "h512_min": _specs(512, 64, (502, 504), **_MIN),
+    "h512_sampled": _specs(512, 64, (500, 501), sampled=(17, 100_003)),
+}
+ALL_TRAINED_SPECS = tuple(sorted({s for group in TRAINED.values() for s in group}))
+
+# sample_actions and the rollout evaluator read the one-step actor of these members
+ACTION_SPECS = (TRAINED["h64"][0], TRAINED["h512"][0])
+ROLLOUT_SPECS = TRAINED["h512"][:2]
+ROLLOUT_ENVS, ROLLOUT_STEPS = 12, 4
+
+
+def action_probe(spec: Spec, rows=50):
+    """(observations, noise) in float32 for a sample_actions call on ``spec``'s state."""
+    rng = np.random.default_rng([spec.seed, 2])
+    return (rng.standard_normal((rows, spec.D)).astype(np.float32),
+            rng.standard_normal((rows, spec.A)).astype(np.float32))
+
+
+def rollout_case():
+    """The env model, initial observations and per-member noise of the trained-like rollout
+    test: as tests/test_gpu_envmodel.py's single-block case (termination logits far below 0,
+    so nothing terminates and whole trajectories compare), with non-trivial LayerNorm."""
+    import envmodel as em
+    spec = em.EnvModelSpec(ROLLOUT_SPECS[0].D, ROLLOUT_SPECS[0].A)
+    sp = em.init_state_predictor(spec, 0)
+    rng = np.random.default_rng(7)
+    for k in sp:
+        if k.startswith("LayerNorm"):
+            sp[k]["scale"] = (1.0 + 0.2 * rng.standard_normal(sp[k]["scale"].shape)).astype(np.float32)
+            sp[k]["bias"] = (0.1 * rng.standard_normal(sp[k]["bias"].shape)).astype(np.float32)
+    tp = em.init_termination_predictor(spec, 1, scale=0.1, bias=-50.0)
+    obs0 = rng.standard_normal((ROLLOUT_ENVS, spec.obs_dim)).astype(np.float32)
+    noise = rng.standard_normal((len(ROLLOUT_SPECS), ROLLOUT_STEPS, ROLLOUT_ENVS, spec.action_dim)).astype(np.float32)
+    return spec, sp, tp, obs0, noise
+
+
+def rollout_raw_actions(member: int):
+    """The one-step actor's outputs before the clamp, [steps][envs][A], along the float64
+    oracle's trajectory of ``rollout_case`` for ROLLOUT_SPECS[member]."""
+    from oracle import envmodel_oracle as EO
+    from oracle import fql_oracle as O
+    _, sp, _, obs0, noise = rollout_case()
+    tm = trained_member(ROLLOUT_SPECS[member])
+    obs, out = obs0.astype(np.float64), []
+    for t in range(ROLLOUT_STEPS):
+        raw = O.sample_actions(tm.cfg, tm.params, obs, noise[member, t].astype(np.float64), clip=False)
+        out.append(raw)
+        obs = EO.state_predictor(sp, obs, np.clip(raw, -1.0, 1.0))
+    return np.stack(out)

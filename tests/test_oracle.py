@@ -78,32 +78,80 @@ def _loss_only(cfg, params, batch, noise):
     return loss
 
 
-@pytest.mark.parametrize("net,key", [
+# (name, config fields, q_offset of trained_like_params or None for init_params).  The
+# trained-like states have non-zero biases, LayerNorm scale != 1 and bias != 0, target !=
+# critic and a good share of saturated actor outputs; "min" keeps Q centred at 0 (mixed
+# signs), where normalize_q_loss's lambda is not 1 / |mean Q| and the min is a real choice.
+STATES = [
+    ("init", {}, None),
+    ("trained", {}, -40.0),
+    ("trained_min", {"q_agg": "min", "normalize_q_loss": True}, 0.0),
+    ("trained_actor_ln", {"actor_layer_norm": True}, -40.0),
+]
+FD_KEYS = [
     ("critic", "Dense_0/kernel"), ("critic", "LayerNorm_1/scale"), ("critic", "Dense_4/bias"),
     ("actor_bc_flow", "Dense_2/kernel"), ("actor_onestep_flow", "Dense_0/kernel"),
     ("actor_onestep_flow", "Dense_4/kernel"),
-])
+]
+FD_KEYS_TRAINED = FD_KEYS + [
+    ("critic", "Dense_2/bias"), ("critic", "LayerNorm_0/bias"), ("actor_bc_flow", "Dense_4/bias"),
+    ("actor_onestep_flow", "Dense_1/bias"),
+]
+FD_KEYS_ACTOR_LN = [("actor_onestep_flow", "LayerNorm_2/scale"), ("actor_bc_flow", "LayerNorm_0/bias")]
+
+
+def _state_params(cfg, seed, q_offset):
+    return O.init_params(cfg, seed) if q_offset is None else O.trained_like_params(cfg, seed, q_offset=q_offset)
+
+
+def _fd_cases():
+    for name, kw, q_offset in STATES[1:]:
+        keys = FD_KEYS_TRAINED + (FD_KEYS_ACTOR_LN if kw.get("actor_layer_norm") else [])
+        for net, key in keys:
+            yield pytest.param(kw, q_offset, net, key, id=f"{name}-{net}-{key}")
+
+
+@pytest.mark.parametrize("net,key", FD_KEYS)
 def test_gradients_match_finite_differences(net, key):
+    _check_finite_differences({}, None, net, key)
+
+
+@pytest.mark.parametrize("kw,q_offset,net,key", list(_fd_cases()))
+def test_gradients_match_finite_differences_trained(kw, q_offset, net, key):
+    _check_finite_differences(kw, q_offset, net, key)
+
+
+def _check_finite_differences(kw, q_offset, net, key):
     # each net's own objective: critic <- critic loss (the actor's Q term reads
     # frozen critic params); bc <- BC loss (the Euler target is stop-gradient);
-    # onestep <- actor loss
-    cfg = small_cfg(alpha=3.0)
+    # onestep <- actor loss, with normalize_q_loss's lambda held (it is a stop-gradient)
+    cfg = small_cfg(alpha=3.0, **kw)
     rng = np.random.default_rng(7)
-    params = O.init_params(cfg, 3)
+    params = _state_params(cfg, 3, q_offset)
     batch, noise = O.make_batch(cfg, 8, rng), O.make_noise(cfg, 8, rng)
-    _, _, grads = O.loss_and_grads(cfg, params, batch, noise)
+    # clip(a_pi) has a kink at +-1, where a central difference is not the gradient: probe on
+    # the rows whose a_pi entries are all at least 1e-3 away from it
+    a_pi = O.sample_actions(cfg, params, batch["observations"], noise["z_d"], clip=False)
+    rows = np.all(np.abs(np.abs(a_pi) - 1.0) >= 1e-3, axis=1)
+    assert rows.sum() >= 6
+    batch = {k: v[rows] for k, v in batch.items()}
+    noise = {k: v[rows] for k, v in noise.items()}
+    if q_offset is not None:  # the state is worth probing: the clip engages and also does not
+        assert 0 < (np.abs(a_pi[rows]) > 1.0).sum() < a_pi[rows].size
+    _, info0, grads = O.loss_and_grads(cfg, params, batch, noise)
+    lam = -info0["actor/q_loss"] / info0["actor/q"]
+    assert cfg.normalize_q_loss or lam == 1.0
     arr = params[net][key]
     flat_idx = rng.choice(arr.size, size=min(6, arr.size), replace=False)
     eps = 1e-6
 
     def objective(pp):
-        if net == "critic":
-            _, info, _ = O.loss_and_grads(cfg, pp, batch, noise, want_grads=False)
-            return info["critic/critic_loss"]
         _, info, _ = O.loss_and_grads(cfg, pp, batch, noise, want_grads=False)
+        if net == "critic":
+            return info["critic/critic_loss"]
         if net == "actor_bc_flow":  # the flow target (distill) is a stop-gradient path
             return info["actor/bc_flow_loss"]
-        return info["actor/actor_loss"]
+        return info["actor/bc_flow_loss"] + cfg.alpha * info["actor/distill_loss"] - lam * info["actor/q"]
 
     for fi in flat_idx:
         idx = np.unravel_index(fi, arr.shape)
@@ -119,12 +167,22 @@ def test_gradients_match_finite_differences(net, key):
 
 
 def test_gradients_match_torch_autograd():
+    _check_torch_autograd(None)
+
+
+@pytest.mark.parametrize("q_offset", [-40.0, 0.0], ids=["q_minus_40", "mixed_sign_q"])
+def test_gradients_match_torch_autograd_trained(q_offset):
+    _check_torch_autograd(q_offset)
+
+
+def _check_torch_autograd(q_offset):
     torch = pytest.importorskip("torch")  # noqa: F841
     from oracle.fql_torch import grads_autograd
-    for kw in ({}, {"q_agg": "min", "normalize_q_loss": True}, {"layer_norm": False, "actor_layer_norm": True}):
+    for kw in ({}, {"q_agg": "min", "normalize_q_loss": True}, {"layer_norm": False, "actor_layer_norm": True},
+               {"actor_layer_norm": True}):
         cfg = small_cfg(**kw)
         rng = np.random.default_rng(11)
-        p = O.init_params(cfg, 2)
+        p = _state_params(cfg, 2, q_offset)
         b, n = O.make_batch(cfg, 8, rng), O.make_noise(cfg, 8, rng)
         loss, info, g = O.loss_and_grads(cfg, p, b, n)
         l2, i2, g2 = grads_autograd(cfg, p, b, n)
@@ -189,3 +247,138 @@ def test_oracle_reproduces_golden_fixture():
         if key.startswith("params_out/"):
             _, net, leaf = key.split("/", 2)
             assert np.array_equal(p[net][leaf].astype(np.float32), g[key])
+
+
+# ---------------------------------------------------------------------------
+# the trained-like state: what it can see that the initial state cannot
+# ---------------------------------------------------------------------------
+def _edit(params, fn):
+    """A copy of ``params`` with fn(net, leaf name, array) -> array applied to every leaf."""
+    return {net: {k: fn(net, k, v.copy()) for k, v in p.items()} for net, p in params.items()}
+
+
+def _zero_dense_bias(nets):
+    return lambda net, k, v: v * 0.0 if net in nets and k.startswith("Dense_") and k.endswith("/bias") else v
+
+
+# name -> (edit of the parameters or None, _mutant keyword of O.update or None, Adam reset)
+KERNEL_MISTAKES = {
+    "critic Dense biases dropped": (_zero_dense_bias(("critic",)), None, False),
+    "target critic Dense biases dropped": (_zero_dense_bias(("target_critic",)), None, False),
+    "BC flow actor Dense biases dropped": (_zero_dense_bias(("actor_bc_flow",)), None, False),
+    "one-step actor Dense biases dropped": (_zero_dense_bias(("actor_onestep_flow",)), None, False),
+    "ensemble member 1 reads member 0's Dense biases": (
+        lambda net, k, v: np.stack([v[0]] * len(v)) if net in ("critic", "target_critic") and k.startswith("Dense_")
+        and k.endswith("/bias") else v, None, False),
+    "LayerNorm scale taken as 1": (lambda net, k, v: v * 0.0 + 1.0 if k.endswith("/scale") else v, None, False),
+    "LayerNorm bias taken as 0": (
+        lambda net, k, v: v * 0.0 if k.startswith("LayerNorm") and k.endswith("/bias") else v, None, False),
+    "TD target from the online critic": (None, "target_is_critic", False),
+    "Q gradient through a saturated clip(a_pi)": (None, "inside_all_true", False),
+    "Euler result not clipped": (None, "euler_unclipped", False),
+    "a_next not clipped": (None, "a_next_unclipped", False),
+    "metric actions not clipped": (None, "metric_unclipped", False),
+    "Adam restarted from m = v = 0, count = 0": (None, None, True),
+}
+# What the initial state, at its first step, cannot see (this test documents it).  It does see
+# a missing Euler clip -- the flow starts from N(0, 1) noise, a third of which is outside
+# [-1, 1], and hardly moves it -- and nothing else in the list.
+BLIND_AT_INIT = set(KERNEL_MISTAKES) - {"Euler result not clipped"}
+
+
+def _moved(cfg, right, wrong):
+    """The checked quantities that differ between two oracle updates by at least 10x the bound
+    the GPU tests hold them to: info values (REL, with its floor), and each leaf's new Adam
+    m and v (MOMENT_REL of the leaf's scale)."""
+    from _helpers import MOMENT_REL, REL
+    (_, opt_r, info_r), (_, opt_w, info_w) = right, wrong
+    out = []
+    for k in O.TRAIN_INFO_KEYS:
+        a, b = float(info_r[k]), float(info_w[k])
+        if abs(a - b) >= 10 * (REL * max(abs(a), abs(b)) + 1e-6):
+            out.append(k)
+    for what in ("m", "v"):
+        for net in O.TRAINABLE:
+            for k, a in opt_r[what][net].items():
+                if np.abs(a - opt_w[what][net][k]).max() >= 10 * MOMENT_REL * np.abs(a).max() > 0:
+                    out.append(f"{net}/{k} adam {what}")
+    return out
+
+
+def _with_mistake(cfg, params, opt, batch, noise, mistake):
+    edit, mutant, reset = KERNEL_MISTAKES[mistake]
+    if edit is not None:
+        params = _edit(params, edit)
+    if mutant == "target_is_critic":
+        params = dict(params, target_critic=params["critic"])
+        mutant = None
+    if reset:
+        opt = O.init_opt_state(params)
+    return O.update(cfg, params, opt, batch, noise, _mutant=mutant)
+
+
+@pytest.mark.parametrize("mistake", list(KERNEL_MISTAKES))
+@pytest.mark.parametrize("variant", ["q_minus_40", "min_mixed_sign_q"])
+def test_trained_like_state_separates_kernel_mistakes(variant, mistake):
+    """Each way a kernel could be wrong that the initial state hides -- an update computed
+    with that mistake equals the correct one there -- moves, from the trained-like state the
+    GPU parity tests start at, at least one quantity those tests check by 10x its bound."""
+    from _helpers import TRAINED, trained_member
+    tm = trained_member(TRAINED["h64" if variant == "q_minus_40" else "h64_min"][0])
+    cfg, b, n = tm.cfg, tm.batches[0], tm.noises[0]
+    moved = _moved(cfg, tm.steps[0], _with_mistake(cfg, tm.params, tm.opt, b, n, mistake))
+    assert moved, f"{mistake}: nothing moves at the trained-like state"
+    print(f"{mistake}: moves {moved[:6]}{' ...' if len(moved) > 6 else ''}")
+    # the same mistake from init_params (first step, zero moments), same batch and noise
+    p0 = O.init_params(cfg, tm.spec.seed)
+    o0 = O.init_opt_state(p0)
+    moved0 = _moved(cfg, O.update(cfg, p0, o0, b, n), _with_mistake(cfg, p0, o0, b, n, mistake))
+    if mistake in BLIND_AT_INIT:
+        assert not moved0, f"{mistake}: the initial state sees it too ({moved0[:6]})"
+    else:
+        assert moved0
+
+
+def _trained_specs():
+    from _helpers import ALL_TRAINED_SPECS
+    return ALL_TRAINED_SPECS
+
+
+@pytest.mark.parametrize("spec", _trained_specs(), ids=lambda s: f"h{s.H}-b{s.B}-d{s.D}-seed{s.seed}-a{s.alpha:g}"
+                         + ("-min" if s.q_offset == 0 else "") + ("-sampled" if s.sampled else ""))
+def test_trained_like_state_conditions(spec):
+    """Conditions on every state tests/test_gpu_parity_trained.py starts from, in float64: at
+    each clamp (a_pi, the Euler result, a_next, the metric actions) 15-85 % of the entries
+    are outside [-1, 1] and none within 1e-4 of +-1, at every step the test takes; with
+    q_agg = min each ensemble member is the minimum in at least 15 % of the rows; and the
+    state is trained-like (target != critic in every leaf, moments non-zero except the
+    target's)."""
+    from _helpers import check_member_conditions, trained_member
+    tm = trained_member(spec)
+    check_member_conditions(tm)
+    for k, v in tm.params["critic"].items():
+        d = np.abs(tm.params["target_critic"][k] - v)
+        assert (d > 0).mean() > 0.99 and d.mean() >= 0.1 * np.abs(v - (spec.q_offset if k == "Dense_4/bias" else 0)).mean(), k
+    for net in O.TRAINABLE:
+        for k, m in tm.opt["m"][net].items():
+            assert m.all() and (tm.opt["v"][net][k] > 0).all(), (net, k)
+            assert m.size < 16 or ((m > 0).any() and (m < 0).any()), (net, k)
+    assert not any(np.any(x) for w in ("m", "v") for x in tm.opt[w]["target_critic"].values())
+    assert tm.opt["count"] == 1000
+    if spec.q_offset == 0:   # mixed-sign Q: normalize_q_loss's lambda is not 1 / |mean Q|
+        info = tm.steps[0][2]
+        assert abs(info["actor/q_loss"]) < 0.99
+
+
+def test_trained_like_action_and_rollout_conditions():
+    """The same clamp conditions for what the sample_actions and rollout GPU tests feed the
+    one-step actor's head."""
+    from _helpers import (ACTION_SPECS, ROLLOUT_SPECS, action_probe, check_clamp_conditions, rollout_raw_actions,
+                          trained_member)
+    for spec in ACTION_SPECS:
+        tm = trained_member(spec)
+        obs, z = action_probe(spec)
+        raw = O.sample_actions(tm.cfg, tm.params, obs.astype(np.float64), z.astype(np.float64), clip=False)
+        check_clamp_conditions(raw, f"sample_actions {spec}")
+    for i, spec in enumerate(ROLLOUT_SPECS):
+        check_clamp_conditions(rollout_raw_actions(i), f"rollout {spec}")
