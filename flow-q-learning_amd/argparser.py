@@ -8,7 +8,7 @@ import argparse
 from ast import literal_eval
 from pathlib import Path
 
-from trainer.config import AgentConfig, TrainerConfig
+from trainer.config import AgentConfig, ModelRolloutConfig, TrainerConfig
 
 
 def get_argparser() -> argparse.ArgumentParser:
@@ -43,6 +43,14 @@ def get_argparser() -> argparse.ArgumentParser:
     p.add_argument("--agent.encoder", type=str, default=None)
     p.add_argument("--single_experiment", action="store_true")
     p.add_argument("--job_id", type=int, default=0)
+    # training on world-model branches (trainer.config.ModelRolloutConfig; no reference
+    # counterpart): off while --model_rollout_branches is 0
+    p.add_argument("--model_rollout_branches", type=int, default=0)
+    p.add_argument("--model_rollout_horizon", type=int, default=5)
+    p.add_argument("--model_rollout_interval", type=int, default=1000)
+    p.add_argument("--model_rollout_warmup", type=int, default=0)
+    p.add_argument("--model_real_ratio", type=float, default=0.5)
+    p.add_argument("--model_buffer_rows", type=int, default=100_000)
     return p
 
 
@@ -61,6 +69,19 @@ def build_config_from_args(args: argparse.Namespace) -> TrainerConfig:
     agent = AgentConfig(**{k: v for k, v in agent_kw.items() if k in AgentConfig.__dataclass_fields__})
     return TrainerConfig(**{k: v for k, v in trainer_kw.items() if k in TrainerConfig.__dataclass_fields__},
                          agent=agent)
+
+
+def build_model_rollout_config_from_args(args: argparse.Namespace) -> ModelRolloutConfig:
+    """The --model_rollout_* / --model_real_ratio / --model_buffer_rows flags (a namespace
+    without them: the inert defaults)."""
+    d = ModelRolloutConfig()
+    return ModelRolloutConfig(
+        branches=getattr(args, "model_rollout_branches", d.branches),
+        horizon=getattr(args, "model_rollout_horizon", d.horizon),
+        interval=getattr(args, "model_rollout_interval", d.interval),
+        warmup=getattr(args, "model_rollout_warmup", d.warmup),
+        real_ratio=getattr(args, "model_real_ratio", d.real_ratio),
+        buffer_rows=getattr(args, "model_buffer_rows", d.buffer_rows))
 
 
 def get_env_model_argparser() -> argparse.ArgumentParser:

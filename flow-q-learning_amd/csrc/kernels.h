@@ -351,7 +351,52 @@ struct SampleArgs {
     int nz;
     const int* slots;
 };
-void launch_sample(const SampleArgs& a, hipStream_t s);
+// The per-member synthetic-transition rings (fqlpop_synth_create): the dataset's five
+// row-major fields per slot, `cap` rows each, and the device-resident counters.
+constexpr int SYNTH_CTR = 4;   // counters per slot: rows, head, appended, (unused)
+struct SynthRing {
+    float *obs, *act, *rew, *mask, *nobs;   // slot s at + s * cap * {D, A, 1, 1, D}
+    long long cap;
+    long long* ctr;               // [slots][SYNTH_CTR]
+    const float* ratio;           // [1]: real_ratio rho
+};
+// ring == null: sample_kernel, the production launch (it reads none of the ring's state).
+// Else the mixed training draw (sample_ring_kernel): with u = (w2 >> 8) * 2^-24 of the row's
+// Philox block, the row is the offline row (w0 * n_rows) >> 32 if u < rho or the slot's ring
+// is empty, else position (w0 * rows) >> 32 of the slot's ring.  Dataset draws only.
+void launch_sample(const SampleArgs& a, hipStream_t s, const SynthRing* ring = nullptr);
+
+// ---------------------------------------------- synthetic-transition rings --
+// fqlpop_synth_collect, between launch_rollout (record mode, device buffers) and the step:
+//   launch_synth_starts  init_obs[e] = obs[idx[e]], idx = start_rows (device-visible), or,
+//                        start_rows null, (w0 * n_rows) >> 32 with w0 the first word of
+//                        Philox4x32-10 at counter (e, 0, 0x5E13, 0) under the call seed;
+//   launch_synth_append  the valid transitions (t < length of env e) of every active member
+//                        in (t, e) order to positions (head + i) mod cap of its ring; reads
+//                        head, writes no counter;
+//   launch_synth_commit  head, rows, appended of every active member advanced by its count.
+struct SynthCollectArgs {
+    SynthRing ring;
+    int D, A;
+    int n_envs, max_steps;        // branches, horizon
+    const float* out;             // rollout results [nz][n_envs][2]: success, length
+    const float* out_obs;         // [nz][n_envs][D]
+    const float* traj_obs;        // [nz][max_steps][n_envs][D]
+    const float* traj_act;        // [nz][max_steps][n_envs][A]
+    int nz;
+    const int* slots;
+};
+void launch_synth_starts(const float* obs, long long n_rows, int D, const long long* start_rows, uint64_t seed,
+                         int n_envs, float* init_obs, hipStream_t s);
+void launch_synth_append(const SynthCollectArgs& a, hipStream_t s);
+void launch_synth_commit(const SynthCollectArgs& a, hipStream_t s);
+// fqlpop_clone_members: the valid rows and the counters of src[p]'s ring into dst[p]'s.
+struct SynthCloneArgs {
+    SynthRing ring;
+    int D, A, n_pairs;
+    int src[16], dst[16];         // CLONE_MAX_PAIRS
+};
+void launch_synth_clone(const SynthCloneArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- loss ----
 struct LossArgs {

@@ -3417,8 +3417,12 @@ DEV void philox_normals(float* n, int cnt, uint64_t seed, uint32_t row, uint32_t
 // t (Philox word 0), then part p writes the features k = p mod SP, the Philox
 // normal pairs q = p mod SP and action j = p.  Values are identical to a
 // one-thread-per-row draw (same counters).
+// RING (sample_ring_kernel): the mixed draw of a population with synthetic-transition
+// rings (SynthRing, kernels.h); sample_kernel is the RING = false instantiation and reads
+// nothing of the ring.
 constexpr int SP = 8;
-__global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
+template <bool RING>
+DEV void sample_body(const SampleArgs& a, const SynthRing& rg) {
     constexpr int RPB = 256 / SP;  // rows per block
     const int nbb = (a.B + RPB - 1) / RPB;
     const int bb = blockIdx.x % nbb, z = blockIdx.x / nbb;
@@ -3447,13 +3451,28 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
         rew = pb[(long long)B * (D + A) + b];
         mask = pb[(long long)B * (D + A + 1) + b];
         nobs = pb + (long long)B * (D + A + 2) + (long long)b * D;
-    } else {
+    } else if constexpr (!RING) {
         const long long idx = (long long)(((unsigned long long)c0[0] * (unsigned long long)a.n_rows) >> 32);
         actp = a.act + idx * A;
         obs = a.obs + idx * D;
         nobs = a.nobs + idx * D;
         rew = a.rew[idx];
         mask = a.mask[idx];
+    } else {
+        long long idx = (long long)(((unsigned long long)c0[0] * (unsigned long long)a.n_rows) >> 32);
+        const float *dobs = a.obs, *dact = a.act, *drew = a.rew, *dmask = a.mask, *dnobs = a.nobs;
+        const long long rows = rg.ctr[(long long)slot * SYNTH_CTR];
+        if (!(u01(c0[2]) < *rg.ratio) && rows > 0) {  // a ring row, in physical ring order
+            idx = (long long)(((unsigned long long)c0[0] * (unsigned long long)rows) >> 32);
+            const long long so = (long long)slot * rg.cap;
+            dobs = rg.obs + so * D; dact = rg.act + so * A; drew = rg.rew + so; dmask = rg.mask + so;
+            dnobs = rg.nobs + so * D;
+        }
+        actp = dact + idx * A;
+        obs = dobs + idx * D;
+        nobs = dnobs + idx * D;
+        rew = drew[idx];
+        mask = dmask[idx];
     }
     const float* pn = a.inj_noise ? a.inj_noise + z * (long long)B * (4 * A + 1) : nullptr;
     const float t = pn ? pn[(long long)B * 2 * A + b] : u01(c0[1]);
@@ -3536,9 +3555,16 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
     }
 }
 
-void launch_sample(const SampleArgs& a, hipStream_t s) {
+__global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) { sample_body<false>(a, SynthRing{}); }
+__global__ __launch_bounds__(256) void sample_ring_kernel(const SampleArgs a, const SynthRing rg) {
+    sample_body<true>(a, rg);
+}
+
+void launch_sample(const SampleArgs& a, hipStream_t s, const SynthRing* ring) {
     const int rpb = 256 / SP;
-    hipLaunchKernelGGL(sample_kernel, dim3(((a.B + rpb - 1) / rpb) * a.nz), dim3(256), 0, s, a);
+    const dim3 grid(((a.B + rpb - 1) / rpb) * a.nz);
+    if (ring) hipLaunchKernelGGL(sample_ring_kernel, grid, dim3(256), 0, s, a, *ring);
+    else hipLaunchKernelGGL(sample_kernel, grid, dim3(256), 0, s, a);
 }
 
 // =============================================================== losses ====
@@ -4183,6 +4209,164 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_kernel(const RolloutArg
 void launch_rollout(const RolloutArgs& a, hipStream_t s) {
     const dim3 grid(((a.n_envs + EF_NC - 1) / EF_NC) * a.nz);
     hipLaunchKernelGGL(rollout_kernel, grid, dim3(EF_NW * 64), 0, s, a);
+}
+
+// ============================================ synthetic-transition rings ==
+// (SynthCollectArgs, kernels.h)  fqlpop_synth_collect around rollout_kernel's record mode.
+__global__ __launch_bounds__(256) void synth_starts_kernel(const float* obs, long long n_rows, int D,
+                                                           const long long* start_rows, uint64_t seed, int n_envs,
+                                                           float* init_obs) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n_envs * D) return;
+    const int e = (int)(i / D), k = (int)(i % D);
+    long long idx;
+    if (start_rows) {
+        idx = start_rows[e];
+    } else {
+        uint32_t c[4] = {(uint32_t)e, 0u, 0x5E13u, 0u};
+        philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        idx = (long long)(((unsigned long long)c[0] * (unsigned long long)n_rows) >> 32);
+    }
+    init_obs[i] = obs[idx * D + k];
+}
+
+void launch_synth_starts(const float* obs, long long n_rows, int D, const long long* start_rows, uint64_t seed,
+                         int n_envs, float* init_obs, hipStream_t s) {
+    const long long n = (long long)n_envs * D;
+    hipLaunchKernelGGL(synth_starts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, obs, n_rows, D,
+                       start_rows, seed, n_envs, init_obs);
+}
+
+// Block (env tile of 256, step t, member z).  A transition (t, e) is valid iff t < len_e; its
+// index in the call's (t, e) order is
+//   sum_e' min(len_e', t)          the valid transitions of the steps before t
+//   + #{e' < e : len_e' > t}       those of step t before env e,
+// the second term split into the envs before the tile (summed with the first in one pass over
+// the lengths) and a ballot / popcount rank inside the tile.  No atomics: the position
+// depends on the lengths alone.  Reads head, which synth_commit_kernel advances afterwards.
+__global__ __launch_bounds__(256) void synth_append_kernel(const SynthCollectArgs a) {
+    __shared__ int red[256];
+    __shared__ int wtot[4];
+    __shared__ long long pos_s[256];
+    __shared__ unsigned char last_s[256];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int e0 = blockIdx.x * 256, t = blockIdx.y, z = blockIdx.z;
+    const int slot = a.slots[z];
+    const int D = a.D, A = a.A, NE = a.n_envs, T = a.max_steps;
+    const float* out = a.out + (long long)z * NE * 2;
+    int part = 0;
+    for (int e = tid; e < NE; e += 256) {
+        const int len = (int)out[2 * e + 1];
+        part += min(len, t) + ((e < e0 && len > t) ? 1 : 0);
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const int base = red[0];
+    const int e = e0 + tid;
+    const int len = e < NE ? (int)out[2 * e + 1] : 0;
+    const bool valid = len > t;
+    const unsigned long long bal = __ballot(valid);
+    if (lane == 0) wtot[wv] = __popcll(bal);
+    __syncthreads();
+    int rank = __popcll(bal & ((1ull << lane) - 1ull));
+    for (int q = 0; q < wv; ++q) rank += wtot[q];
+    const long long cap = a.ring.cap, so = (long long)slot * cap;
+    const long long head = a.ring.ctr[(long long)slot * SYNTH_CTR + 1];
+    const bool last = t + 1 >= len;  // the env's last step: s' is the rollout's out_obs
+    long long pos = -1;
+    if (valid) {
+        pos = (head + base + rank) % cap;
+        // terminated there (logit > 0: success) -> r = 0, m = 0; a truncation at the horizon is no terminal
+        const bool term = last && out[2 * e] > 0.5f;
+        a.ring.rew[so + pos] = term ? 0.0f : -1.0f;
+        a.ring.mask[so + pos] = term ? 0.0f : 1.0f;
+    }
+    pos_s[tid] = pos;
+    last_s[tid] = last ? 1 : 0;
+    __syncthreads();
+    const long long row_t = ((long long)z * T + t) * NE + e0;  // traj row of (t, e0)
+    for (int i = tid; i < 256 * D; i += 256) {
+        const int c = i / D, k = i % D;
+        const long long p = pos_s[c];
+        if (p < 0) continue;
+        a.ring.obs[(so + p) * D + k] = a.traj_obs[(row_t + c) * D + k];
+        a.ring.nobs[(so + p) * D + k] = last_s[c] ? a.out_obs[((long long)z * NE + e0 + c) * D + k]
+                                                  : a.traj_obs[(row_t + NE + c) * D + k];
+    }
+    for (int i = tid; i < 256 * A; i += 256) {
+        const int c = i / A, k = i % A;
+        const long long p = pos_s[c];
+        if (p < 0) continue;
+        a.ring.act[(so + p) * A + k] = a.traj_act[(row_t + c) * A + k];
+    }
+}
+
+void launch_synth_append(const SynthCollectArgs& a, hipStream_t s) {
+    if (a.nz == 0) return;
+    const dim3 grid((a.n_envs + 255) / 256, a.max_steps, a.nz);
+    hipLaunchKernelGGL(synth_append_kernel, grid, dim3(256), 0, s, a);
+}
+
+// One block per active member: count = sum of the episode lengths; the only writer of the
+// member's counters in a collect.
+__global__ __launch_bounds__(256) void synth_commit_kernel(const SynthCollectArgs a) {
+    __shared__ int red[256];
+    const int tid = threadIdx.x, z = blockIdx.x, slot = a.slots[z];
+    const float* out = a.out + (long long)z * a.n_envs * 2;
+    int part = 0;
+    for (int e = tid; e < a.n_envs; e += 256) part += (int)out[2 * e + 1];
+    red[tid] = part;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        long long* c = a.ring.ctr + (long long)slot * SYNTH_CTR;
+        const long long n = red[0], rows = c[0] + n;
+        c[0] = rows < a.ring.cap ? rows : a.ring.cap;
+        c[1] = (c[1] + n) % a.ring.cap;
+        c[2] += n;
+    }
+}
+
+void launch_synth_commit(const SynthCollectArgs& a, hipStream_t s) {
+    if (a.nz == 0) return;
+    hipLaunchKernelGGL(synth_commit_kernel, dim3(a.nz), dim3(256), 0, s, a);
+}
+
+// Block (chunk, pair): the first rows[src] positions of every field, then (chunk 0) the
+// counters.  dst is never a src of the same call (fqlpop_clone_members), so no block reads
+// counters that another writes.
+__global__ __launch_bounds__(256) void synth_clone_kernel(const SynthCloneArgs a) {
+    const int p = blockIdx.y;
+    const long long cap = a.ring.cap, so = a.src[p] * cap, dn = a.dst[p] * cap;
+    const long long rows = a.ring.ctr[(long long)a.src[p] * SYNTH_CTR];
+    const long long step = (long long)gridDim.x * 256, i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    auto copy = [&](float* f, long long w) {
+        const float* __restrict__ s = f + so * w;
+        float* __restrict__ d = f + dn * w;
+        for (long long i = i0; i < rows * w; i += step) d[i] = s[i];
+    };
+    copy(a.ring.obs, a.D);
+    copy(a.ring.nobs, a.D);
+    copy(a.ring.act, a.A);
+    copy(a.ring.rew, 1);
+    copy(a.ring.mask, 1);
+    if (blockIdx.x == 0 && threadIdx.x < SYNTH_CTR)
+        a.ring.ctr[(long long)a.dst[p] * SYNTH_CTR + threadIdx.x] = a.ring.ctr[(long long)a.src[p] * SYNTH_CTR + threadIdx.x];
+}
+
+void launch_synth_clone(const SynthCloneArgs& a, hipStream_t s) {
+    if (a.n_pairs <= 0) return;
+    long long chunks = (a.ring.cap * a.D + 255) / 256;
+    if (chunks > 2048 / a.n_pairs) chunks = 2048 / a.n_pairs;
+    if (chunks < 1) chunks = 1;
+    hipLaunchKernelGGL(synth_clone_kernel, dim3((unsigned)chunks, (unsigned)a.n_pairs), dim3(256), 0, s, a);
 }
 
 // ====================================================== ensemble rollout ==

@@ -348,6 +348,20 @@ struct fqlpop {
     RolloutArgs ens_args{};                       // the shared leaf layout
     int ens_n = 0;
     double ens_kernel_us = -1.0;   // rollout_ens_kernel's time in the last fqlpop_rollout_ensemble (HIP events)
+    // synthetic-transition rings (fqlpop_synth_create; synth.obs null: none) and what a
+    // collect needs between its launches: one workspace (start observations, the rollout's
+    // out / out_obs / traces for all slots), grown on first use, and a few pinned buffers the
+    // start rows of the collects in flight are read from
+    SynthRing synth{};
+    float* synth_ratio = nullptr;
+    float* synth_ws = nullptr;
+    long long synth_ws_floats = 0;
+    static constexpr int kSynthStage = 4;
+    long long* synth_start_host[kSynthStage] = {};
+    hipEvent_t synth_start_ev[kSynthStage] = {};
+    bool synth_start_used[kSynthStage] = {};
+    long long synth_start_cap = 0;
+    int synth_start_next = 0;
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
@@ -1369,7 +1383,10 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
             launch_head_fwd(HEAD_OS, ha, sM);
         }
     };
-    launch_sample(sa, sM);
+    // the training draw of a population with rings mixes ring rows in (rows and rho are read
+    // from device memory: a captured step sees a later collect or ratio)
+    const bool ring = train && !inj_batch && h->synth.obs != nullptr;
+    launch_sample(sa, sM, ring ? &h->synth : nullptr);
     HIPCHK(hipEventRecord(h->ev_sample, sM));
     if (sF != sM) HIPCHK(hipStreamWaitEvent(sF, h->ev_sample, 0));
     if (sB != sM) HIPCHK(hipStreamWaitEvent(sB, h->ev_sample, 0));
@@ -2099,6 +2116,13 @@ int fqlpop_destroy(fqlpop_t* h) {
             if (st.gen) (void)hipFree(st.gen);
         }
         if (h->euler_pre0) (void)hipFree(h->euler_pre0);
+        for (void* p : {(void*)h->synth.obs, (void*)h->synth.act, (void*)h->synth.rew, (void*)h->synth.mask,
+                        (void*)h->synth.nobs, (void*)h->synth.ctr, (void*)h->synth_ratio, (void*)h->synth_ws})
+            if (p) (void)hipFree(p);
+        for (int i = 0; i < fqlpop::kSynthStage; ++i) {
+            if (h->synth_start_host[i]) (void)hipHostFree(h->synth_start_host[i]);
+            if (h->synth_start_ev[i]) (void)hipEventDestroy(h->synth_start_ev[i]);
+        }
         if (h->split_err_host) (void)hipHostFree(h->split_err_host);
         for (hipEvent_t e : {h->ev_sample, h->ev_bcfwd, h->ev_bcloss, h->ev_flow, h->ev_bdone, h->ev_t0, h->ev_t1})
             if (e) (void)hipEventDestroy(e);
@@ -2423,13 +2447,16 @@ int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int r
         if (reinit) {
             (void)absorb_split_error(h);
             init_member(h, member, seed);
+            if (h->synth.ctr)  // a fresh member has collected nothing
+                HIPCHK(hipMemset(h->synth.ctr + (long long)member * SYNTH_CTR, 0, sizeof(long long) * SYNTH_CTR));
             h->poisoned[member] = 0;  // a fresh member: nothing a failed launch wrote is left
         }
     });
 }
 
 // Per-slot buffers of struct fqlpop and what the clone does with them:
-//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count;
+//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count; the member's
+//            synthetic-transition ring and its counters (synth, when created: its own launch);
 //   written  alpha, seeds, skeys (the values given for dst), h_alpha / h_seeds;
 //   scratch  grads, stats, the network inputs (os_in .. tg_in, cr_in_buf), every Net's U / G /
 //            MU / RS / DU / DH / C1 / C2 / part, q .. dout_os, inj_batch / inj_noise: a step
@@ -2490,6 +2517,12 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
                 a.skeys[i] = sample_key(seeds[p0 + i], alphas[p0 + i]);
             }
             launch_clone(a, h->sM);
+            if (h->synth.obs) {  // the ring is part of what dst's next step reads
+                SynthCloneArgs sc{};
+                sc.ring = h->synth; sc.D = h->D; sc.A = h->A; sc.n_pairs = a.n_pairs;
+                for (int i = 0; i < a.n_pairs; ++i) { sc.src[i] = a.src[i]; sc.dst[i] = a.dst[i]; }
+                launch_synth_clone(sc, h->sM);
+            }
         }
         HIPCHK(hipGetLastError());
         for (int i = 0; i < n_pairs; ++i) {
@@ -2729,27 +2762,39 @@ int fqlpop_set_env_model(fqlpop_t* h, const fqlpop_envmodel_config* cfg, const f
 }
 
 namespace {
+// What every rollout of the active members under fqlpop_set_env_model's model needs
+// (fqlpop_rollout, _rollout_record, fqlpop_synth_collect).
+void rollout_check(fqlpop_t* h) {
+    if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
+    if (!rollout_supported(h->H, h->L, h->D, h->A))
+        throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+    if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+}
+// The launch arguments of such a rollout but for its buffers (init_obs, noise and the
+// outputs: device pointers the caller sets): the current parameters, the env model, the
+// active members.
+RolloutArgs rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed) {
+    RolloutArgs r = h->em_args;
+    r.params = h->params; r.P = h->P; r.os_off = h->os.off;
+    for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
+    r.D = h->D; r.A = h->A; r.L = h->L;
+    r.sp = h->sp_params; r.tp = h->tp_params;
+    r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
+    r.nz = h->nz; r.slots = h->slots;
+    return r;
+}
 // fqlpop_rollout / fqlpop_rollout_record (the latter with both trace outputs)
 void rollout_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise,
                  float* out, float* out_obs, float* out_traj_obs, float* out_traj_act) {
     {
         ARGCHK(h && init_obs && out, "null argument");
         ARGCHK(n_envs > 0 && max_steps > 0, "n_envs and max_steps must be positive");
-        if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
-        if (!rollout_supported(h->H, h->L, h->D, h->A))
-            throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
-        if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+        rollout_check(h);
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->sM));
         const int nz = h->nz, D = h->D, A = h->A;
         if (nz == 0) return;
-        RolloutArgs r = h->em_args;
-        r.params = h->params; r.P = h->P; r.os_off = h->os.off;
-        for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
-        r.D = D; r.A = A; r.L = h->L;
-        r.sp = h->sp_params; r.tp = h->tp_params;
-        r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
-        r.nz = nz; r.slots = h->slots;
+        RolloutArgs r = rollout_args(h, n_envs, max_steps, seed);
         float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_tobs = nullptr,
               *d_tact = nullptr;
         const size_t n_traj = (size_t)nz * max_steps * n_envs;
@@ -2795,6 +2840,197 @@ int fqlpop_rollout_record(fqlpop_t* h, const float* init_obs, int n_envs, int ma
     return guard([&] {
         ARGCHK(out_traj_obs && out_traj_act, "null argument");
         rollout_run(h, init_obs, n_envs, max_steps, seed, noise, out, out_obs, out_traj_obs, out_traj_act);
+    });
+}
+
+// ------------------------------------------------- synthetic-transition rings
+namespace {
+void need_rings(fqlpop_t* h) {
+    ARGCHK(h != nullptr, "null handle");
+    if (!h->synth.obs) throw FqErr{FQLPOP_E_STATE, "no synthetic-transition rings (fqlpop_synth_create)"};
+}
+// floats per ring row over the five fields
+long long synth_row_floats(const fqlpop* h) { return 2LL * h->D + h->A + 2; }
+void drop_graphs(fqlpop* h) {
+    for (auto& kv : h->graphs)
+        if (kv.second.exec) { HIPCHK(hipGraphExecDestroy(kv.second.exec)); kv.second.exec = nullptr; }
+}
+}  // namespace
+
+int fqlpop_synth_create(fqlpop_t* h, int64_t capacity_rows) {
+    return guard([&] {
+        ARGCHK(h != nullptr, "null handle");
+        ARGCHK(capacity_rows >= 1 && capacity_rows < (1LL << 32), "capacity_rows must be in 1..2^32-1");
+        if (h->synth.obs) throw FqErr{FQLPOP_E_STATE, "the synthetic-transition rings exist already"};
+        HIPCHK(hipSetDevice(h->device));
+        sync_all_streams(h);
+        const long long cap = capacity_rows, n = h->n;
+        const unsigned long long bytes = sizeof(float) * (unsigned long long)n * cap * synth_row_floats(h);
+        SynthRing r{};
+        r.cap = cap;
+        float** fields[5] = {&r.obs, &r.act, &r.rew, &r.mask, &r.nobs};
+        const long long width[5] = {h->D, h->A, 1, 1, h->D};
+        bool ok = true;
+        for (int i = 0; i < 5 && ok; ++i) ok = hipMalloc(fields[i], sizeof(float) * n * cap * width[i]) == hipSuccess;
+        ok = ok && hipMalloc(&r.ctr, sizeof(long long) * SYNTH_CTR * n) == hipSuccess;
+        if (ok && !h->synth_ratio) ok = hipMalloc(&h->synth_ratio, sizeof(float)) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (float** f : fields)
+                if (*f) (void)hipFree(*f);
+            if (r.ctr) (void)hipFree(r.ctr);
+            throw FqErr{FQLPOP_E_HIP, "synthetic-transition rings: allocating " + std::to_string(bytes) + " bytes (" +
+                                          std::to_string(n) + " members x " + std::to_string(cap) + " rows) failed"};
+        }
+        r.ratio = h->synth_ratio;
+        const float one = 1.0f;
+        HIPCHK(hipMemset(r.ctr, 0, sizeof(long long) * SYNTH_CTR * n));
+        HIPCHK(hipMemcpy(h->synth_ratio, &one, sizeof(float), hipMemcpyHostToDevice));
+        h->synth = r;
+        drop_graphs(h);  // a captured training step has the ring-less sampler baked in
+    });
+}
+
+int fqlpop_synth_set_ratio(fqlpop_t* h, float real_ratio) {
+    return guard([&] {
+        need_rings(h);
+        ARGCHK(real_ratio >= 0.0f && real_ratio <= 1.0f, "real_ratio must be in [0, 1]");
+        HIPCHK(hipSetDevice(h->device));
+        uint32_t bits;
+        std::memcpy(&bits, &real_ratio, sizeof(bits));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->synth_ratio, (int)bits, 1, h->sM));
+    });
+}
+
+int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows) {
+    return guard([&] {
+        need_rings(h);
+        if (h->ds[0].rows == 0) throw FqErr{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
+        rollout_check(h);
+        ARGCHK(n_branches >= 1 && horizon >= 1, "n_branches and horizon must be positive");
+        ARGCHK((long long)n_branches * horizon <= h->synth.cap, "n_branches * horizon exceeds the ring capacity");
+        // the append's grid has a step axis, and its prefix counts are 32-bit
+        ARGCHK(horizon <= 65535 && (long long)n_branches * horizon < (1LL << 31),
+               "horizon or n_branches * horizon too large");
+        if (start_rows)
+            for (int e = 0; e < n_branches; ++e)
+                ARGCHK(start_rows[e] >= 0 && start_rows[e] < h->ds[0].rows, "a start row is out of range");
+        if (h->nz == 0) return;
+        HIPCHK(hipSetDevice(h->device));
+        const long long nb = n_branches, T = horizon, n = h->n, D = h->D, A = h->A;
+        const long long need = nb * D + n * nb * (2 + D) + n * T * nb * (D + A);
+        if (need > h->synth_ws_floats) {  // grown on first use (the earlier collects read the old one)
+            HIPCHK(hipStreamSynchronize(h->sM));
+            if (h->synth_ws) (void)hipFree(h->synth_ws);
+            h->synth_ws = nullptr;
+            h->synth_ws_floats = 0;
+            if (hipMalloc(&h->synth_ws, sizeof(float) * need) != hipSuccess) {
+                (void)hipGetLastError();
+                throw FqErr{FQLPOP_E_HIP, "collect workspace: allocating " + std::to_string(sizeof(float) * need) +
+                                              " bytes failed"};
+            }
+            h->synth_ws_floats = need;
+        }
+        const long long* d_start = nullptr;
+        int stage = -1;
+        if (start_rows) {
+            if (nb > h->synth_start_cap) {
+                HIPCHK(hipStreamSynchronize(h->sM));
+                for (int i = 0; i < fqlpop::kSynthStage; ++i) {
+                    if (h->synth_start_host[i]) (void)hipHostFree(h->synth_start_host[i]);
+                    h->synth_start_host[i] = nullptr;
+                    h->synth_start_used[i] = false;
+                }
+                h->synth_start_cap = 0;
+                for (int i = 0; i < fqlpop::kSynthStage; ++i) {
+                    HIPCHK(hipHostMalloc((void**)&h->synth_start_host[i], sizeof(long long) * nb, hipHostMallocMapped));
+                    if (!h->synth_start_ev[i])
+                        HIPCHK(hipEventCreateWithFlags(&h->synth_start_ev[i], hipEventDisableTiming));
+                }
+                h->synth_start_cap = nb;
+            }
+            stage = h->synth_start_next;
+            h->synth_start_next = (stage + 1) % fqlpop::kSynthStage;
+            // the buffer's last reader (the start gather of kSynthStage collects ago) has run
+            if (h->synth_start_used[stage]) HIPCHK(hipEventSynchronize(h->synth_start_ev[stage]));
+            for (int e = 0; e < n_branches; ++e) h->synth_start_host[stage][e] = start_rows[e];
+            long long* dp = nullptr;
+            HIPCHK(hipHostGetDevicePointer((void**)&dp, h->synth_start_host[stage], 0));
+            d_start = dp;
+        }
+        float* w = h->synth_ws;
+        float* d_init = w; w += nb * D;
+        float* d_out = w; w += n * nb * 2;
+        float* d_oobs = w; w += n * nb * D;
+        float* d_tobs = w; w += n * T * nb * D;
+        float* d_tact = w;
+        hipStream_t s = h->sM;
+        launch_synth_starts(h->ds[0].obs, h->ds[0].rows, h->D, d_start, seed, n_branches, d_init, s);
+        if (stage >= 0) {
+            HIPCHK(hipEventRecord(h->synth_start_ev[stage], s));
+            h->synth_start_used[stage] = true;
+        }
+        // fqlpop_rollout_record's launch on the handle's buffers (noise NULL).  The traces are
+        // not zeroed: the append reads only the entries the rollout wrote (t < episode length).
+        RolloutArgs r = rollout_args(h, n_branches, horizon, seed);
+        r.init_obs = d_init; r.noise = nullptr; r.out = d_out; r.out_obs = d_oobs;
+        r.traj_obs = d_tobs; r.traj_act = d_tact;
+        launch_rollout(r, s);
+        SynthCollectArgs c{};
+        c.ring = h->synth; c.D = h->D; c.A = h->A; c.n_envs = n_branches; c.max_steps = horizon;
+        c.out = d_out; c.out_obs = d_oobs; c.traj_obs = d_tobs; c.traj_act = d_tact;
+        c.nz = h->nz; c.slots = h->slots;
+        launch_synth_append(c, s);
+        launch_synth_commit(c, s);
+        HIPCHK(hipGetLastError());
+    });
+}
+
+int fqlpop_synth_info(fqlpop_t* h, int member, int64_t* rows, int64_t* head, int64_t* appended) {
+    return guard([&] {
+        need_rings(h);
+        check_member(h, member);
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        long long c[SYNTH_CTR];
+        HIPCHK(hipMemcpy(c, h->synth.ctr + (long long)member * SYNTH_CTR, sizeof(c), hipMemcpyDeviceToHost));
+        if (rows) *rows = c[0];
+        if (head) *head = c[1];
+        if (appended) *appended = c[2];
+    });
+}
+
+int fqlpop_synth_read(fqlpop_t* h, int member, float* obs, float* act, float* rew, float* mask, float* next_obs,
+                      int64_t n) {
+    return guard([&] {
+        need_rings(h);
+        check_member(h, member);
+        ARGCHK(obs && act && rew && mask && next_obs, "null argument");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->sM));
+        long long rows = 0;
+        HIPCHK(hipMemcpy(&rows, h->synth.ctr + (long long)member * SYNTH_CTR, sizeof(rows), hipMemcpyDeviceToHost));
+        ARGCHK(n >= 0 && n <= rows, "n exceeds the ring's valid rows");
+        if (n == 0) return;
+        const long long so = (long long)member * h->synth.cap;
+        auto down = [&](float* dst, const float* src, long long w) {
+            HIPCHK(hipMemcpy(dst, src + so * w, sizeof(float) * n * w, hipMemcpyDeviceToHost));
+        };
+        down(obs, h->synth.obs, h->D);
+        down(act, h->synth.act, h->A);
+        down(rew, h->synth.rew, 1);
+        down(mask, h->synth.mask, 1);
+        down(next_obs, h->synth.nobs, h->D);
+    });
+}
+
+int fqlpop_synth_clear(fqlpop_t* h, int member) {
+    return guard([&] {
+        need_rings(h);
+        ARGCHK(member >= -1 && member < h->n, "member index out of range");
+        HIPCHK(hipSetDevice(h->device));
+        long long* p = h->synth.ctr + (member < 0 ? 0 : (long long)member * SYNTH_CTR);
+        HIPCHK(hipMemsetAsync(p, 0, sizeof(long long) * SYNTH_CTR * (member < 0 ? h->n : 1), h->sM));
     });
 }
 

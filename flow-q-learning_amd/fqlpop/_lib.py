@@ -159,6 +159,14 @@ _SIGS = {
     "fqlpop_rollout_ensemble": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_int32), _F, _F]),
     "fqlpop_rollout_ensemble_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "fqlpop_synth_create": (ctypes.c_int, [_P, ctypes.c_int64]),
+    "fqlpop_synth_set_ratio": (ctypes.c_int, [_P, ctypes.c_float]),
+    "fqlpop_synth_collect": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_synth_info": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_synth_read": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64]),
+    "fqlpop_synth_clear": (ctypes.c_int, [_P, ctypes.c_int]),
     "fqlpop_emtrain_param_count": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_create": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

@@ -165,6 +165,14 @@ def eval_round_seed(base_seed: int, round_index: int) -> int:
     return int(np.random.default_rng([int(base_seed) & 0xFFFFFFFF, int(round_index)]).integers(0, 2**31 - 1))
 
 
+def collect_seed(base_seed: int, collect_index: int) -> int:
+    """Seed of the ``collect_index``-th collect of world-model branches of a run
+    (``Population.collect``): a function of the run seed and that index alone.  The third
+    word keeps it apart from ``eval_round_seed`` of the same numbers."""
+    words = [int(base_seed) & 0xFFFFFFFF, int(collect_index), 0x5E13]
+    return int(np.random.default_rng(words).integers(0, 2**31 - 1))
+
+
 def member_eval_seed(base_seed: int, round_index: int, cfg) -> int:
     """Seed of one candidate's own evaluation in round ``round_index`` (tasks without
     a batched world-model evaluation): a function of the run seed, the round and the

@@ -457,6 +457,56 @@ class Population:
         check(self.lib.fqlpop_rollout_ensemble_time(self._h, ctypes.byref(us)))
         return us.value
 
+    # ------------------------------------------- training on world-model branches
+    def synth_create(self, capacity_rows: int):
+        """A ring of ``capacity_rows`` synthetic transitions for every member
+        (fqlpop_synth_create); real_ratio starts at 1, so nothing changes until it is lowered."""
+        check(self.lib.fqlpop_synth_create(self._h, int(capacity_rows)))
+        self.synth_capacity = int(capacity_rows)
+
+    def set_real_ratio(self, real_ratio: float):
+        """The share of offline rows in the training minibatch (fqlpop_synth_set_ratio): 1
+        offline only, 0 ring rows only (while a member's ring is empty it draws offline
+        rows).  Holds from the next enqueued step on."""
+        check(self.lib.fqlpop_synth_set_ratio(self._h, float(real_ratio)))
+
+    def collect(self, n_branches: int, horizon: int, seed: int, start_rows=None):
+        """Branches of every ACTIVE member in the env model of ``set_env_model``, appended to
+        its ring on the device (fqlpop_synth_collect): ``n_branches`` branches of at most
+        ``horizon`` steps from rows of the training dataset -- ``start_rows`` (int
+        [n_branches]) or drawn on the device from ``seed`` -- the same rows for every member.
+        Stream-ordered with ``step`` and ``clone_members``; returns without waiting."""
+        sr = None
+        if start_rows is not None:
+            sr = np.ascontiguousarray(np.asarray(start_rows, dtype=np.int64).reshape(-1))
+            if sr.shape[0] != int(n_branches):
+                raise ValueError(f"start_rows needs {int(n_branches)} entries, got {sr.shape[0]}")
+        check(self.lib.fqlpop_synth_collect(
+            self._h, int(n_branches), int(horizon), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+            None if sr is None else sr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+
+    def synth_info(self, member: int) -> dict:
+        """{"rows", "head", "appended"} of one member's ring; synchronises."""
+        r, hd, ap = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib.fqlpop_synth_info(self._h, int(member), ctypes.byref(r), ctypes.byref(hd), ctypes.byref(ap)))
+        return {"rows": int(r.value), "head": int(hd.value), "appended": int(ap.value)}
+
+    def synth_read(self, member: int, n: int | None = None) -> dict:
+        """Ring positions 0 .. n - 1 (default: every valid row) of one member as a dataset
+        dict (observations, actions, rewards, masks, next_observations); synchronises."""
+        n = self.synth_info(member)["rows"] if n is None else int(n)
+        D, A = self.cfg.obs_dim, self.cfg.action_dim
+        out = {"observations": np.zeros((n, D), np.float32), "actions": np.zeros((n, A), np.float32),
+               "rewards": np.zeros(n, np.float32), "masks": np.zeros(n, np.float32),
+               "next_observations": np.zeros((n, D), np.float32)}
+        check(self.lib.fqlpop_synth_read(self._h, int(member), fptr(out["observations"]), fptr(out["actions"]),
+                                         fptr(out["rewards"]), fptr(out["masks"]), fptr(out["next_observations"]), n))
+        return out
+
+    def synth_clear(self, member: int = -1):
+        """Empty one member's ring, or (-1) all; stream-ordered."""
+        check(self.lib.fqlpop_synth_clear(self._h, int(member)))
+
     # ----------------------------------------------------------------- state
     def get_flat(self, member: int, which: int = STATE_PARAMS) -> np.ndarray:
         flat = np.zeros(self.state_size, dtype=np.float32)

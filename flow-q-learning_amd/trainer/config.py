@@ -40,6 +40,37 @@ class ExperimentConfig:
 
 
 @dataclass
+class ModelRolloutConfig:
+    """Training on world-model branches (no reference counterpart, so not a TrainerConfig
+    field: that class mirrors the reference's).  Off while ``branches`` is 0.  Every
+    ``interval`` updates, once a group has passed ``warmup`` updates, each member rolls
+    ``branches`` branches of at most ``horizon`` steps in the task's env model into its
+    ring of ``buffer_rows`` rows; the training minibatch takes the share ``real_ratio`` of
+    its rows from the offline data and the rest from the ring."""
+    branches: int = 0
+    horizon: int = 5
+    interval: int = 1000
+    warmup: int = 0
+    real_ratio: float = 0.5
+    buffer_rows: int = 100_000
+
+    @property
+    def enabled(self) -> bool:
+        return self.branches > 0
+
+    def validate(self) -> None:
+        if not self.enabled:
+            return
+        if self.horizon < 1 or self.interval < 1 or self.warmup < 0:
+            raise ValueError("model rollouts need horizon >= 1, interval >= 1 and warmup >= 0")
+        if not 0.0 <= self.real_ratio <= 1.0:
+            raise ValueError(f"model_real_ratio must be in [0, 1], got {self.real_ratio}")
+        if self.branches * self.horizon > self.buffer_rows:
+            raise ValueError(f"model_buffer_rows {self.buffer_rows} holds less than one collect "
+                             f"({self.branches} branches x {self.horizon} steps)")
+
+
+@dataclass
 class TrainerConfig:
     seed: int = 0
     steps: int = 1_000_000

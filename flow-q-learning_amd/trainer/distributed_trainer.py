@@ -38,15 +38,18 @@ import numpy as np
 from fqlpop import distributed as D
 from hpo.strategy import HpoStrategy
 from task.task import Task
-from trainer.config import TrainerConfig
-from trainer.trainer import PBT_DISTRIBUTED_MSG, Trainer
+from trainer.config import ModelRolloutConfig, TrainerConfig
+from trainer.trainer import MODEL_ROLLOUT_DISTRIBUTED_MSG, PBT_DISTRIBUTED_MSG, Trainer
 
 
 class DistributedTrainer(Trainer):
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
-                 device: int = 0):
+                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None):
         if hasattr(strategy, "parent_of"):
             raise NotImplementedError(PBT_DISTRIBUTED_MSG)
+        if model_rollouts is not None and model_rollouts.enabled:
+            raise NotImplementedError(MODEL_ROLLOUT_DISTRIBUTED_MSG)
+        self.model_rollouts = ModelRolloutConfig()
         self.rank, self.world_size = D.world()
         self.task = task
         self.strategy = strategy

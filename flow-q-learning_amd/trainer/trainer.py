@@ -30,13 +30,20 @@ from fqlpop import Population, PopulationConfig
 from fqlpop import distributed as D
 from hpo.strategy import HpoStrategy
 from task.task import Task
-from trainer.config import TrainerConfig
+from trainer.config import ModelRolloutConfig, TrainerConfig
 from trainer.experiment import Experiment, agent_config_for, train_population
 from dataclasses import asdict
 
 PBT_DISTRIBUTED_MSG = ("strategies that clone members (parent_of: PopulationBasedTraining) run on one GPU only: "
                        "cross-rank exploit is not implemented; run tune_alpha.py --strategy pbt without "
                        "torch.distributed.run (WORLD_SIZE = 1)")
+MODEL_ROLLOUT_DISTRIBUTED_MSG = ("training on world-model branches (--model_rollout_branches) runs on one GPU only: "
+                                 "a member's ring of synthetic transitions lives on its GPU and is not moved "
+                                 "when pruning rebalances members between ranks; run tune_alpha.py without "
+                                 "torch.distributed.run (WORLD_SIZE = 1)")
+MODEL_ROLLOUT_TASK_MSG = ("training on world-model branches (--model_rollout_branches) needs a task that can attach "
+                          "an env model to the population: OfflineTaskWithSimulatedEvaluations (--task simulated); "
+                          "got {task}")
 LINEAGE_COLUMNS = ("round", "step", "child", "parent", "parent_alpha", "child_alpha", "parent_score")
 
 
@@ -44,12 +51,20 @@ class Trainer:
     _clones = False  # (DistributedTrainer refuses cloning strategies)
 
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
-                 device: int = 0):
+                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None):
         self.task = task
         self.strategy = strategy
         self.config = config
         self.experiments = {}
         self.member_of = {}
+        # training on world-model branches: off (and nothing below differs) unless branches > 0
+        self.model_rollouts = model_rollouts if model_rollouts is not None else ModelRolloutConfig()
+        self.collect_index = int(state_dict.get("collect_index", 0)) if state_dict else 0
+        if self.model_rollouts.enabled:  # refused before any GPU call
+            from task.offline_task_simulated import OfflineTaskWithSimulatedEvaluations
+            if not isinstance(task, OfflineTaskWithSimulatedEvaluations):
+                raise ValueError(MODEL_ROLLOUT_TASK_MSG.format(task=type(task).__name__))
+            self.model_rollouts.validate()
         # a strategy that exposes parent_of (PopulationBasedTraining) refills the slots of the
         # candidates it drops with clones of others; everything below keyed on _clones is new
         # ground, and Identity / SuccessiveHalving runs take none of it
@@ -96,6 +111,12 @@ class Trainer:
             pop.set_dataset(dd["train"], "train")
             pop.set_dataset(dd["val"], "val")
         self._free_slots = list(range(len(configs)))
+        if self.model_rollouts.enabled:
+            # the rings start empty, on a resumed run too (they are not checkpointed): until a
+            # member's first collect its minibatches are offline rows only
+            self.task.attach(pop)
+            pop.synth_create(self.model_rollouts.buffer_rows)
+            pop.set_real_ratio(self.model_rollouts.real_ratio)
         return pop
 
     def _slot_for(self, cfg) -> int:
@@ -123,6 +144,8 @@ class Trainer:
             # exactly len(candidates) slots
             sd["retired"] = list(self.retired_experiments)
             sd["lineage"] = list(self.lineage)
+        if self.model_rollouts.enabled:
+            sd["collect_index"] = self.collect_index
         return sd
 
     def _base_state_dict(self) -> dict:
@@ -145,11 +168,29 @@ class Trainer:
             groups.setdefault(exp.current_step, []).append(exp)
         for step, exps in groups.items():
             n = min(self.config.eval_interval, self.config.steps - step)
-            if exps[0].on_device:
+            if exps[0].on_device and self.model_rollouts.enabled:
+                self._train_with_rollouts(exps, n)
+            elif exps[0].on_device:
                 train_population(exps, n)
             else:
                 for e in exps:
                     e.train(self.config.eval_interval)
+
+    def _train_with_rollouts(self, exps, n: int) -> None:
+        """``n`` updates of one lock-step group in chunks that end at the multiples of
+        ``model_rollouts.interval``; after each such chunk, from ``warmup`` updates on, every
+        member of the group rolls its branches into its ring (one ``Population.collect``,
+        stream-ordered between the steps: no synchronisation).  The collect after the run's
+        last update is skipped: nothing would train on it."""
+        mr = self.model_rollouts
+        cur, target = exps[0].current_step, exps[0].current_step + n
+        while cur < target:
+            nxt = min(target, (cur // mr.interval + 1) * mr.interval)
+            train_population(exps, nxt - cur)  # (leaves exactly this group active)
+            cur = nxt
+            if cur % mr.interval == 0 and cur >= mr.warmup and cur < self.config.steps:
+                self.population.collect(mr.branches, mr.horizon, D.collect_seed(self.config.seed, self.collect_index))
+                self.collect_index += 1
 
     def _evaluate_round(self, configs) -> dict:
         """World-model tasks: every candidate of the round in one GPU rollout

@@ -13,6 +13,12 @@ Data: --task synthetic (default; SURVEY.md 8d transitions + a toy evaluation
 env), --task npz (local OGBench .npz files under --data_directory) or --task
 simulated (candidates scored by world-model rollouts on the GPU).
 
+Training on world-model branches (--task simulated, one GPU): --model_rollout_branches N
+--model_rollout_horizon H --model_rollout_interval I [--model_rollout_warmup W]
+[--model_real_ratio R] [--model_buffer_rows C]: every I updates each member rolls N branches
+of H steps in the env model into its own on-device ring, and its minibatches take the share
+R from the offline data, the rest from the ring (trainer/trainer.py; off by default).
+
 Multi-GPU (BASELINE configs 4 / 5): launched by torch.distributed.run with one
 process per GPU (``python -m torch.distributed.run --nproc-per-node 8
 --master-addr 127.0.0.1 tune_alpha.py ...``), the population is sharded over the
@@ -31,7 +37,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from argparser import build_config_from_args, get_argparser  # noqa: E402
+from argparser import build_config_from_args, build_model_rollout_config_from_args, get_argparser  # noqa: E402
 from hpo.identity import Identity  # noqa: E402
 from hpo.pbt import PopulationBasedTraining  # noqa: E402
 from hpo.successive_halving import SuccessiveHalving  # noqa: E402
@@ -99,8 +105,14 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     config = build_config_from_args(args)
+    model_rollouts = build_model_rollout_config_from_args(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     device = 0
+    if world_size > 1 and model_rollouts.enabled and not args.single_experiment:
+        from trainer.trainer import MODEL_ROLLOUT_DISTRIBUTED_MSG
+        sys.exit(MODEL_ROLLOUT_DISTRIBUTED_MSG)  # before any process group exists
+    if args.single_experiment and model_rollouts.enabled:
+        sys.exit("--model_rollout_branches needs the population Trainer (drop --single_experiment)")
     if world_size > 1 and args.strategy == "pbt" and not args.single_experiment:
         from trainer.trainer import PBT_DISTRIBUTED_MSG
         sys.exit(PBT_DISTRIBUTED_MSG)  # before any process group exists
@@ -157,9 +169,10 @@ def main(argv=None):
                                      state_dict=state.get("strategy"))
     if world_size > 1:
         from trainer.distributed_trainer import DistributedTrainer
-        trainer = DistributedTrainer(task, strategy, config, state_dict=state.get("trainer"), device=device)
+        trainer = DistributedTrainer(task, strategy, config, state_dict=state.get("trainer"), device=device,
+                                     model_rollouts=model_rollouts)
     else:
-        trainer = Trainer(task, strategy, config, state_dict=state.get("trainer"))
+        trainer = Trainer(task, strategy, config, state_dict=state.get("trainer"), model_rollouts=model_rollouts)
     trainer.train(max_evaluations=args.max_evaluations)
     trainer_state = trainer.state_dict()  # collective under DistributedTrainer (rank 0 gets it)
     if trainer_state is not None:

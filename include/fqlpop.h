@@ -204,7 +204,8 @@ int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int r
 /* Copies the complete training state of member src[i] into member dst[i], i < n_pairs, and
  * gives dst[i] alpha alphas[i] and seed seeds[i]: both parameter buffers and their W^T
  * copies, the target critic, Adam m and v and the update count, in one device launch on the
- * stream the steps run on.  Ordered after the steps enqueued before it and before later
+ * stream the steps run on (and, with fqlpop_synth_create's rings, the ring and its counters
+ * in a second one).  Ordered after the steps enqueued before it and before later
  * ones; no host staging and no synchronisation, so it may return before the copy has run
  * (fqlpop_sync waits).  FQLPOP_E_ARG, with nothing enqueued, unless n_pairs >= 1, every
  * index is in range, the dst are pairwise distinct and no dst is also a src; a src may
@@ -376,6 +377,71 @@ int fqlpop_rollout_ensemble(fqlpop_t* h, const float* init_obs, int n_envs, int 
  * handle, in microseconds (HIP events around the launch, as fqlpop_envmodel_replay_time).
  * FQLPOP_E_STATE before the first call.  [no reference counterpart] */
 int fqlpop_rollout_ensemble_time(fqlpop_t* h, double* kernel_us);
+
+/* ---------------------------------------------------------------------
+ * Training on world-model branches: a ring of synthetic transitions per member, filled on
+ * the device by short on-policy branches in the env model, and a training draw that mixes
+ * ring rows with offline rows (MBPO-style branched rollouts).  The reference's
+ * Experiment.train is offline only (trainer/experiment.py:106-109): every call of this
+ * section has [no reference counterpart].  A population without rings behaves exactly as
+ * before. */
+
+/* Allocates, for every one of the n_members slots, a ring of capacity_rows rows of the
+ * dataset's five row-major fields (obs[D], act[A], rew, mask, next_obs[D]) and its
+ * device-resident counters: rows (valid rows, <= capacity), head (next write position),
+ * appended (total so far), all 0; real_ratio is 1.  FQLPOP_E_ARG for capacity_rows < 1 (or
+ * >= 2^32); a failed allocation is FQLPOP_E_HIP with the size in the message and leaves no
+ * rings; a second call is FQLPOP_E_STATE.  Synchronises; drops the captured step graphs.
+ * Every other call of this section is FQLPOP_E_STATE before it. */
+int fqlpop_synth_create(fqlpop_t* h, int64_t capacity_rows);
+
+/* real_ratio rho in [0, 1] (else FQLPOP_E_ARG): a device-resident value the training draw
+ * reads, written in stream order, so it holds from the next enqueued step on, captured
+ * graphs included.  Row b of a member's training minibatch at update count c, with
+ * w0..w3 the Philox4x32-10 block at counter (b, c, train salt, 0) under the member key
+ * (w0 the row draw and w1 the flow time, as without rings) and u = (w2 >> 8) * 2^-24:
+ *   u < rho (float32) or rows == 0:  offline row (w0 * n_rows) >> 32, as without rings;
+ *   else:                            position (w0 * rows) >> 32 of the member's ring.
+ * rho = 1, or empty rings: every value of the step is what it is without rings, bit for
+ * bit.  fqlpop_total_loss and the injected steps never read the rings. */
+int fqlpop_synth_set_ratio(fqlpop_t* h, float real_ratio);
+
+/* For every ACTIVE member: n_branches branches of at most horizon steps of its one-step
+ * policy in fqlpop_set_env_model's model, appended to its ring.
+ *   starts  branch e starts at the training dataset's obs[idx[e]], the same for all members:
+ *           idx[e] = start_rows[e] (host int64 [n_branches], each in [0, n_rows)), or, with
+ *           start_rows NULL, (w0 * n_rows) >> 32 with w0 the first word of Philox4x32-10 at
+ *           counter (e, 0, 0x5E13, 0) under the key (low, high 32 bits of seed).
+ *   branch  exactly fqlpop_rollout_record(init_obs = those rows, n_envs = n_branches,
+ *           max_steps = horizon, seed, noise = NULL): the same launch on device buffers.
+ *   rows    step t < len_e of branch e gives (s_t, a_t, r, m, s_{t+1}): s_{t+1} the next
+ *           recorded observation, for the branch's last step the rollout's out_obs; r = 0,
+ *           m = 0 if the step terminated (logit > 0), else r = -1, m = 1
+ *           (task/offline_task_simulated.py:85-107; reaching horizon is a truncation).
+ *   order   the call's valid transitions in (t, then e) order go to ring positions
+ *           (head + i) mod capacity; then head advances by their count, rows = min(capacity,
+ *           rows + count).  A position is a prefix count over that order, never the order
+ *           in which blocks run: identical runs give byte-identical rings.
+ * Stream-ordered with the steps and clones enqueued before and after it; copies nothing to
+ * the host and may return before it has run.  Before any launch: FQLPOP_E_STATE without
+ * rings, env model or training dataset; FQLPOP_E_UNSUPPORTED as fqlpop_rollout;
+ * FQLPOP_E_ARG for n_branches < 1, horizon < 1 (or > 65535), n_branches * horizon > capacity
+ * (or >= 2^31) or a start row out of range.  No active member: succeeds and does nothing. */
+int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows);
+
+/* The counters of one member's ring (any may be NULL); synchronises. */
+int fqlpop_synth_info(fqlpop_t* h, int member, int64_t* rows, int64_t* head, int64_t* appended);
+
+/* Ring positions 0 .. n - 1 of one member (n <= rows, else FQLPOP_E_ARG) to host arrays
+ * obs [n][obs_dim], act [n][action_dim], rew [n], mask [n], next_obs [n][obs_dim];
+ * synchronises.  For tests and checkpoints. */
+int fqlpop_synth_read(fqlpop_t* h, int member, float* obs, float* act, float* rew, float* mask, float* next_obs,
+                      int64_t n);
+
+/* Empties one member's ring (counters to 0), or every ring with member = -1; stream-ordered.
+ * fqlpop_set_member with reinit != 0 does the same for its member, and
+ * fqlpop_clone_members gives dst[i] a copy of src[i]'s ring and counters. */
+int fqlpop_synth_clear(fqlpop_t* h, int member);
 
 /* ---------------------------------------------------------------------------
  * Env-model trainer: the reference's world-model
