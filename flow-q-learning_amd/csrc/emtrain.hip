@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/fqlpop.h"
+#include "hostmem.h"
 #include "kernels.h"
 
 #define DEV __device__ __forceinline__
@@ -1458,41 +1459,24 @@ __global__ __launch_bounds__(256) void em_adam_kernel(const AdamArgsEm a) {
 }  // namespace fq
 
 // ===================================================================== ABI ==
+using namespace fq;
 using namespace fq::em;
 
 namespace {
-thread_local std::string em_err;
-struct EmErr {
-    int code;
-    std::string msg;
-};
-#define EMCHK(x)                                                                          \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) throw EmErr{FQLPOP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)}; \
-    } while (0)
-#define EMARG(c, m)                                          \
-    do {                                                     \
-        if (!(c)) throw EmErr{FQLPOP_E_ARG, std::string(m)}; \
-    } while (0)
+// fqlpop_last_error's text lives in runtime.cpp, which does not use hostmem.h yet: the shared
+// guard's text is handed on (an empty text after a success)
 template <class F>
 int em_guard(F&& f) {
-    try {
-        f();
-        em_err.clear();
-        return FQLPOP_OK;
-    } catch (const EmErr& e) {
-        em_err = e.msg;
-        fq::set_last_error(e.msg.c_str());
-        return e.code;
-    }
+    const int rc = guard(std::forward<F>(f));
+    fq::set_last_error(g_last_error.c_str());
+    return rc;
 }
 
 // flax leaf order (path-sorted): Dense_i/bias, Dense_i/kernel ..., LayerNorm_0/bias, LayerNorm_0/scale
 Net layout(int in, int nh, const int* hid, int out, bool ln, long long* total) {
     Net n{};
     n.n = nh + 1;
-    EMARG(n.n <= MAXL, "too many layers");
+    ARGCHK(n.n <= MAXL, "too many layers");
     n.dims[0] = in;
     for (int i = 0; i < nh; ++i) n.dims[i + 1] = hid[i];
     n.dims[nh + 1] = out;
@@ -1531,19 +1515,24 @@ struct fqlpop_emtrain {
     int device = 0;
     Net net{}, tpn{};
     long long P = 0, PT = 0;
-    float *params = nullptr, *m = nullptr, *v = nullptr, *part = nullptr, *logs = nullptr, *tp = nullptr;
-    float *wt = nullptr, *tpt = nullptr;  // W^T copies (the backward's dX reads)
-    float *d_obs = nullptr, *d_act = nullptr, *d_rew = nullptr, *d_nobs = nullptr;
-    long long n_rows = 0;
-    float *i_obs = nullptr, *i_act = nullptr, *i_rew = nullptr, *i_nobs = nullptr;
-    unsigned char* i_keep = nullptr;
+    DevBuf<float> params, m, v, part, logs;
+    DevBuf<float> wt;                     // W^T copies (the backward's dX reads)
+    struct Frozen {                       // the frozen termination predictor and its W^T copies
+        DevBuf<float> tp, tpt;
+    } frozen;
+    struct Data {                         // the dataset (rows == 0, null pointers: none)
+        DevBuf<float> obs, act, rew, nobs;
+        long long rows = 0;
+    } data;
+    DevBuf<float> i_obs, i_act, i_rew, i_nobs;
+    DevBuf<unsigned char> i_keep;
     long long count = 0;
     int blocks = 0;
     int lds_bytes = 0;
     int T = 1;                   // rows per sequence of a batch (FQLPOP_EM_MULTISTEP: sequence_length)
-    float* seq = nullptr;        // multistep: per-(block, step) activation store
+    DevBuf<float> seq;           // multistep: per-(block, step) activation store
     long long seq_stride = 0;
-    unsigned long long* probe = nullptr;  // diagnostic builds: sweep phase sums (mapped host memory)
+    HostBuf<unsigned long long> probe;    // diagnostic builds: sweep phase sums (mapped host memory)
     long long probe_launches = 0;
     bool sweep = false;          // multistep through em_sweep_kernel + em_seq_dw_kernel (sw_fits)
     int tchunks = 1;             // sweep: T chunks of the dW GEMM (partial sets per block)
@@ -1554,34 +1543,25 @@ struct fqlpop_emtrain {
     int xcd = 0;                 // engine option em_ens_xcd at creation
     uint64_t seeds[ENS_MAX] = {};
     long long s_par = 0, s_part = 0, s_logs = 0, s_seq = 0, s_obs = 0, s_act = 0, s_rew = 0, s_keep = 0;
-    hipStream_t s = nullptr;
+    Stream<> s;
 };
 
-static void em_free(fqlpop_emtrain* h) {
-    for (void* p : {(void*)h->params, (void*)h->m, (void*)h->v, (void*)h->part, (void*)h->logs, (void*)h->tp,
-                    (void*)h->d_obs, (void*)h->d_act, (void*)h->d_rew, (void*)h->d_nobs, (void*)h->i_obs,
-                    (void*)h->i_act, (void*)h->i_rew, (void*)h->i_nobs, (void*)h->i_keep, (void*)h->seq,
-                    (void*)h->wt, (void*)h->tpt})
-        if (p) (void)hipFree(p);
-    if (h->s) (void)hipStreamDestroy(h->s);
-}
-
 static void em_layouts(const fqlpop_emtrain_config* c, Net* net, long long* P, Net* tpn, long long* PT) {
-    EMARG(c->obs_dim > 0 && c->action_dim >= 0, "bad obs/action dims");
-    EMARG(c->num_hidden >= 0 && c->num_hidden < MAXL, "bad num_hidden");
-    for (int i = 0; i < c->num_hidden; ++i) EMARG(c->hidden_dims[i] > 0 && c->hidden_dims[i] <= 1024, "bad hidden dim");
+    ARGCHK(c->obs_dim > 0 && c->action_dim >= 0, "bad obs/action dims");
+    ARGCHK(c->num_hidden >= 0 && c->num_hidden < MAXL, "bad num_hidden");
+    for (int i = 0; i < c->num_hidden; ++i) ARGCHK(c->hidden_dims[i] > 0 && c->hidden_dims[i] <= 1024, "bad hidden dim");
     if (c->kind == FQLPOP_EM_STATE_PREDICTOR || c->kind == FQLPOP_EM_MULTISTEP) {
         *net = layout(c->obs_dim + c->action_dim, c->num_hidden, c->hidden_dims, c->obs_dim, true, P);
         *PT = 0;
         if (c->termination_weight > 0.f) {
-            EMARG(c->tp_num_hidden >= 0 && c->tp_num_hidden < MAXL, "bad tp_num_hidden");
+            ARGCHK(c->tp_num_hidden >= 0 && c->tp_num_hidden < MAXL, "bad tp_num_hidden");
             *tpn = layout(c->obs_dim, c->tp_num_hidden, c->tp_hidden_dims, 1, false, PT);
         } else {
             *tpn = Net{};
             tpn->ln_scale = tpn->ln_bias = -1;
         }
     } else {
-        EMARG(c->kind == FQLPOP_EM_TERMINATION,
+        ARGCHK(c->kind == FQLPOP_EM_TERMINATION,
               "kind must be FQLPOP_EM_STATE_PREDICTOR, FQLPOP_EM_TERMINATION or FQLPOP_EM_MULTISTEP");
         *net = layout(c->obs_dim, c->num_hidden, c->hidden_dims, 1, false, P);
         *tpn = Net{};
@@ -1607,7 +1587,7 @@ extern "C" {
 
 int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_params) {
     return em_guard([&] {
-        EMARG(cfg && n_params, "null argument");
+        ARGCHK(cfg && n_params, "null argument");
         Net a, b;
         long long P, PT;
         em_layouts(cfg, &a, &P, &b, &PT);
@@ -1622,8 +1602,8 @@ int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_para
 static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* params, int64_t n_params,
                       const uint64_t* seeds, int xcd, int device, fqlpop_emtrain_t** out) {
     {
-        EMARG(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
-        EMARG(cfg->steps > 0, "steps must be > 0");
+        ARGCHK(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
+        ARGCHK(cfg->steps > 0, "steps must be > 0");
         auto h = std::make_unique<fqlpop_emtrain>();
         h->cfg = *cfg;
         h->device = device;
@@ -1632,22 +1612,22 @@ static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* para
         for (int k = 0; k < K; ++k) h->seeds[k] = seeds[k];
         h->cfg.seed = seeds[0];
         em_layouts(cfg, &h->net, &h->P, &h->tpn, &h->PT);
-        EMARG(n_params == h->P * K, "params size mismatch");
+        ARGCHK(n_params == h->P * K, "params size mismatch");
         // LDS: x0, xhat [K0][R], acts [sum dims][R], gA, gB [maxd][R], nobs [D][R], tp acts
         int maxd = 0, sum = 0, tsum = 0;
         for (int i = 0; i <= h->net.n; ++i) { maxd = std::max(maxd, h->net.dims[i]); sum += h->net.dims[i]; }
         for (int i = 0; i <= h->tpn.n && h->tpn.n > 0; ++i) { maxd = std::max(maxd, h->tpn.dims[i]); tsum += h->tpn.dims[i]; }
         const bool ms = cfg->kind == FQLPOP_EM_MULTISTEP;
         if (ms) {
-            EMARG(cfg->sequence_length >= 1, "sequence_length must be >= 1");
-            EMARG(cfg->episode_length > cfg->sequence_length, "episode_length must exceed sequence_length");
+            ARGCHK(cfg->sequence_length >= 1, "sequence_length must be >= 1");
+            ARGCHK(cfg->episode_length > cfg->sequence_length, "episode_length must exceed sequence_length");
             h->T = cfg->sequence_length;
         }
         // multistep: + the carried-gradient buffer, + the prediction buffer when no frozen
         // termination predictor owns one
         const long long fl = (long long)R * (2 * h->net.dims[0] + sum + 3 * maxd + cfg->obs_dim + tsum +
                                              (ms ? cfg->obs_dim * (h->tpn.n > 0 ? 1 : 2) : 0));
-        EMARG(fl * 4 <= 150 * 1024, "env-model layer widths exceed the LDS budget of the fused step");
+        ARGCHK(fl * 4 <= 150 * 1024, "env-model layer widths exceed the LDS budget of the fused step");
         h->lds_bytes = (int)(fl * 4);
         h->blocks = cfg->batch_size / R;
         if (ms && fq::engine_option_em_seq_sweep() && sw_fits(h->net, h->tpn, h->tpn.n > 0, cfg->obs_dim)) {
@@ -1678,59 +1658,49 @@ static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* para
             h->seq_stride = (long long)R * (h->net.dims[0] + 1 + act + D + gfl);
             h->s_seq = h->seq_stride * h->T * h->blocks;
         }
-        try {
-            EMCHK(hipSetDevice(device));
-            EMCHK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
-            const long long PK = h->s_par * K;
-            EMCHK(hipMalloc(&h->params, 4 * PK));
-            EMCHK(hipMalloc(&h->m, 4 * PK));
-            EMCHK(hipMalloc(&h->v, 4 * PK));
-            EMCHK(hipMalloc(&h->part, 4 * h->s_part * K));
-            EMCHK(hipMalloc(&h->logs, 4 * h->s_logs * K));
-            EMCHK(hipMalloc(&h->wt, 4 * PK));
-            EMCHK(hipMemset(h->params, 0, 4 * PK));
-            EMCHK(hipMemset(h->wt, 0, 4 * PK));
-            for (int k = 0; k < K; ++k) {
-                const float* pk = params + (long long)k * P;
-                EMCHK(hipMemcpy(h->params + k * h->s_par, pk, 4 * P, hipMemcpyHostToDevice));
-                const std::vector<float> wt = transposed(h->net, pk, P);
-                EMCHK(hipMemcpy(h->wt + k * h->s_par, wt.data(), 4 * P, hipMemcpyHostToDevice));
-            }
-            EMCHK(hipMemset(h->m, 0, 4 * PK));
-            EMCHK(hipMemset(h->v, 0, 4 * PK));
-            EMCHK(hipMemset(h->logs, 0, 4 * h->s_logs * K));
-            if (ms) {
-                // the record store of every model (about 300 MB per model at B = T = 256, default widths)
-                const long long bytes = 4 * h->s_seq * K;
-                const hipError_t e = hipMalloc(&h->seq, bytes);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    throw EmErr{FQLPOP_E_HIP, "multistep record store: hipMalloc of " + std::to_string(bytes) + " bytes (" +
-                                                  std::to_string(K) + " models x " + std::to_string(4 * h->s_seq) +
-                                                  ") failed: " + hipGetErrorString(e)};
-                }
-            }
-            EMCHK(hipMalloc(&h->i_obs, 4 * h->s_obs * K));
-            EMCHK(hipMalloc(&h->i_act, 4 * std::max(1LL, h->s_act * K)));
-            EMCHK(hipMalloc(&h->i_rew, 4 * h->s_rew * K));
-            EMCHK(hipMalloc(&h->i_nobs, 4 * h->s_obs * K));
-            EMCHK(hipMalloc(&h->i_keep, h->s_keep * K));
-            EMCHK(hipFuncSetAttribute((const void*)em_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-            EMCHK(hipFuncSetAttribute((const void*)em_seq_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      h->lds_bytes));
-            if (h->sweep)
-                EMCHK(hipFuncSetAttribute((const void*)em_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          h->sweep_lds));
-#ifdef FQ_DIAG
-            if (h->sweep && std::getenv("FQLPOP_EM_PROBE")) {
-                EMCHK(hipHostMalloc((void**)&h->probe, 8 * EM_PH_N, hipHostMallocMapped | hipHostMallocCoherent));
-                std::memset(h->probe, 0, 8 * EM_PH_N);
-            }
-#endif
-        } catch (...) {
-            em_free(h.get());
-            throw;
+        HIPCHK(hipSetDevice(device));
+        h->s = Stream<>::create();
+        const long long PK = h->s_par * K;
+        h->params = DevBuf<float>(PK, "env-model parameters");
+        h->m = DevBuf<float>(PK, "env-model Adam moments");
+        h->v = DevBuf<float>(PK, "env-model Adam moments");
+        h->part = DevBuf<float>(h->s_part * K, "env-model partial grads");
+        h->logs = DevBuf<float>(h->s_logs * K);
+        h->wt = DevBuf<float>(PK, "env-model parameters");
+        HIPCHK(hipMemset(h->params, 0, 4 * PK));
+        HIPCHK(hipMemset(h->wt, 0, 4 * PK));
+        for (int k = 0; k < K; ++k) {
+            const float* pk = params + (long long)k * P;
+            HIPCHK(hipMemcpy(h->params + k * h->s_par, pk, 4 * P, hipMemcpyHostToDevice));
+            const std::vector<float> wt = transposed(h->net, pk, P);
+            HIPCHK(hipMemcpy(h->wt + k * h->s_par, wt.data(), 4 * P, hipMemcpyHostToDevice));
         }
+        HIPCHK(hipMemset(h->m, 0, 4 * PK));
+        HIPCHK(hipMemset(h->v, 0, 4 * PK));
+        HIPCHK(hipMemset(h->logs, 0, 4 * h->s_logs * K));
+        if (ms) {
+            // the record store of every model (about 300 MB per model at B = T = 256, default widths)
+            const std::string what = "multistep record store (" + std::to_string(K) + " models x " +
+                                     std::to_string(4 * h->s_seq) + " bytes)";
+            h->seq = DevBuf<float>(h->s_seq * K, what.c_str());
+        }
+        h->i_obs = DevBuf<float>(h->s_obs * K);
+        h->i_act = DevBuf<float>(std::max(1LL, h->s_act * K));
+        h->i_rew = DevBuf<float>(h->s_rew * K);
+        h->i_nobs = DevBuf<float>(h->s_obs * K);
+        h->i_keep = DevBuf<unsigned char>(h->s_keep * K);
+        HIPCHK(hipFuncSetAttribute((const void*)em_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+        HIPCHK(hipFuncSetAttribute((const void*)em_seq_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   h->lds_bytes));
+        if (h->sweep)
+            HIPCHK(hipFuncSetAttribute((const void*)em_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       h->sweep_lds));
+#ifdef FQ_DIAG
+        if (h->sweep && std::getenv("FQLPOP_EM_PROBE")) {
+            h->probe = HostBuf<unsigned long long>(EM_PH_N, hipHostMallocMapped | hipHostMallocCoherent);
+            std::memset(h->probe, 0, 8 * EM_PH_N);
+        }
+#endif
         *out = h.release();
     }
 }
@@ -1740,7 +1710,7 @@ extern "C" {
 int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params, int64_t n_params, int device,
                           fqlpop_emtrain_t** out) {
     return em_guard([&] {
-        EMARG(cfg && params && out, "null argument");
+        ARGCHK(cfg && params && out, "null argument");
         em_create(cfg, 1, params, n_params, &cfg->seed, 0, device, out);
     });
 }
@@ -1748,16 +1718,16 @@ int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params,
 int fqlpop_emtrain_create_ensemble(const fqlpop_emtrain_config* cfg, int n_models, const float* params,
                                    int64_t n_params, const uint64_t* seeds, int device, fqlpop_emtrain_t** out) {
     return em_guard([&] {
-        EMARG(cfg && params && out, "null argument");
-        EMARG(seeds, "null seeds: an ensemble takes one seed per model");
-        EMARG(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
+        ARGCHK(cfg && params && out, "null argument");
+        ARGCHK(seeds, "null seeds: an ensemble takes one seed per model");
+        ARGCHK(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
         em_create(cfg, n_models, params, n_params, seeds, fq::engine_option_em_ens_xcd(), device, out);
     });
 }
 
 int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models) {
     return em_guard([&] {
-        EMARG(h && n_models, "null argument");
+        ARGCHK(h && n_models, "null argument");
         *n_models = h->K;
     });
 }
@@ -1765,13 +1735,13 @@ int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models) {
 int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xcd_mode, int linear_block,
                                       int* grid_blocks, int* model, int* block) {
     return em_guard([&] {
-        EMARG(grid_blocks && model && block, "null argument");
-        EMARG(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
-        EMARG(blocks_per_model >= 1 && blocks_per_model <= (1 << 20), "blocks_per_model must be 1..2^20");
-        EMARG(xcd_mode == 0 || xcd_mode == 1, "xcd_mode must be 0 or 1");
+        ARGCHK(grid_blocks && model && block, "null argument");
+        ARGCHK(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
+        ARGCHK(blocks_per_model >= 1 && blocks_per_model <= (1 << 20), "blocks_per_model must be 1..2^20");
+        ARGCHK(xcd_mode == 0 || xcd_mode == 1, "xcd_mode must be 0 or 1");
         int m = -1, b = -1;
         const int grid = ens_block_map(n_models, blocks_per_model, xcd_mode, 0, &m, &b);
-        EMARG(linear_block >= 0 && linear_block < grid, "linear_block outside the grid");
+        ARGCHK(linear_block >= 0 && linear_block < grid, "linear_block outside the grid");
         ens_block_map(n_models, blocks_per_model, xcd_mode, linear_block, &m, &b);
         *grid_blocks = grid;
         *model = m;
@@ -1790,47 +1760,51 @@ int fqlpop_emtrain_destroy(fqlpop_emtrain_t* h) {
                 if (h->probe[i])
                     std::fprintf(stderr, " %d:%.2f", i, h->probe[i] * 0.01 / ((double)h->probe_launches * h->T));
             std::fprintf(stderr, "\n");
-            (void)hipHostFree(h->probe);
         }
-        em_free(h);
         delete h;
     });
 }
 
 int fqlpop_emtrain_set_frozen_termination(fqlpop_emtrain_t* h, const float* tp_params, int64_t n) {
     return em_guard([&] {
-        EMARG(h && tp_params, "null argument");
-        EMARG(h->PT > 0, "no frozen termination predictor in this config (termination_weight == 0)");
-        EMARG(n == h->PT, "termination predictor size mismatch");
-        EMCHK(hipSetDevice(h->device));
-        if (!h->tp) EMCHK(hipMalloc(&h->tp, 4 * h->PT));
-        if (!h->tpt) EMCHK(hipMalloc(&h->tpt, 4 * h->PT));
-        EMCHK(hipMemcpy(h->tp, tp_params, 4 * h->PT, hipMemcpyHostToDevice));
-        const std::vector<float> tt = transposed(h->tpn, tp_params, h->PT);
-        EMCHK(hipMemcpy(h->tpt, tt.data(), 4 * h->PT, hipMemcpyHostToDevice));
+        ARGCHK(h && tp_params, "null argument");
+        ARGCHK(h->PT > 0, "no frozen termination predictor in this config (termination_weight == 0)");
+        ARGCHK(n == h->PT, "termination predictor size mismatch");
+        HIPCHK(hipSetDevice(h->device));
+        replace_built(h->frozen, [&] {
+            fqlpop_emtrain::Frozen f{DevBuf<float>(h->PT), DevBuf<float>(h->PT)};
+            HIPCHK(hipMemcpy(f.tp, tp_params, 4 * h->PT, hipMemcpyHostToDevice));
+            const std::vector<float> tt = transposed(h->tpn, tp_params, h->PT);
+            HIPCHK(hipMemcpy(f.tpt, tt.data(), 4 * h->PT, hipMemcpyHostToDevice));
+            HIPCHK(hipStreamSynchronize(h->s));  // the current predictor's last reader has run
+            return f;
+        });
     });
 }
 
 int fqlpop_emtrain_set_dataset(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                const float* next_obs, int64_t n_rows) {
     return em_guard([&] {
-        EMARG(h && obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null argument");
-        EMARG(n_rows > 0, "n_rows must be > 0");
+        ARGCHK(h && obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null argument");
+        ARGCHK(n_rows > 0, "n_rows must be > 0");
         if (h->cfg.kind == FQLPOP_EM_MULTISTEP)  // MultistepLoader reshapes to [n / episode_length][episode_length]
-            EMARG(n_rows % h->cfg.episode_length == 0, "multistep: n_rows must be a multiple of episode_length");
-        EMCHK(hipSetDevice(h->device));
-        for (float* p : {h->d_obs, h->d_act, h->d_rew, h->d_nobs})
-            if (p) EMCHK(hipFree(p));
+            ARGCHK(n_rows % h->cfg.episode_length == 0, "multistep: n_rows must be a multiple of episode_length");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
         const long long D = h->cfg.obs_dim, A = h->cfg.action_dim;
-        EMCHK(hipMalloc(&h->d_obs, 4 * n_rows * D));
-        EMCHK(hipMalloc(&h->d_act, 4 * std::max(1LL, n_rows * A)));
-        EMCHK(hipMalloc(&h->d_rew, 4 * n_rows));
-        EMCHK(hipMalloc(&h->d_nobs, 4 * n_rows * D));
-        EMCHK(hipMemcpy(h->d_obs, obs, 4 * n_rows * D, hipMemcpyHostToDevice));
-        if (A) EMCHK(hipMemcpy(h->d_act, act, 4 * n_rows * A, hipMemcpyHostToDevice));
-        EMCHK(hipMemcpy(h->d_rew, rew, 4 * n_rows, hipMemcpyHostToDevice));
-        EMCHK(hipMemcpy(h->d_nobs, next_obs, 4 * n_rows * D, hipMemcpyHostToDevice));
-        h->n_rows = n_rows;
+        replace_released(h->data, [&] {
+            fqlpop_emtrain::Data d;
+            d.obs = DevBuf<float>(n_rows * D, "env-model dataset");
+            d.act = DevBuf<float>(std::max(1LL, n_rows * A), "env-model dataset");
+            d.rew = DevBuf<float>(n_rows, "env-model dataset");
+            d.nobs = DevBuf<float>(n_rows * D, "env-model dataset");
+            HIPCHK(hipMemcpy(d.obs, obs, 4 * n_rows * D, hipMemcpyHostToDevice));
+            if (A) HIPCHK(hipMemcpy(d.act, act, 4 * n_rows * A, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d.rew, rew, 4 * n_rows, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d.nobs, next_obs, 4 * n_rows * D, hipMemcpyHostToDevice));
+            d.rows = n_rows;
+            return d;
+        });
     });
 }
 
@@ -1851,9 +1825,9 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected, bool share
     a.net = h->net;
     a.tpn = h->tpn;
     a.params = h->params;
-    a.tp = h->tp;
+    a.tp = h->frozen.tp;
     a.wt = h->wt;
-    a.tpt = h->tpt;
+    a.tpt = h->frozen.tpt;
     a.part = h->part;
     a.P = h->P;
     a.logs = h->logs;
@@ -1862,8 +1836,8 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected, bool share
         a.obs = h->i_obs; a.act = h->i_act; a.rew = h->i_rew; a.nobs = h->i_nobs;
         a.n_rows = (long long)c.batch_size * h->T;
     } else {
-        a.obs = h->d_obs; a.act = h->d_act; a.rew = h->d_rew; a.nobs = h->d_nobs;
-        a.n_rows = h->n_rows;
+        a.obs = h->data.obs; a.act = h->data.act; a.rew = h->data.rew; a.nobs = h->data.nobs;
+        a.n_rows = h->data.rows;
     }
     a.step = h->count;
     a.B = c.batch_size; a.D = c.obs_dim; a.A = c.action_dim;
@@ -1875,7 +1849,7 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected, bool share
     a.tchunks = h->tchunks;
     if (h->probe && train) {
         unsigned long long* dp = nullptr;
-        EMCHK(hipHostGetDevicePointer((void**)&dp, h->probe, 0));
+        HIPCHK(hipHostGetDevicePointer((void**)&dp, h->probe, 0));
         a.probe = dp;
         ++h->probe_launches;
     }
@@ -1891,7 +1865,7 @@ static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
     const unsigned K = (unsigned)h->K;
     if (h->sweep) {
         hipLaunchKernelGGL(em_sweep_kernel, dim3(grid), dim3(SW_NT), h->sweep_lds, h->s, a);
-        EMCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         if (a.train) {
             SeqDwArgs d{};
             d.seq = h->seq; d.seq_stride = h->seq_stride; d.part = h->part; d.P = h->P; d.net = h->net;
@@ -1910,7 +1884,7 @@ static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
     } else {
         hipLaunchKernelGGL(em_grad_kernel, dim3(grid), dim3(NT), h->lds_bytes, h->s, a);
     }
-    EMCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (!a.train) return;
     // optax.cosine_decay_schedule(init, steps)(count), adam bias correction with count + 1
     const auto& c = h->cfg;
@@ -1923,77 +1897,77 @@ static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
     ad.bc1 = (float)(1.0 - std::pow(0.9, (double)(h->count + 1)));
     ad.bc2 = (float)(1.0 - std::pow(0.999, (double)(h->count + 1)));
     hipLaunchKernelGGL(em_adam_kernel, dim3((unsigned)((h->P + 255) / 256), K), dim3(256), 0, h->s, ad);
-    EMCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     ++h->count;
 }
 
 static void em_check_ready(fqlpop_emtrain* h) {
-    if (h->cfg.kind != FQLPOP_EM_TERMINATION && h->cfg.termination_weight > 0.f && !h->tp)
-        throw EmErr{FQLPOP_E_STATE, "termination_weight > 0 needs fqlpop_emtrain_set_frozen_termination"};
+    if (h->cfg.kind != FQLPOP_EM_TERMINATION && h->cfg.termination_weight > 0.f && !h->frozen.tp)
+        throw Err{FQLPOP_E_STATE, "termination_weight > 0 needs fqlpop_emtrain_set_frozen_termination"};
 }
 
 int fqlpop_emtrain_step(fqlpop_emtrain_t* h, int n_steps) {
     return em_guard([&] {
-        EMARG(h && n_steps >= 0, "bad argument");
-        EMARG(h->n_rows > 0, "no dataset: call fqlpop_emtrain_set_dataset");
+        ARGCHK(h && n_steps >= 0, "bad argument");
+        ARGCHK(h->data.rows > 0, "no dataset: call fqlpop_emtrain_set_dataset");
         em_check_ready(h);
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         for (int i = 0; i < n_steps; ++i) em_launch_step(h, em_args(h, true, false));
     });
 }
 
 // the single-model entry points refuse an ensemble handle, naming the call that serves it
 #define EM_SINGLE(h, call) \
-    EMARG((h)->K == 1, "this handle holds an ensemble of models: use " call)
+    ARGCHK((h)->K == 1, "this handle holds an ensemble of models: use " call)
 
 // nb batches ([nb][B..] host arrays; 1: the one batch of a single model or a shared one) into
 // the injected slots 0..nb-1
 static void em_upload_batch(fqlpop_emtrain* h, const float* obs, const float* act, const float* rew,
                             const float* next_obs, int nb = 1) {
-    EMARG(obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null batch array");
+    ARGCHK(obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null batch array");
     const long long B = (long long)h->cfg.batch_size * h->T * nb, D = h->cfg.obs_dim, A = h->cfg.action_dim;
-    EMCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * D, hipMemcpyHostToDevice, h->s));
-    if (A) EMCHK(hipMemcpyAsync(h->i_act, act, 4 * B * A, hipMemcpyHostToDevice, h->s));
-    EMCHK(hipMemcpyAsync(h->i_rew, rew, 4 * B, hipMemcpyHostToDevice, h->s));
-    EMCHK(hipMemcpyAsync(h->i_nobs, next_obs, 4 * B * D, hipMemcpyHostToDevice, h->s));
+    HIPCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * D, hipMemcpyHostToDevice, h->s));
+    if (A) HIPCHK(hipMemcpyAsync(h->i_act, act, 4 * B * A, hipMemcpyHostToDevice, h->s));
+    HIPCHK(hipMemcpyAsync(h->i_rew, rew, 4 * B, hipMemcpyHostToDevice, h->s));
+    HIPCHK(hipMemcpyAsync(h->i_nobs, next_obs, 4 * B * D, hipMemcpyHostToDevice, h->s));
 }
 
 int fqlpop_emtrain_step_injected(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                  const float* next_obs, const uint8_t* keep_mask) {
     return em_guard([&] {
-        EMARG(h, "null handle");
+        ARGCHK(h, "null handle");
         EM_SINGLE(h, "fqlpop_emtrain_step_injected_ensemble");
         em_check_ready(h);
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         em_upload_batch(h, obs, act, rew, next_obs);
         StepArgs a = em_args(h, true, true);
         if (keep_mask) {
-            EMCHK(hipMemcpyAsync(h->i_keep, keep_mask, (size_t)h->cfg.batch_size * h->cfg.obs_dim,
+            HIPCHK(hipMemcpyAsync(h->i_keep, keep_mask, (size_t)h->cfg.batch_size * h->cfg.obs_dim,
                                  hipMemcpyHostToDevice, h->s));
             a.keep = h->i_keep;
         }
         em_launch_step(h, a);
-        EMCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
+        HIPCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
     });
 }
 
 int fqlpop_emtrain_step_injected_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                           const float* next_obs, const uint8_t* keep_mask, int shared) {
     return em_guard([&] {
-        EMARG(h, "null handle");
-        EMARG(shared == 0 || shared == 1, "shared must be 0 or 1");
+        ARGCHK(h, "null handle");
+        ARGCHK(shared == 0 || shared == 1, "shared must be 0 or 1");
         em_check_ready(h);
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         const int nb = shared ? 1 : h->K;
         em_upload_batch(h, obs, act, rew, next_obs, nb);
         StepArgs a = em_args(h, true, true, shared != 0);
         if (keep_mask) {
-            EMCHK(hipMemcpyAsync(h->i_keep, keep_mask, (size_t)h->cfg.batch_size * h->cfg.obs_dim * nb,
+            HIPCHK(hipMemcpyAsync(h->i_keep, keep_mask, (size_t)h->cfg.batch_size * h->cfg.obs_dim * nb,
                                  hipMemcpyHostToDevice, h->s));
             a.keep = h->i_keep;
         }
         em_launch_step(h, a);
-        EMCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
+        HIPCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
     });
 }
 
@@ -2024,25 +1998,25 @@ static void em_logs_model(const fqlpop_emtrain* h, const float* lg, float* out) 
 // logs [K][FQLPOP_EM_LOG_STRIDE]: one copy and one synchronisation for all K models
 static void em_logs(fqlpop_emtrain* h, float* out) {
     std::vector<float> lg((size_t)h->s_logs * h->K);
-    EMCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
-    EMCHK(hipStreamSynchronize(h->s));
+    HIPCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
+    HIPCHK(hipStreamSynchronize(h->s));
     for (int k = 0; k < h->K; ++k)
         em_logs_model(h, lg.data() + (size_t)k * h->s_logs, out + (size_t)k * FQLPOP_EM_LOG_STRIDE);
 }
 
 int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs) {
     return em_guard([&] {
-        EMARG(h && logs, "null argument");
+        ARGCHK(h && logs, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_read_logs_ensemble");
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         em_logs(h, logs);
     });
 }
 
 int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs) {
     return em_guard([&] {
-        EMARG(h && logs, "null argument");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && logs, "null argument");
+        HIPCHK(hipSetDevice(h->device));
         em_logs(h, logs);
     });
 }
@@ -2050,10 +2024,10 @@ int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs) {
 int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                         const float* next_obs, float* logs) {
     return em_guard([&] {
-        EMARG(h && logs, "null argument");
+        ARGCHK(h && logs, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_eval_ensemble");
         em_check_ready(h);
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         em_upload_batch(h, obs, act, rew, next_obs);
         em_launch_step(h, em_args(h, false, true));
         em_logs(h, logs);
@@ -2063,10 +2037,10 @@ int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act,
 int fqlpop_emtrain_eval_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                  const float* next_obs, int shared, float* logs) {
     return em_guard([&] {
-        EMARG(h && logs, "null argument");
-        EMARG(shared == 0 || shared == 1, "shared must be 0 or 1");
+        ARGCHK(h && logs, "null argument");
+        ARGCHK(shared == 0 || shared == 1, "shared must be 0 or 1");
         em_check_ready(h);
-        EMCHK(hipSetDevice(h->device));
+        HIPCHK(hipSetDevice(h->device));
         em_upload_batch(h, obs, act, rew, next_obs, shared ? 1 : h->K);
         em_launch_step(h, em_args(h, false, true, shared != 0));
         em_logs(h, logs);
@@ -2074,17 +2048,17 @@ int fqlpop_emtrain_eval_ensemble(fqlpop_emtrain_t* h, const float* obs, const fl
 }
 
 static void em_get_params(fqlpop_emtrain* h, int model, int which, float* out, int64_t n) {
-    EMARG(n == h->P, "params size mismatch");
-    EMARG(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
-    EMCHK(hipSetDevice(h->device));
+    ARGCHK(n == h->P, "params size mismatch");
+    ARGCHK(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
+    HIPCHK(hipSetDevice(h->device));
     const float* src = (which == 0 ? h->params : which == 1 ? h->m : h->v) + model * h->s_par;
-    EMCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
-    EMCHK(hipStreamSynchronize(h->s));
+    HIPCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(hipStreamSynchronize(h->s));
 }
 
 int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_t n) {
     return em_guard([&] {
-        EMARG(h && out, "null argument");
+        ARGCHK(h && out, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_get_params_model");
         em_get_params(h, 0, which, out, n);
     });
@@ -2092,24 +2066,24 @@ int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_
 
 int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, float* out, int64_t n) {
     return em_guard([&] {
-        EMARG(h && out, "null argument");
-        EMARG(model >= 0 && model < h->K, "model index out of range");
+        ARGCHK(h && out, "null argument");
+        ARGCHK(model >= 0 && model < h->K, "model index out of range");
         em_get_params(h, model, which, out, n);
     });
 }
 
 int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count) {
     return em_guard([&] {
-        EMARG(h && count, "null argument");
+        ARGCHK(h && count, "null argument");
         *count = h->count;
     });
 }
 
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h) {
     return em_guard([&] {
-        EMARG(h, "null handle");
-        EMCHK(hipSetDevice(h->device));
-        EMCHK(hipStreamSynchronize(h->s));
+        ARGCHK(h, "null handle");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
     });
 }
 
@@ -2358,23 +2332,29 @@ struct fqlpop_initobs {
     VaeArgs proto{};                     // layer table and segments
     Net seg_net[3]{};                    // the segments as em_adam_kernel's Dense chains
     long long P = 0;
-    float *params = nullptr, *wt = nullptr, *m = nullptr, *v = nullptr, *part = nullptr, *logs = nullptr;
-    float *d_obs = nullptr, *i_obs = nullptr, *i_eps = nullptr;
-    float *s_z = nullptr, *s_out = nullptr;  // fqlpop_initobs_sample buffers (grown on demand)
-    long long s_cap = 0;
-    long long n_rows = 0, count = 0;
+    DevBuf<float> params, wt, m, v, part, logs;
+    DevBuf<float> i_obs, i_eps;
+    struct Data {                        // the dataset (rows == 0, null pointer: none)
+        DevBuf<float> obs;
+        long long rows = 0;
+    } data;
+    struct Staging {                     // fqlpop_initobs_sample buffers (grown on demand)
+        DevBuf<float> z, out;
+        long long cap = 0;
+    } stage;
+    long long count = 0;
     int blocks = 0, lds_bytes = 0, dec_lds = 0;
-    hipStream_t s = nullptr;
+    Stream<> s;
 };
 
 namespace {
 // the layer table in flat (flax path-sorted) order; throws E_ARG on a bad shape
 void vae_layout(const fqlpop_initobs_config* c, VaeArgs* a, long long* P) {
-    EMARG(c->obs_dim >= 1 && c->obs_dim <= 4096, "obs_dim must be in 1..4096");
-    EMARG(c->latent_dim >= 1 && c->latent_dim <= 64, "latent_dim must be in 1..64");
-    EMARG(c->num_hidden >= 1 && c->num_hidden <= VMAXH, "num_hidden must be in 1..6");
+    ARGCHK(c->obs_dim >= 1 && c->obs_dim <= 4096, "obs_dim must be in 1..4096");
+    ARGCHK(c->latent_dim >= 1 && c->latent_dim <= 64, "latent_dim must be in 1..64");
+    ARGCHK(c->num_hidden >= 1 && c->num_hidden <= VMAXH, "num_hidden must be in 1..6");
     for (int i = 0; i < c->num_hidden; ++i)
-        EMARG(c->hidden_dims[i] >= 1 && c->hidden_dims[i] <= 512, "hidden widths must be in 1..512");
+        ARGCHK(c->hidden_dims[i] >= 1 && c->hidden_dims[i] <= 512, "hidden widths must be in 1..512");
     const int nh = c->num_hidden, D = c->obs_dim, L = c->latent_dim;
     *a = VaeArgs{};
     a->nh = nh; a->D = D; a->L = L;
@@ -2422,13 +2402,6 @@ Net vae_chain(const VaeDense* const* ds, int n, long long base) {
     return net;
 }
 
-void vae_free(fqlpop_initobs* h) {
-    for (void* p : {(void*)h->params, (void*)h->wt, (void*)h->m, (void*)h->v, (void*)h->part, (void*)h->logs,
-                    (void*)h->d_obs, (void*)h->i_obs, (void*)h->i_eps, (void*)h->s_z, (void*)h->s_out})
-        if (p) (void)hipFree(p);
-    if (h->s) (void)hipStreamDestroy(h->s);
-}
-
 VaeArgs vae_args(fqlpop_initobs* h, bool train, bool injected, const float* eps) {
     VaeArgs a = h->proto;
     a.train = train ? 1 : 0;
@@ -2438,8 +2411,8 @@ VaeArgs vae_args(fqlpop_initobs* h, bool train, bool injected, const float* eps)
     for (int s = 0; s < 3; ++s) a.part[s] = h->part + (long long)h->blocks * a.segoff[s];
     a.logs = h->logs;
     a.injected = injected ? 1 : 0;
-    a.obs = injected ? h->i_obs : h->d_obs;
-    a.n_rows = injected ? h->cfg.batch_size : h->n_rows;
+    a.obs = injected ? h->i_obs.get() : h->data.obs.get();
+    a.n_rows = injected ? h->cfg.batch_size : h->data.rows;
     a.eps = eps;
     a.seed = h->cfg.seed;
     a.step = h->count;
@@ -2449,7 +2422,7 @@ VaeArgs vae_args(fqlpop_initobs* h, bool train, bool injected, const float* eps)
 
 void vae_launch(fqlpop_initobs* h, const VaeArgs& a) {
     hipLaunchKernelGGL(em_vae_grad_kernel, dim3(h->blocks), dim3(NT), h->lds_bytes, h->s, a);
-    EMCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (!a.train) return;
     // optax.cosine_decay_schedule(init, steps)(count), adam bias correction with count + 1
     const auto& c = h->cfg;
@@ -2465,7 +2438,7 @@ void vae_launch(fqlpop_initobs* h, const VaeArgs& a) {
         ad.P = a.segP[s]; ad.blocks = h->blocks;
         ad.lr = lr; ad.bc1 = bc1; ad.bc2 = bc2;
         hipLaunchKernelGGL(em_adam_kernel, dim3((unsigned)((ad.P + 255) / 256)), dim3(256), 0, h->s, ad);
-        EMCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     ++h->count;
 }
@@ -2473,8 +2446,8 @@ void vae_launch(fqlpop_initobs* h, const VaeArgs& a) {
 // logs [FQLPOP_INITOBS_LOG_STRIDE] = reconstruction_loss, kl, loss (vae_loss's logs)
 void vae_logs(fqlpop_initobs* h, float* out) {
     std::vector<float> lg((size_t)VLOG * h->blocks);
-    EMCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
-    EMCHK(hipStreamSynchronize(h->s));
+    HIPCHK(hipMemcpyAsync(lg.data(), h->logs, 4 * lg.size(), hipMemcpyDeviceToHost, h->s));
+    HIPCHK(hipStreamSynchronize(h->s));
     double s[VLOG] = {0};
     for (int b = 0; b < h->blocks; ++b)
         for (int k = 0; k < VLOG; ++k) s[k] += lg[(size_t)b * VLOG + k];
@@ -2488,8 +2461,8 @@ void vae_logs(fqlpop_initobs* h, float* out) {
 
 void vae_upload(fqlpop_initobs* h, const float* obs, const float* eps) {
     const long long B = h->cfg.batch_size;
-    EMCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * h->cfg.obs_dim, hipMemcpyHostToDevice, h->s));
-    if (eps) EMCHK(hipMemcpyAsync(h->i_eps, eps, 4 * B * h->cfg.latent_dim, hipMemcpyHostToDevice, h->s));
+    HIPCHK(hipMemcpyAsync(h->i_obs, obs, 4 * B * h->cfg.obs_dim, hipMemcpyHostToDevice, h->s));
+    if (eps) HIPCHK(hipMemcpyAsync(h->i_eps, eps, 4 * B * h->cfg.latent_dim, hipMemcpyHostToDevice, h->s));
 }
 }  // namespace
 
@@ -2497,7 +2470,7 @@ extern "C" {
 
 int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_params) {
     return em_guard([&] {
-        EMARG(cfg && n_params, "null argument");
+        ARGCHK(cfg && n_params, "null argument");
         VaeArgs a;
         long long P;
         vae_layout(cfg, &a, &P);
@@ -2508,15 +2481,15 @@ int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_para
 int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params, int64_t n_params, int device,
                           fqlpop_initobs_t** out) {
     return em_guard([&] {
-        EMARG(cfg && params && out, "null argument");
+        ARGCHK(cfg && params && out, "null argument");
         auto h = std::make_unique<fqlpop_initobs>();
         h->cfg = *cfg;
         h->device = device;
         vae_layout(cfg, &h->proto, &h->P);
-        EMARG(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
-        EMARG(cfg->steps > 0, "steps must be > 0");
-        EMARG(cfg->reconstruction_weight >= 0.f, "reconstruction_weight must be >= 0");
-        EMARG(n_params == h->P, "params size mismatch");
+        ARGCHK(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
+        ARGCHK(cfg->steps > 0, "steps must be > 0");
+        ARGCHK(cfg->reconstruction_weight >= 0.f, "reconstruction_weight must be >= 0");
+        ARGCHK(n_params == h->P, "params size mismatch");
         const VaeArgs& a = h->proto;
         const int nh = a.nh, D = a.D, L = a.L;
         // dynamic + static LDS of em_vae_grad_kernel (its layout comment), before any GPU call
@@ -2524,7 +2497,7 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
         for (int i = 0; i < nh; ++i) sumh += cfg->hidden_dims[i];
         const long long fl = (long long)R * (2 * D + 2 * sumh + 6 * L + 2 * a.maxd);
         if (fl * 4 + VAE_STATIC_LDS > 160 * 1024)
-            throw EmErr{FQLPOP_E_UNSUPPORTED,
+            throw Err{FQLPOP_E_UNSUPPORTED,
                         "initial-observation VAE: layer widths need " + std::to_string(fl * 4 + VAE_STATIC_LDS) +
                             " bytes of LDS, the fused step has 163840"};
         h->lds_bytes = (int)(fl * 4);
@@ -2540,17 +2513,17 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
             ch[0] = &a.lv;
             h->seg_net[2] = vae_chain(ch, 1, a.segoff[2]);
         }
-        EMCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(device));
         const long long P = h->P, B = cfg->batch_size;
-        EMCHK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
-        EMCHK(hipMalloc(&h->params, 4 * P));
-        EMCHK(hipMalloc(&h->wt, 4 * P));
-        EMCHK(hipMalloc(&h->m, 4 * P));
-        EMCHK(hipMalloc(&h->v, 4 * P));
-        EMCHK(hipMalloc(&h->part, 4 * P * h->blocks));
-        EMCHK(hipMalloc(&h->logs, 4 * (long long)VLOG * h->blocks));
-        EMCHK(hipMalloc(&h->i_obs, 4 * B * D));
-        EMCHK(hipMalloc(&h->i_eps, 4 * B * L));
+        h->s = Stream<>::create();
+        h->params = DevBuf<float>(P, "VAE parameters");
+        h->wt = DevBuf<float>(P, "VAE parameters");
+        h->m = DevBuf<float>(P, "VAE Adam moments");
+        h->v = DevBuf<float>(P, "VAE Adam moments");
+        h->part = DevBuf<float>(P * h->blocks, "VAE partial grads");
+        h->logs = DevBuf<float>((long long)VLOG * h->blocks);
+        h->i_obs = DevBuf<float>(B * D);
+        h->i_eps = DevBuf<float>(B * L);
         std::vector<float> wt(params, params + P);
         auto tr = [&](const VaeDense& d) {
             for (int k = 0; k < d.K; ++k)
@@ -2560,18 +2533,18 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
         for (int i = 0; i < nh; ++i) tr(a.enc[i]);
         tr(a.mu);
         tr(a.lv);
-        EMCHK(hipMemcpy(h->params, params, 4 * P, hipMemcpyHostToDevice));
-        EMCHK(hipMemcpy(h->wt, wt.data(), 4 * P, hipMemcpyHostToDevice));
-        EMCHK(hipMemset(h->m, 0, 4 * P));
-        EMCHK(hipMemset(h->v, 0, 4 * P));
-        EMCHK(hipMemset(h->logs, 0, 4 * (long long)VLOG * h->blocks));
+        HIPCHK(hipMemcpy(h->params, params, 4 * P, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->wt, wt.data(), 4 * P, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(h->m, 0, 4 * P));
+        HIPCHK(hipMemset(h->v, 0, 4 * P));
+        HIPCHK(hipMemset(h->logs, 0, 4 * (long long)VLOG * h->blocks));
         // the limit is the kernel's, not the handle's: the largest any live handle may need
         static int grad_lds_max = 0, dec_lds_max = 0;
         grad_lds_max = std::max(grad_lds_max, h->lds_bytes);
         dec_lds_max = std::max(dec_lds_max, h->dec_lds);
-        EMCHK(hipFuncSetAttribute((const void*)em_vae_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIPCHK(hipFuncSetAttribute((const void*)em_vae_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   grad_lds_max));
-        EMCHK(hipFuncSetAttribute((const void*)em_vae_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIPCHK(hipFuncSetAttribute((const void*)em_vae_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   dec_lds_max));
         *out = h.release();
     });
@@ -2581,51 +2554,49 @@ int fqlpop_initobs_destroy(fqlpop_initobs_t* h) {
     return em_guard([&] {
         if (!h) return;
         (void)hipSetDevice(h->device);
-        if (h->s) (void)hipStreamSynchronize(h->s);
-        vae_free(h);
+        (void)hipDeviceSynchronize();
         delete h;
     });
 }
 
 int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_rows) {
     return em_guard([&] {
-        EMARG(h && obs, "null argument");
-        EMARG(n_rows > 0, "n_rows must be > 0");
-        EMCHK(hipSetDevice(h->device));
-        EMCHK(hipStreamSynchronize(h->s));
-        if (h->d_obs) EMCHK(hipFree(h->d_obs));
-        h->d_obs = nullptr;
-        h->n_rows = 0;
-        EMCHK(hipMalloc(&h->d_obs, 4 * n_rows * h->cfg.obs_dim));
-        EMCHK(hipMemcpy(h->d_obs, obs, 4 * n_rows * h->cfg.obs_dim, hipMemcpyHostToDevice));
-        h->n_rows = n_rows;
+        ARGCHK(h && obs, "null argument");
+        ARGCHK(n_rows > 0, "n_rows must be > 0");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
+        replace_released(h->data, [&] {
+            fqlpop_initobs::Data d{DevBuf<float>(n_rows * h->cfg.obs_dim, "initial-observation dataset"), n_rows};
+            HIPCHK(hipMemcpy(d.obs, obs, 4 * n_rows * h->cfg.obs_dim, hipMemcpyHostToDevice));
+            return d;
+        });
     });
 }
 
 int fqlpop_initobs_step(fqlpop_initobs_t* h, int n_steps) {
     return em_guard([&] {
-        EMARG(h && n_steps >= 0, "bad argument");
-        if (h->n_rows <= 0) throw EmErr{FQLPOP_E_STATE, "no dataset: call fqlpop_initobs_set_dataset first"};
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && n_steps >= 0, "bad argument");
+        if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_initobs_set_dataset first"};
+        HIPCHK(hipSetDevice(h->device));
         for (int i = 0; i < n_steps; ++i) vae_launch(h, vae_args(h, true, false, nullptr));
     });
 }
 
 int fqlpop_initobs_step_injected(fqlpop_initobs_t* h, const float* obs, const float* eps) {
     return em_guard([&] {
-        EMARG(h && obs, "null argument");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && obs, "null argument");
+        HIPCHK(hipSetDevice(h->device));
         vae_upload(h, obs, eps);
         vae_launch(h, vae_args(h, true, true, eps ? h->i_eps : nullptr));
-        EMCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
+        HIPCHK(hipStreamSynchronize(h->s));  // host batch buffers are reused
     });
 }
 
 int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps, float* logs) {
     return em_guard([&] {
-        EMARG(h && obs && logs, "null argument");
-        EMARG(eps, "fqlpop_initobs_eval needs eps (an evaluation is a function of its inputs)");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && obs && logs, "null argument");
+        ARGCHK(eps, "fqlpop_initobs_eval needs eps (an evaluation is a function of its inputs)");
+        HIPCHK(hipSetDevice(h->device));
         vae_upload(h, obs, eps);
         vae_launch(h, vae_args(h, false, true, h->i_eps));
         vae_logs(h, logs);
@@ -2634,69 +2605,64 @@ int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps,
 
 int fqlpop_initobs_read_logs(fqlpop_initobs_t* h, float* logs) {
     return em_guard([&] {
-        EMARG(h && logs, "null argument");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && logs, "null argument");
+        HIPCHK(hipSetDevice(h->device));
         vae_logs(h, logs);
     });
 }
 
 int fqlpop_initobs_get_params(fqlpop_initobs_t* h, int which, float* out, int64_t n) {
     return em_guard([&] {
-        EMARG(h && out, "null argument");
-        EMARG(n == h->P, "params size mismatch");
-        EMARG(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && out, "null argument");
+        ARGCHK(n == h->P, "params size mismatch");
+        ARGCHK(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
+        HIPCHK(hipSetDevice(h->device));
         const float* src = which == 0 ? h->params : which == 1 ? h->m : h->v;
-        EMCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
-        EMCHK(hipStreamSynchronize(h->s));
+        HIPCHK(hipMemcpyAsync(out, src, 4 * n, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(hipStreamSynchronize(h->s));
     });
 }
 
 int fqlpop_initobs_get_count(fqlpop_initobs_t* h, int64_t* count) {
     return em_guard([&] {
-        EMARG(h && count, "null argument");
+        ARGCHK(h && count, "null argument");
         *count = h->count;
     });
 }
 
 int fqlpop_initobs_sync(fqlpop_initobs_t* h) {
     return em_guard([&] {
-        EMARG(h, "null handle");
-        EMCHK(hipSetDevice(h->device));
-        EMCHK(hipStreamSynchronize(h->s));
+        ARGCHK(h, "null handle");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
     });
 }
 
 int fqlpop_initobs_sample(fqlpop_initobs_t* h, int64_t n, uint64_t seed, const float* z, float* out) {
     return em_guard([&] {
-        EMARG(h && out, "null argument");
-        EMARG(n >= 1 && n <= (1LL << 31) - R, "n must be in 1..2^31 - 16");
-        EMCHK(hipSetDevice(h->device));
+        ARGCHK(h && out, "null argument");
+        ARGCHK(n >= 1 && n <= (1LL << 31) - R, "n must be in 1..2^31 - 16");
+        HIPCHK(hipSetDevice(h->device));
         const long long D = h->cfg.obs_dim, L = h->cfg.latent_dim;
-        if (n > h->s_cap) {
-            EMCHK(hipStreamSynchronize(h->s));
-            for (float** p : {&h->s_z, &h->s_out}) {
-                if (*p) EMCHK(hipFree(*p));
-                *p = nullptr;
-            }
-            h->s_cap = 0;
-            EMCHK(hipMalloc(&h->s_z, 4 * n * L));
-            EMCHK(hipMalloc(&h->s_out, 4 * n * D));
-            h->s_cap = n;
+        if (n > h->stage.cap) {
+            HIPCHK(hipStreamSynchronize(h->s));
+            replace_released(h->stage, [&] {
+                return fqlpop_initobs::Staging{DevBuf<float>(n * L, "sample staging"), DevBuf<float>(n * D, "sample staging"), n};
+            });
         }
-        if (z) EMCHK(hipMemcpyAsync(h->s_z, z, 4 * n * L, hipMemcpyHostToDevice, h->s));
+        if (z) HIPCHK(hipMemcpyAsync(h->stage.z, z, 4 * n * L, hipMemcpyHostToDevice, h->s));
         VaeDecArgs a{};
         a.nh = h->proto.nh; a.D = (int)D; a.L = (int)L;
         for (int i = 0; i <= a.nh; ++i) a.dec[i] = h->proto.dec[i];
         a.params = h->params;
-        a.z = z ? h->s_z : nullptr;
-        a.out = h->s_out;
+        a.z = z ? h->stage.z.get() : nullptr;
+        a.out = h->stage.out;
         a.n = n;
         a.seed = seed;
         hipLaunchKernelGGL(em_vae_decode_kernel, dim3((unsigned)((n + R - 1) / R)), dim3(NT), h->dec_lds, h->s, a);
-        EMCHK(hipGetLastError());
-        EMCHK(hipMemcpyAsync(out, h->s_out, 4 * n * D, hipMemcpyDeviceToHost, h->s));
-        EMCHK(hipStreamSynchronize(h->s));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, h->stage.out, 4 * n * D, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(hipStreamSynchronize(h->s));
     });
 }
 

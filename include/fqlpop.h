@@ -499,10 +499,12 @@ int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_para
 int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params, int64_t n_params, int device,
                           fqlpop_emtrain_t** out);
 int fqlpop_emtrain_destroy(fqlpop_emtrain_t* h);
-/* utils/envmodel.py load_model("termination_predictor") of the state trainer's __init__. */
+/* utils/envmodel.py load_model("termination_predictor") of the state trainer's __init__.
+ * A failed call keeps the earlier predictor. */
 int fqlpop_emtrain_set_frozen_termination(fqlpop_emtrain_t* h, const float* tp_params, int64_t n);
 /* The StepLoader's dataset (utils/data_loader.py:47-52), uploaded once: rows sampled on
- * device (uniform with replacement, Philox keyed by seed and step). */
+ * device (uniform with replacement, Philox keyed by seed and step).  Released before the
+ * new one is allocated: a failed upload (FQLPOP_E_HIP) leaves no dataset. */
 int fqlpop_emtrain_set_dataset(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                const float* next_obs, int64_t n_rows);
 /* n_steps train_steps on device-sampled batches (asynchronous). */
@@ -605,7 +607,8 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
                           fqlpop_initobs_t** out);
 int fqlpop_initobs_destroy(fqlpop_initobs_t* h);
 /* InitialObservationLoader's rows (utils/data_loader.py:14-22), [n_rows][obs_dim], copied:
- * minibatches are drawn from them on the device, uniform with replacement. */
+ * minibatches are drawn from them on the device, uniform with replacement.  Released before
+ * the new rows are allocated: a failed upload (FQLPOP_E_HIP) leaves no dataset. */
 int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_rows);
 /* n_steps updates on device-drawn rows and device-drawn eps (vae_loss + adam;
  * asynchronous).  FQLPOP_E_STATE before fqlpop_initobs_set_dataset. */
