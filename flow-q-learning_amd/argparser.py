@@ -51,6 +51,10 @@ def get_argparser() -> argparse.ArgumentParser:
     p.add_argument("--model_rollout_warmup", type=int, default=0)
     p.add_argument("--model_real_ratio", type=float, default=0.5)
     p.add_argument("--model_buffer_rows", type=int, default=100_000)
+    # branches under the env-model ensemble (--env_model_ensemble), rewards lowered by
+    # penalty x the ensemble's disagreement
+    p.add_argument("--model_rollout_ensemble", action="store_true")
+    p.add_argument("--model_rollout_penalty", type=float, default=0.0)
     return p
 
 
@@ -81,7 +85,9 @@ def build_model_rollout_config_from_args(args: argparse.Namespace) -> ModelRollo
         interval=getattr(args, "model_rollout_interval", d.interval),
         warmup=getattr(args, "model_rollout_warmup", d.warmup),
         real_ratio=getattr(args, "model_real_ratio", d.real_ratio),
-        buffer_rows=getattr(args, "model_buffer_rows", d.buffer_rows))
+        buffer_rows=getattr(args, "model_buffer_rows", d.buffer_rows),
+        ensemble=getattr(args, "model_rollout_ensemble", d.ensemble),
+        penalty=getattr(args, "model_rollout_penalty", d.penalty))
 
 
 def get_env_model_argparser() -> argparse.ArgumentParser:

@@ -385,6 +385,10 @@ struct SynthCollectArgs {
     const float* traj_act;        // [nz][max_steps][n_envs][A]
     int nz;
     const int* slots;
+    // fqlpop_synth_collect_ensemble with a penalty: a valid row's reward is its base reward
+    // (0 on a terminated step, -1 otherwise) - penalty * traj_unc[z][t][e].  Null: the base reward.
+    const float* traj_unc;        // null or [nz][max_steps][n_envs]
+    float penalty;
 };
 void launch_synth_starts(const float* obs, long long n_rows, int D, const long long* start_rows, uint64_t seed,
                          int n_envs, float* init_obs, hipStream_t s);
@@ -529,14 +533,24 @@ void launch_rollout(const RolloutArgs& a, hipStream_t s);
 //     counter (e, t, 0x5E12, 0) and the key of the call seed alone.  A step runs the chain
 //     of every model some live column chose and keeps each live column's own s' and
 //     logit; a column that is done keeps its observation.
-// base: sp / tp are null, every other field as for launch_rollout (actions, out_logit and
-// the trace outputs null).
+// base: sp / tp are null, every other field as for launch_rollout (actions and out_logit
+// null; the trace outputs null in mode 0).
+// Record (mode 1 only; fqlpop_rollout_ensemble_record, fqlpop_synth_collect_ensemble): with
+// base.traj_obs / traj_act set, the (s, a) of every column that runs step t at rollout_kernel's
+// row [member][t - 1][env], and (traj_model) that column's model.  With traj_unc set, a
+// step runs the chain of ALL n_models models, merges as before, and writes per live column
+//   u = sqrt(max(0, Q / K - |m|^2 / K^2)),  r_k = s'_k - s'_0,  Q = sum_k |r_k|^2,  m = sum_k r_k
+// the norm of the ensemble's per-coordinate standard deviation of s': exactly 0 when the
+// models' predictions are bitwise equal.  out / out_obs do not depend on any of the four.
+// A launch with all four null runs the instantiation without this code (REC = false).
 constexpr int ENS_MAX_MODELS = 16;
 struct RolloutEnsArgs {
     RolloutArgs base;
     const EnvModelNet* nets;       // device [n_models]: base's layout with model k's sp / tp
     int n_models, mode;
     const int* choice;             // mode 1: null or device [max_steps][n_envs], each in [0, n_models)
+    int* traj_model;               // null or [nz][max_steps][n_envs]
+    float* traj_unc;               // null or [nz][max_steps][n_envs]
 };
 void launch_rollout_ens(const RolloutEnsArgs& a, hipStream_t s);
 

@@ -4282,7 +4282,9 @@ __global__ __launch_bounds__(256) void synth_append_kernel(const SynthCollectArg
         pos = (head + base + rank) % cap;
         // terminated there (logit > 0: success) -> r = 0, m = 0; a truncation at the horizon is no terminal
         const bool term = last && out[2 * e] > 0.5f;
-        a.ring.rew[so + pos] = term ? 0.0f : -1.0f;
+        float rew = term ? 0.0f : -1.0f;
+        if (a.traj_unc) rew -= a.penalty * a.traj_unc[((long long)z * T + t) * NE + e];  // MOPO-style penalty
+        a.ring.rew[so + pos] = rew;
         a.ring.mask[so + pos] = term ? 0.0f : 1.0f;
     }
     pos_s[tid] = pos;
@@ -4382,6 +4384,14 @@ void launch_synth_clone(const SynthCloneArgs& a, hipStream_t s) {
 //     and result stay, whatever its tile-mates do, so an env's episode does not depend on
 //     n_envs or on its tile.
 // LDS: the rollout's plus sel_obs [64][16], a logit row and a choice row.
+// REC (mixed only; launch_rollout_ens picks it when a trace output is set): the record
+// outputs at rollout_kernel's place and row, and with traj_unc the disagreement u of
+// kernels.h: every model's chain runs (need = all), u0_s keeps s'_0 and um_s the sum m of
+// the differences r_k = s'_k - s'_0, both [64][16], and uq_s the columns' Q; the loop over
+// models is block-uniform either way.  The merge is the same statements, so out / out_obs
+// do not depend on REC.  REC = false is the kernel as it was: the launches without traces
+// run that instantiation.  (REC = true spills 32 bytes per lane to scratch.)
+template <bool REC>
 __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const RolloutEnsArgs ga) {
     constexpr int H = EF_H, NC = EF_NC, NT = EF_NW * 64, PF = EF_PF;
     __shared__ __attribute__((aligned(16))) float slab[H * NC + 64];
@@ -4396,6 +4406,7 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const Rollou
     __shared__ int done_s[NC];
     __shared__ float res_s[NC][2];
     __shared__ int all_done;
+    __shared__ float u0_s[REC ? 64 * NC : 1], um_s[REC ? 64 * NC : 1], uq_s[NC];
 
     const RolloutArgs& g = ga.base;
     const EnvModelNet* __restrict__ nets = ga.nets;
@@ -4530,6 +4541,21 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const Rollou
             }
             __syncthreads();
         }
+        const bool unc = REC && ga.traj_unc != nullptr;
+        if (REC && g.traj_obs) {  // (s, a) and the model of the envs that run this step, as rollout_kernel
+            for (int e = tid; e < (D + A) * NC; e += NT) {
+                const bool ob = e < D * NC;
+                const int R = ob ? D : A, q = ob ? e : e - D * NC;
+                const int c = q / R, k = q % R;
+                if (!done_s[c]) {
+                    const long long row = ((long long)z * g.max_steps + (t - 1)) * g.n_envs + e0 + c;
+                    if (ob) g.traj_obs[row * D + k] = obs_s[k * NC + c];
+                    else g.traj_act[row * A + k] = act_s[k * NC + c];
+                }
+            }
+            if (ga.traj_model && tid < NC && !done_s[tid])
+                ga.traj_model[((long long)z * g.max_steps + (t - 1)) * g.n_envs + e0 + tid] = ch_s[tid];
+        }
         // ---- env-model step under every model this step needs --------------
         unsigned need = 1u << km;
         if (mixed) {
@@ -4537,6 +4563,7 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const Rollou
             for (int c = 0; c < NC; ++c)
                 if (!done_s[c]) need |= 1u << ch_s[c];
             need = (unsigned)__builtin_amdgcn_readfirstlane((int)need);
+            if (unc) need = (1u << K) - 1u;  // a live column exists (else the loop has ended): all models
         }
         const float* cur = sel_logit;
         for (int kk = 0; kk < K; ++kk) {
@@ -4548,10 +4575,34 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const Rollou
                     if (!done_s[c] && ch_s[c] == kk) sel_obs[e] = obs_n[e];
                 }
                 if (tid < NC && !done_s[tid] && ch_s[tid] == kk) sel_logit[tid] = logit[tid];
+                if (unc) {
+                    if (kk == 0) {
+                        for (int e = tid; e < D * NC; e += NT) {
+                            u0_s[e] = obs_n[e];
+                            um_s[e] = 0.f;
+                        }
+                        if (tid < NC) uq_s[tid] = 0.f;
+                    } else if (tid < NC) {  // kk - 1's barrier orders this after u0_s / um_s of the models before
+                        float q = 0.f;
+                        for (int k = 0; k < D; ++k) {
+                            const float r = obs_n[k * NC + tid] - u0_s[k * NC + tid];
+                            um_s[k * NC + tid] += r;
+                            q += r * r;
+                        }
+                        uq_s[tid] += q;
+                    }
+                }
                 __syncthreads();
             } else {
                 cur = logit;
             }
+        }
+        if (unc && tid < NC && !done_s[tid]) {
+            float mm = 0.f;
+            for (int k = 0; k < D; ++k) mm += um_s[k * NC + tid] * um_s[k * NC + tid];
+            const float fk = (float)K;
+            ga.traj_unc[((long long)z * g.max_steps + (t - 1)) * g.n_envs + e0 + tid] =
+                sqrtf(fmaxf(uq_s[tid] / fk - mm / (fk * fk), 0.f));
         }
         // ---- bookkeeping (evaluate_actor_fn: first terminated / truncated step)
         if (tid < NC) {
@@ -4596,7 +4647,10 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void rollout_ens_kernel(const Rollou
 void launch_rollout_ens(const RolloutEnsArgs& a, hipStream_t s) {
     const int ntile = (a.base.n_envs + EF_NC - 1) / EF_NC;
     const dim3 grid((unsigned)(ntile * a.base.nz * (a.mode == 1 ? 1 : a.n_models)));
-    hipLaunchKernelGGL(rollout_ens_kernel, grid, dim3(EF_NW * 64), 0, s, a);
+    if (a.mode == 1 && (a.base.traj_obs || a.traj_model || a.traj_unc))
+        hipLaunchKernelGGL(rollout_ens_kernel<true>, grid, dim3(EF_NW * 64), 0, s, a);
+    else
+        hipLaunchKernelGGL(rollout_ens_kernel<false>, grid, dim3(EF_NW * 64), 0, s, a);
 }
 
 // ================================================== recorded-action replay ==

@@ -2783,6 +2783,28 @@ RolloutArgs rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed) 
     r.nz = h->nz; r.slots = h->slots;
     return r;
 }
+// What every rollout under the ensemble needs (fqlpop_rollout_ensemble, _record,
+// fqlpop_synth_collect_ensemble).
+void ens_check(fqlpop_t* h) {
+    if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
+    if (!rollout_supported(h->H, h->L, h->D, h->A))
+        throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+    if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+}
+// The launch arguments of such a rollout but for its buffers (init_obs, noise, choice and
+// the outputs: device pointers the caller sets), as rollout_args for the single model.
+RolloutEnsArgs ens_rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed, int mode) {
+    RolloutEnsArgs e{};
+    RolloutArgs& r = e.base;
+    r = h->ens_args;
+    r.params = h->params; r.P = h->P; r.os_off = h->os.off;
+    for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
+    r.D = h->D; r.A = h->A; r.L = h->L;
+    r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
+    r.nz = h->nz; r.slots = h->slots;
+    e.nets = h->ens_nets; e.n_models = h->ens_n; e.mode = mode;
+    return e;
+}
 // fqlpop_rollout / fqlpop_rollout_record (the latter with both trace outputs)
 void rollout_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise,
                  float* out, float* out_obs, float* out_traj_obs, float* out_traj_act) {
@@ -2902,11 +2924,18 @@ int fqlpop_synth_set_ratio(fqlpop_t* h, float real_ratio) {
     });
 }
 
-int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows) {
-    return guard([&] {
+namespace {
+// fqlpop_synth_collect (ensemble false: rollout_kernel under the single model) and
+// fqlpop_synth_collect_ensemble (rollout_ens_kernel, mixed, the device's own choice; with
+// penalty > 0 its disagreement output, which the append subtracts from the rewards).
+void synth_collect_run(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows,
+                       bool ensemble, float penalty) {
+    {
         need_rings(h);
         if (h->ds[0].rows == 0) throw FqErr{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
-        rollout_check(h);
+        if (ensemble) ens_check(h);
+        else rollout_check(h);
+        ARGCHK(std::isfinite(penalty) && penalty >= 0.0f, "penalty must be finite and >= 0");
         ARGCHK(n_branches >= 1 && horizon >= 1, "n_branches and horizon must be positive");
         ARGCHK((long long)n_branches * horizon <= h->synth.cap, "n_branches * horizon exceeds the ring capacity");
         // the append's grid has a step axis, and its prefix counts are 32-bit
@@ -2918,7 +2947,8 @@ int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed
         if (h->nz == 0) return;
         HIPCHK(hipSetDevice(h->device));
         const long long nb = n_branches, T = horizon, n = h->n, D = h->D, A = h->A;
-        const long long need = nb * D + n * nb * (2 + D) + n * T * nb * (D + A);
+        const bool unc = ensemble && penalty > 0.0f;
+        const long long need = nb * D + n * nb * (2 + D) + n * T * nb * (D + A + (unc ? 1 : 0));
         if (need > h->synth_ws_floats) {  // grown on first use (the earlier collects read the old one)
             HIPCHK(hipStreamSynchronize(h->sM));
             if (h->synth_ws) (void)hipFree(h->synth_ws);
@@ -2963,7 +2993,8 @@ int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed
         float* d_out = w; w += n * nb * 2;
         float* d_oobs = w; w += n * nb * D;
         float* d_tobs = w; w += n * T * nb * D;
-        float* d_tact = w;
+        float* d_tact = w; w += n * T * nb * A;
+        float* d_tunc = unc ? w : nullptr;
         hipStream_t s = h->sM;
         launch_synth_starts(h->ds[0].obs, h->ds[0].rows, h->D, d_start, seed, n_branches, d_init, s);
         if (stage >= 0) {
@@ -2972,18 +3003,38 @@ int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed
         }
         // fqlpop_rollout_record's launch on the handle's buffers (noise NULL).  The traces are
         // not zeroed: the append reads only the entries the rollout wrote (t < episode length).
-        RolloutArgs r = rollout_args(h, n_branches, horizon, seed);
-        r.init_obs = d_init; r.noise = nullptr; r.out = d_out; r.out_obs = d_oobs;
-        r.traj_obs = d_tobs; r.traj_act = d_tact;
-        launch_rollout(r, s);
+        if (ensemble) {  // fqlpop_rollout_ensemble_record's launch likewise (noise and choice NULL)
+            RolloutEnsArgs e = ens_rollout_args(h, n_branches, horizon, seed, FQLPOP_ENS_MIXED);
+            RolloutArgs& r = e.base;
+            r.init_obs = d_init; r.noise = nullptr; r.out = d_out; r.out_obs = d_oobs;
+            r.traj_obs = d_tobs; r.traj_act = d_tact;
+            e.traj_unc = d_tunc;
+            launch_rollout_ens(e, s);
+        } else {
+            RolloutArgs r = rollout_args(h, n_branches, horizon, seed);
+            r.init_obs = d_init; r.noise = nullptr; r.out = d_out; r.out_obs = d_oobs;
+            r.traj_obs = d_tobs; r.traj_act = d_tact;
+            launch_rollout(r, s);
+        }
         SynthCollectArgs c{};
         c.ring = h->synth; c.D = h->D; c.A = h->A; c.n_envs = n_branches; c.max_steps = horizon;
         c.out = d_out; c.out_obs = d_oobs; c.traj_obs = d_tobs; c.traj_act = d_tact;
+        c.traj_unc = d_tunc; c.penalty = penalty;
         c.nz = h->nz; c.slots = h->slots;
         launch_synth_append(c, s);
         launch_synth_commit(c, s);
         HIPCHK(hipGetLastError());
-    });
+    }
+}
+}  // namespace
+
+int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows) {
+    return guard([&] { synth_collect_run(h, n_branches, horizon, seed, start_rows, false, 0.0f); });
+}
+
+int fqlpop_synth_collect_ensemble(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows,
+                                  float penalty) {
+    return guard([&] { synth_collect_run(h, n_branches, horizon, seed, start_rows, true, penalty); });
 }
 
 int fqlpop_synth_info(fqlpop_t* h, int member, int64_t* rows, int64_t* head, int64_t* appended) {
@@ -3177,66 +3228,104 @@ int fqlpop_set_env_model_ensemble(fqlpop_t* h, const fqlpop_envmodel_config* cfg
     });
 }
 
+namespace {
+// fqlpop_rollout_ensemble / fqlpop_rollout_ensemble_record (the latter with out_traj_obs and
+// out_traj_act, and either of out_traj_model / out_traj_unc)
+void ens_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed, const float* noise, int mode,
+             const int32_t* choice, float* out, float* out_obs, float* out_traj_obs, float* out_traj_act,
+             int32_t* out_traj_model, float* out_traj_unc) {
+    ARGCHK(h && init_obs && out, "null argument");
+    ARGCHK(n_envs > 0 && max_steps > 0, "n_envs and max_steps must be positive");
+    ARGCHK(mode == FQLPOP_ENS_PER_MODEL || mode == FQLPOP_ENS_MIXED, "mode must be FQLPOP_ENS_PER_MODEL or FQLPOP_ENS_MIXED");
+    ARGCHK(!(choice && mode == FQLPOP_ENS_PER_MODEL), "choice is for FQLPOP_ENS_MIXED only");
+    ARGCHK(!(out_traj_obs && mode == FQLPOP_ENS_PER_MODEL), "record is for FQLPOP_ENS_MIXED only");
+    if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
+    const int K = h->ens_n;
+    const size_t n_choice = (size_t)max_steps * n_envs;
+    if (choice)
+        for (size_t i = 0; i < n_choice; ++i)
+            ARGCHK(choice[i] >= 0 && choice[i] < K, "choice entries must be in [0, n_models)");
+    ens_check(h);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->sM));
+    const int nz = h->nz, D = h->D, A = h->A;
+    if (nz == 0) return;
+    RolloutEnsArgs e = ens_rollout_args(h, n_envs, max_steps, seed, mode);
+    RolloutArgs& r = e.base;
+    const size_t rows = (size_t)nz * (mode == FQLPOP_ENS_PER_MODEL ? K : 1) * n_envs;
+    const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
+    const size_t n_traj = (size_t)nz * max_steps * n_envs;
+    float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_tobs = nullptr,
+          *d_tact = nullptr, *d_tunc = nullptr;
+    int *d_choice = nullptr, *d_tmodel = nullptr;
+    HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
+    HIPCHK(hipMalloc(&d_out, sizeof(float) * rows * 2));
+    HIPCHK(hipMemcpy(d_obs, init_obs, sizeof(float) * n_envs * D, hipMemcpyHostToDevice));
+    if (noise) {
+        HIPCHK(hipMalloc(&d_noise, sizeof(float) * n_noise));
+        HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
+    }
+    if (choice) {
+        HIPCHK(hipMalloc(&d_choice, sizeof(int) * n_choice));
+        HIPCHK(hipMemcpy(d_choice, choice, sizeof(int) * n_choice, hipMemcpyHostToDevice));
+    }
+    if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * rows * D));
+    if (out_traj_obs) {  // zeroed: the kernel writes the steps an env ran only
+        HIPCHK(hipMalloc(&d_tobs, sizeof(float) * n_traj * D));
+        HIPCHK(hipMalloc(&d_tact, sizeof(float) * n_traj * A));
+        HIPCHK(hipMemsetAsync(d_tobs, 0, sizeof(float) * n_traj * D, h->sM));
+        HIPCHK(hipMemsetAsync(d_tact, 0, sizeof(float) * n_traj * A, h->sM));
+        if (out_traj_model) {
+            HIPCHK(hipMalloc(&d_tmodel, sizeof(int) * n_traj));
+            HIPCHK(hipMemsetAsync(d_tmodel, 0, sizeof(int) * n_traj, h->sM));
+        }
+        if (out_traj_unc) {
+            HIPCHK(hipMalloc(&d_tunc, sizeof(float) * n_traj));
+            HIPCHK(hipMemsetAsync(d_tunc, 0, sizeof(float) * n_traj, h->sM));
+        }
+    }
+    r.init_obs = d_obs; r.noise = d_noise; r.out = d_out; r.out_obs = d_oobs;
+    r.traj_obs = d_tobs; r.traj_act = d_tact;
+    e.choice = d_choice; e.traj_model = d_tmodel; e.traj_unc = d_tunc;
+    HIPCHK(hipEventRecord(h->ev_t0, h->sM));
+    launch_rollout_ens(e, h->sM);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_t1, h->sM));
+    HIPCHK(hipStreamSynchronize(h->sM));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+    h->ens_kernel_us = 1000.0 * ms;
+    HIPCHK(hipMemcpy(out, d_out, sizeof(float) * rows * 2, hipMemcpyDeviceToHost));
+    if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * rows * D, hipMemcpyDeviceToHost));
+    if (out_traj_obs) {
+        HIPCHK(hipMemcpy(out_traj_obs, d_tobs, sizeof(float) * n_traj * D, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out_traj_act, d_tact, sizeof(float) * n_traj * A, hipMemcpyDeviceToHost));
+        if (out_traj_model) HIPCHK(hipMemcpy(out_traj_model, d_tmodel, sizeof(int) * n_traj, hipMemcpyDeviceToHost));
+        if (out_traj_unc) HIPCHK(hipMemcpy(out_traj_unc, d_tunc, sizeof(float) * n_traj, hipMemcpyDeviceToHost));
+    }
+    for (float* p : {d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact, d_tunc})
+        if (p) (void)hipFree(p);
+    for (int* p : {d_choice, d_tmodel})
+        if (p) (void)hipFree(p);
+}
+}  // namespace
+
 int fqlpop_rollout_ensemble(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
                             const float* noise, int mode, const int32_t* choice, float* out, float* out_obs) {
     return guard([&] {
-        ARGCHK(h && init_obs && out, "null argument");
-        ARGCHK(n_envs > 0 && max_steps > 0, "n_envs and max_steps must be positive");
-        ARGCHK(mode == FQLPOP_ENS_PER_MODEL || mode == FQLPOP_ENS_MIXED, "mode must be FQLPOP_ENS_PER_MODEL or FQLPOP_ENS_MIXED");
-        ARGCHK(!(choice && mode == FQLPOP_ENS_PER_MODEL), "choice is for FQLPOP_ENS_MIXED only");
-        if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
-        const int K = h->ens_n;
-        const size_t n_choice = (size_t)max_steps * n_envs;
-        if (choice)
-            for (size_t i = 0; i < n_choice; ++i)
-                ARGCHK(choice[i] >= 0 && choice[i] < K, "choice entries must be in [0, n_models)");
-        if (!rollout_supported(h->H, h->L, h->D, h->A))
-            throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
-        if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipStreamSynchronize(h->sM));
-        const int nz = h->nz, D = h->D, A = h->A;
-        if (nz == 0) return;
-        RolloutEnsArgs e{};
-        RolloutArgs& r = e.base;
-        r = h->ens_args;
-        r.params = h->params; r.P = h->P; r.os_off = h->os.off;
-        for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
-        r.D = D; r.A = A; r.L = h->L;
-        r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
-        r.nz = nz; r.slots = h->slots;
-        e.nets = h->ens_nets; e.n_models = K; e.mode = mode;
-        const size_t rows = (size_t)nz * (mode == FQLPOP_ENS_PER_MODEL ? K : 1) * n_envs;
-        const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
-        float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr;
-        int* d_choice = nullptr;
-        HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
-        HIPCHK(hipMalloc(&d_out, sizeof(float) * rows * 2));
-        HIPCHK(hipMemcpy(d_obs, init_obs, sizeof(float) * n_envs * D, hipMemcpyHostToDevice));
-        if (noise) {
-            HIPCHK(hipMalloc(&d_noise, sizeof(float) * n_noise));
-            HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
-        }
-        if (choice) {
-            HIPCHK(hipMalloc(&d_choice, sizeof(int) * n_choice));
-            HIPCHK(hipMemcpy(d_choice, choice, sizeof(int) * n_choice, hipMemcpyHostToDevice));
-        }
-        if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * rows * D));
-        r.init_obs = d_obs; r.noise = d_noise; r.out = d_out; r.out_obs = d_oobs;
-        e.choice = d_choice;
-        HIPCHK(hipEventRecord(h->ev_t0, h->sM));
-        launch_rollout_ens(e, h->sM);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev_t1, h->sM));
-        HIPCHK(hipStreamSynchronize(h->sM));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
-        h->ens_kernel_us = 1000.0 * ms;
-        HIPCHK(hipMemcpy(out, d_out, sizeof(float) * rows * 2, hipMemcpyDeviceToHost));
-        if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * rows * D, hipMemcpyDeviceToHost));
-        for (float* p : {d_obs, d_noise, d_out, d_oobs})
-            if (p) (void)hipFree(p);
-        if (d_choice) (void)hipFree(d_choice);
+        ens_run(h, init_obs, n_envs, max_steps, seed, noise, mode, choice, out, out_obs, nullptr, nullptr, nullptr,
+                nullptr);
+    });
+}
+
+int fqlpop_rollout_ensemble_record(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                                   const float* noise, int mode, const int32_t* choice, float* out, float* out_obs,
+                                   float* out_traj_obs, float* out_traj_act, int32_t* out_traj_model,
+                                   float* out_traj_unc) {
+    return guard([&] {
+        ARGCHK(out_traj_obs && out_traj_act, "null argument");
+        ens_run(h, init_obs, n_envs, max_steps, seed, noise, mode, choice, out, out_obs, out_traj_obs, out_traj_act,
+                out_traj_model, out_traj_unc);
     });
 }
 

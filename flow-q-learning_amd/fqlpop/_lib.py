@@ -158,6 +158,11 @@ _SIGS = {
                                                      ctypes.c_int64, _F, ctypes.c_int64]),
     "fqlpop_rollout_ensemble": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_int32), _F, _F]),
+    "fqlpop_rollout_ensemble_record": (ctypes.c_int, [_P, _F, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _F,
+                                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _F, _F, _F, _F,
+                                                      ctypes.POINTER(ctypes.c_int32), _F]),
+    "fqlpop_synth_collect_ensemble": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                     ctypes.POINTER(ctypes.c_int64), ctypes.c_float]),
     "fqlpop_rollout_ensemble_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "fqlpop_synth_create": (ctypes.c_int, [_P, ctypes.c_int64]),
     "fqlpop_synth_set_ratio": (ctypes.c_int, [_P, ctypes.c_float]),

@@ -418,7 +418,7 @@ class Population:
         self._ens_n = k
 
     def rollout_ensemble(self, init_obs, max_steps: int, seed: int = 0, mode: str = "per_model", noise=None,
-                         choice=None, return_obs: bool = False):
+                         choice=None, return_obs: bool = False, record: bool = False, uncertainty: bool = False):
         """World-model evaluation of every ACTIVE member under the ensemble in one launch
         (fqlpop_rollout_ensemble).  noise None or [n_active, max_steps, n_envs, act], shared
         by all models.
@@ -428,10 +428,21 @@ class Population:
         mode "mixed" (trajectory sampling): at step t env e steps under model
         choice[t - 1, e] (int [max_steps, n_envs]; None: drawn on the device from ``seed``,
         the same sequence for every member); returns (success, lengths) [n_active, n_envs].
-        With return_obs the observations after the last step follow."""
+        With return_obs the observations after the last step follow.
+
+        record (mixed only; fqlpop_rollout_ensemble_record) appends traj_obs
+        [n_active, max_steps, n_envs, obs], traj_act [.., act] as ``rollout(record=True)``
+        and traj_model (int32 [n_active, max_steps, n_envs]: the model of each step);
+        uncertainty (implies record) appends traj_unc (float32, same shape): the norm of the
+        ensemble's per-coordinate standard deviation of s' at that (s, a), for which every
+        step runs all K models.  All are 0 from an env's episode length on; the results
+        before them do not change."""
         modes = {"per_model": _lib.ENS_PER_MODEL, "mixed": _lib.ENS_MIXED}
         if mode not in modes:
             raise ValueError(f"mode must be 'per_model' or 'mixed', got {mode!r}")
+        record = bool(record or uncertainty)
+        if record and mode != "mixed":
+            raise ValueError("record / uncertainty need mode='mixed'")
         obs = _f32(init_obs).reshape(-1, self.cfg.obs_dim)
         n_envs = obs.shape[0]
         na = len(self.active_ids)
@@ -444,12 +455,23 @@ class Population:
         lead = (na, getattr(self, "_ens_n", 1)) if mode == "per_model" else (na,)
         out = np.zeros(lead + (n_envs, 2), dtype=np.float32)
         oobs = np.zeros(lead + (n_envs, self.cfg.obs_dim), dtype=np.float32) if return_obs else None
-        check(self.lib.fqlpop_rollout_ensemble(
-            self._h, fptr(obs), n_envs, int(max_steps), ctypes.c_uint64(int(seed) & (2**64 - 1)),
-            None if nz is None else fptr(nz), modes[mode],
-            None if ch is None else ch.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            fptr(out), None if oobs is None else fptr(oobs)))
-        return (out[..., 0], out[..., 1]) + ((oobs,) if return_obs else ())
+        args = (self._h, fptr(obs), n_envs, int(max_steps), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+                None if nz is None else fptr(nz), modes[mode],
+                None if ch is None else ch.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                fptr(out), None if oobs is None else fptr(oobs))
+        res = (out[..., 0], out[..., 1]) + ((oobs,) if return_obs else ())
+        if not record:
+            check(self.lib.fqlpop_rollout_ensemble(*args))
+            return res
+        tr = (na, int(max_steps), n_envs)
+        tobs = np.zeros(tr + (self.cfg.obs_dim,), dtype=np.float32)
+        tact = np.zeros(tr + (self.cfg.action_dim,), dtype=np.float32)
+        tmodel = np.zeros(tr, dtype=np.int32)
+        tunc = np.zeros(tr, dtype=np.float32) if uncertainty else None
+        check(self.lib.fqlpop_rollout_ensemble_record(
+            *args, fptr(tobs), fptr(tact), tmodel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            None if tunc is None else fptr(tunc)))
+        return res + (tobs, tact, tmodel) + ((tunc,) if uncertainty else ())
 
     def ensemble_kernel_us(self) -> float:
         """GPU time of the kernel of the last rollout_ensemble call (HIP events)."""
@@ -470,20 +492,31 @@ class Population:
         rows).  Holds from the next enqueued step on."""
         check(self.lib.fqlpop_synth_set_ratio(self._h, float(real_ratio)))
 
-    def collect(self, n_branches: int, horizon: int, seed: int, start_rows=None):
+    def collect(self, n_branches: int, horizon: int, seed: int, start_rows=None, ensemble: bool = False,
+                penalty: float = 0.0):
         """Branches of every ACTIVE member in the env model of ``set_env_model``, appended to
         its ring on the device (fqlpop_synth_collect): ``n_branches`` branches of at most
         ``horizon`` steps from rows of the training dataset -- ``start_rows`` (int
         [n_branches]) or drawn on the device from ``seed`` -- the same rows for every member.
-        Stream-ordered with ``step`` and ``clone_members``; returns without waiting."""
+        Stream-ordered with ``step`` and ``clone_members``; returns without waiting.
+
+        ensemble: the branches run under ``set_env_model_ensemble``'s models, a model drawn
+        per branch and step from ``seed`` (fqlpop_synth_collect_ensemble; ``set_env_model`` is
+        not needed).  penalty > 0 (ensemble only): rewards are lowered by penalty times the
+        ensemble's disagreement at that step (``rollout_ensemble(uncertainty=True)``)."""
         sr = None
         if start_rows is not None:
             sr = np.ascontiguousarray(np.asarray(start_rows, dtype=np.int64).reshape(-1))
             if sr.shape[0] != int(n_branches):
                 raise ValueError(f"start_rows needs {int(n_branches)} entries, got {sr.shape[0]}")
-        check(self.lib.fqlpop_synth_collect(
-            self._h, int(n_branches), int(horizon), ctypes.c_uint64(int(seed) & (2**64 - 1)),
-            None if sr is None else sr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        if not ensemble and float(penalty) != 0.0:
+            raise ValueError("penalty needs ensemble=True")
+        args = (self._h, int(n_branches), int(horizon), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+                None if sr is None else sr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        if ensemble:
+            check(self.lib.fqlpop_synth_collect_ensemble(*args, ctypes.c_float(float(penalty))))
+        else:
+            check(self.lib.fqlpop_synth_collect(*args))
 
     def synth_info(self, member: int) -> dict:
         """{"rows", "head", "appended"} of one member's ring; synchronises."""

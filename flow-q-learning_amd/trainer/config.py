@@ -46,13 +46,18 @@ class ModelRolloutConfig:
     ``interval`` updates, once a group has passed ``warmup`` updates, each member rolls
     ``branches`` branches of at most ``horizon`` steps in the task's env model into its
     ring of ``buffer_rows`` rows; the training minibatch takes the share ``real_ratio`` of
-    its rows from the offline data and the rest from the ring."""
+    its rows from the offline data and the rest from the ring.  With ``ensemble`` the
+    branches run under the task's env-model ensemble, a model drawn per branch and step
+    (trajectory sampling), and ``penalty`` > 0 lowers a synthetic reward by that factor
+    times the ensemble's disagreement about the step (a MOPO-style uncertainty penalty)."""
     branches: int = 0
     horizon: int = 5
     interval: int = 1000
     warmup: int = 0
     real_ratio: float = 0.5
     buffer_rows: int = 100_000
+    ensemble: bool = False
+    penalty: float = 0.0
 
     @property
     def enabled(self) -> bool:
@@ -65,6 +70,11 @@ class ModelRolloutConfig:
             raise ValueError("model rollouts need horizon >= 1, interval >= 1 and warmup >= 0")
         if not 0.0 <= self.real_ratio <= 1.0:
             raise ValueError(f"model_real_ratio must be in [0, 1], got {self.real_ratio}")
+        if not self.penalty >= 0.0 or self.penalty == float("inf"):
+            raise ValueError(f"model_rollout_penalty must be finite and >= 0, got {self.penalty}")
+        if self.penalty > 0.0 and not self.ensemble:
+            raise ValueError("model_rollout_penalty needs --model_rollout_ensemble: the penalty is the "
+                             "ensemble's disagreement")
         if self.branches * self.horizon > self.buffer_rows:
             raise ValueError(f"model_buffer_rows {self.buffer_rows} holds less than one collect "
                              f"({self.branches} branches x {self.horizon} steps)")

@@ -44,6 +44,9 @@ MODEL_ROLLOUT_DISTRIBUTED_MSG = ("training on world-model branches (--model_roll
 MODEL_ROLLOUT_TASK_MSG = ("training on world-model branches (--model_rollout_branches) needs a task that can attach "
                           "an env model to the population: OfflineTaskWithSimulatedEvaluations (--task simulated); "
                           "got {task}")
+MODEL_ROLLOUT_ENSEMBLE_MSG = ("branches under the env-model ensemble (--model_rollout_ensemble) need a task with an "
+                              "ensemble: OfflineTaskWithSimulatedEvaluations(env_models=... or ensemble_size=K) "
+                              "(--env_model_ensemble K); this task has one env model")
 LINEAGE_COLUMNS = ("round", "step", "child", "parent", "parent_alpha", "child_alpha", "parent_score")
 
 
@@ -65,6 +68,8 @@ class Trainer:
             if not isinstance(task, OfflineTaskWithSimulatedEvaluations):
                 raise ValueError(MODEL_ROLLOUT_TASK_MSG.format(task=type(task).__name__))
             self.model_rollouts.validate()
+            if self.model_rollouts.ensemble and task.env_models is None:
+                raise ValueError(MODEL_ROLLOUT_ENSEMBLE_MSG)
         # a strategy that exposes parent_of (PopulationBasedTraining) refills the slots of the
         # candidates it drops with clones of others; everything below keyed on _clones is new
         # ground, and Identity / SuccessiveHalving runs take none of it
@@ -189,7 +194,8 @@ class Trainer:
             train_population(exps, nxt - cur)  # (leaves exactly this group active)
             cur = nxt
             if cur % mr.interval == 0 and cur >= mr.warmup and cur < self.config.steps:
-                self.population.collect(mr.branches, mr.horizon, D.collect_seed(self.config.seed, self.collect_index))
+                self.population.collect(mr.branches, mr.horizon, D.collect_seed(self.config.seed, self.collect_index),
+                                        ensemble=mr.ensemble, penalty=mr.penalty)
                 self.collect_index += 1
 
     def _evaluate_round(self, configs) -> dict:

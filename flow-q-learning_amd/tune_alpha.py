@@ -18,6 +18,9 @@ Training on world-model branches (--task simulated, one GPU): --model_rollout_br
 [--model_real_ratio R] [--model_buffer_rows C]: every I updates each member rolls N branches
 of H steps in the env model into its own on-device ring, and its minibatches take the share
 R from the offline data, the rest from the ring (trainer/trainer.py; off by default).
+--env_model_ensemble 5 --model_rollout_ensemble --model_rollout_penalty 1.0
+runs the branches under the K-model ensemble instead (a model drawn per branch and step) and
+lowers every synthetic reward by the penalty times the models' disagreement about that step.
 
 Multi-GPU (BASELINE configs 4 / 5): launched by torch.distributed.run with one
 process per GPU (``python -m torch.distributed.run --nproc-per-node 8

@@ -373,6 +373,26 @@ int fqlpop_set_env_model_ensemble(fqlpop_t* h, const fqlpop_envmodel_config* cfg
 int fqlpop_rollout_ensemble(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
                             const float* noise, int mode, const int32_t* choice, float* out, float* out_obs);
 
+/* fqlpop_rollout_ensemble in FQLPOP_ENS_MIXED with the transitions and the ensemble's
+ * disagreement recorded.  out_traj_obs [n_active][max_steps][n_envs][obs_dim] and
+ * out_traj_act [..][action_dim] (both required) are fqlpop_rollout_record's: entry [t] of an
+ * env is the observation before its step t + 1 and the clipped action taken there.  Optional
+ * (NULL or host [n_active][max_steps][n_envs]):
+ *   out_traj_model  int32: the model the env stepped under at that step;
+ *   out_traj_unc    u = sqrt(max(0, Q / K - |m|^2 / K^2)) with s'_k model k's next observation
+ *                   from that (s, a), r_k = s'_k - s'_0, Q = sum_k |r_k|^2, m = sum_k r_k and
+ *                   K = n_models: the norm of the ensemble's per-coordinate standard deviation
+ *                   of s'.  Exactly 0 when the models' predictions are bitwise equal.  With
+ *                   it, every step runs all n_models models, not only the chosen ones.
+ * All four are zero where an env did not run the step.  out / out_obs are bit for bit
+ * fqlpop_rollout_ensemble's for the same arguments, with or without out_traj_unc.  Errors
+ * as there, plus FQLPOP_E_ARG for FQLPOP_ENS_PER_MODEL or a NULL out_traj_obs /
+ * out_traj_act.  Synchronises.  [no reference counterpart] */
+int fqlpop_rollout_ensemble_record(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint64_t seed,
+                                   const float* noise, int mode, const int32_t* choice, float* out, float* out_obs,
+                                   float* out_traj_obs, float* out_traj_act, int32_t* out_traj_model,
+                                   float* out_traj_unc);
+
 /* GPU time of the kernel of the last successful fqlpop_rollout_ensemble call on this
  * handle, in microseconds (HIP events around the launch, as fqlpop_envmodel_replay_time).
  * FQLPOP_E_STATE before the first call.  [no reference counterpart] */
@@ -428,6 +448,22 @@ int fqlpop_synth_set_ratio(fqlpop_t* h, float real_ratio);
  * FQLPOP_E_ARG for n_branches < 1, horizon < 1 (or > 65535), n_branches * horizon > capacity
  * (or >= 2^31) or a start row out of range.  No active member: succeeds and does nothing. */
 int fqlpop_synth_collect(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows);
+
+/* fqlpop_synth_collect with the branches run under fqlpop_set_env_model_ensemble's models
+ * (trajectory sampling) instead of fqlpop_set_env_model's, which it does not need:
+ *   branch  exactly fqlpop_rollout_ensemble_record(init_obs = those rows, n_envs = n_branches,
+ *           max_steps = horizon, seed, noise = NULL, FQLPOP_ENS_MIXED, choice = NULL): the same
+ *           launch on device buffers, so every member meets the same model sequence.  A
+ *           branch's last s_{t+1} is the env's own (a finished env is never merged with its
+ *           tile-mates there).
+ *   penalty 0: only the chosen models run and the rows are as above.  > 0: every step runs
+ *           all models and a row's reward is r - penalty * u with u that step's out_traj_unc
+ *           (a MOPO-style uncertainty penalty); m and every other field are unchanged.
+ * Starts, rows, order, stream order and the errors are fqlpop_synth_collect's, with
+ * FQLPOP_E_STATE "no env model ensemble set" for its "no env model set", plus FQLPOP_E_ARG
+ * for a negative or non-finite penalty; all before any launch. */
+int fqlpop_synth_collect_ensemble(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, const int64_t* start_rows,
+                                  float penalty);
 
 /* The counters of one member's ring (any may be NULL); synchronises. */
 int fqlpop_synth_info(fqlpop_t* h, int member, int64_t* rows, int64_t* head, int64_t* appended);
