@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/fqlpop.h"
+#include "emboot.h"
 #include "hostmem.h"
 #include "kernels.h"
 
@@ -125,6 +126,15 @@ struct StepArgs {
     long long seq_stride;
     int tchunks;                        // sweep path: T chunks of the dW GEMM (partials per block)
     unsigned long long* probe;          // diagnostic builds only (FQLPOP_EM_PROBE): sweep phase times
+    // device-sampled launches only (em_unit): null, or model 0's table of units, tab_stride
+    // entries (n_units) per model.  Training: the bootstrap table.  oob_eval
+    // (fqlpop_emtrain_eval_oob): the out-of-bag list, n_oob[model] long, for batch oob_batch of
+    // the call's draw oob_draw.  (Behind every earlier field, whose offsets the kernels keep.)
+    const long long* tab;
+    long long tab_stride;
+    const long long* n_oob;
+    int oob_eval;
+    uint32_t oob_batch, oob_draw;
 };
 
 // ----------------------------------------------------------------- Philox
@@ -145,6 +155,11 @@ DEV float urand(uint64_t seed, uint32_t a, uint32_t b, uint32_t c) {
     philox(x, (uint32_t)seed, (uint32_t)(seed >> 32));
     return (x[0] >> 8) * (1.0f / 16777216.0f);
 }
+
+// Counter word 2 of the unit draws: a minibatch row, a multistep episode (the VAE section lists
+// its own); a bootstrap table entry and an out-of-bag unit (include/fqlpop.h)
+constexpr uint32_t SALT_ROW = 0xE7u, SALT_EP = 0xE5u;
+constexpr uint32_t SALT_BOOT = FQLPOP_EM_SALT_BOOT, SALT_OOB = FQLPOP_EM_SALT_OOB;
 
 DEV float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
@@ -357,8 +372,9 @@ struct ModelView {
     float *part, *logs, *seq;
     const float *obs, *act, *rew, *nobs;
     const unsigned char* keep;
+    const long long* tab;
     uint64_t seed;
-    int blk;
+    int blk, model;
 };
 DEV bool ens_enter(const StepArgs& a, ModelView& m) {
     const EnsAxis& e = a.ens;
@@ -384,6 +400,8 @@ DEV bool ens_enter(const StepArgs& a, ModelView& m) {
         if (model < 0) return false;  // padding of the XCD placement
     }
     m.blk = blk;
+    m.model = model;
+    m.tab = a.tab ? a.tab + model * a.tab_stride : nullptr;
     m.params = a.params + model * e.par;
     m.wt = a.wt + model * e.par;
     m.part = a.part + model * e.part;
@@ -397,6 +415,22 @@ DEV bool ens_enter(const StepArgs& a, ModelView& m) {
     m.seed = e.seeds[0];  // (with the other arguments; a later model's is one more scalar load)
     if (model > 0) m.seed = e.seeds[model];
     return true;
+}
+
+// The unit (dataset row, or episode of the multistep model) of batch position gr in a
+// device-sampled launch; *c2: the counter's third word (the multistep window start).  The index
+// u = (x1 << 32 | x0) mod n_units is the unit itself without a table (a handle without
+// bootstrap: the draw as it always was), else the table's entry u.  An out-of-bag evaluation
+// draws from its own counter, over the model's list.  Every condition is block-uniform.
+DEV long long em_unit(const StepArgs& a, const ModelView& m, int gr, uint32_t salt, long long n_units, uint32_t* c2) {
+    const bool ev = a.oob_eval != 0;
+    uint32_t c[4] = {(uint32_t)gr, ev ? a.oob_batch : (uint32_t)a.step, ev ? SALT_OOB : salt, ev ? a.oob_draw : 0u};
+    philox(c, (uint32_t)m.seed, (uint32_t)(m.seed >> 32));
+    *c2 = c[2];
+    const uint64_t v = ((uint64_t)c[1] << 32) | c[0];
+    if (!m.tab) return (long long)(v % (uint64_t)n_units);
+    const long long n = ev ? a.n_oob[m.model] : n_units;
+    return m.tab[v % (uint64_t)n];
 }
 
 __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
@@ -433,9 +467,8 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
         const int gr = blk * R + tid;
         long long id = gr;
         if (!a.injected) {
-            uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE7u, 0u};
-            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
-            id = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)a.n_rows);
+            uint32_t c2;
+            id = em_unit(a, mv, gr, SALT_ROW, a.n_rows, &c2);
         }
         rowid[tid] = id;
         lab[tid] = mv.rew[id] == 0.f ? 1.f : 0.f;
@@ -621,11 +654,9 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
         const int gr = blk * R + tid;
         long long base = (long long)gr * T;
         if (!a.injected) {
-            uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE5u, 0u};
-            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
-            const long long n_ep = a.n_rows / a.ep_len;
-            const long long ep = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)n_ep);
-            const long long st = (long long)(c[2] % (uint32_t)(a.ep_len - T));
+            uint32_t c2;
+            const long long ep = em_unit(a, mv, gr, SALT_EP, a.n_rows / a.ep_len, &c2);
+            const long long st = (long long)(c2 % (uint32_t)(a.ep_len - T));
             base = ep * a.ep_len + st;
         }
         rowbase[tid] = base;
@@ -1054,11 +1085,9 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         const int gr = blk * R + tid;
         long long base = (long long)gr * T;
         if (!a.injected) {  // MultistepLoader windows, as em_seq_grad_kernel
-            uint32_t c[4] = {(uint32_t)gr, (uint32_t)a.step, 0xE5u, 0u};
-            philox(c, (uint32_t)mv.seed, (uint32_t)(mv.seed >> 32));
-            const long long n_ep = a.n_rows / a.ep_len;
-            const long long ep = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)n_ep);
-            const long long st = (long long)(c[2] % (uint32_t)(a.ep_len - T));
+            uint32_t c2;
+            const long long ep = em_unit(a, mv, gr, SALT_EP, a.n_rows / a.ep_len, &c2);
+            const long long st = (long long)(c2 % (uint32_t)(a.ep_len - T));
             base = ep * a.ep_len + st;
         }
         rowbase[tid] = base;
@@ -1455,6 +1484,135 @@ __global__ __launch_bounds__(256) void em_adam_kernel(const AdamArgsEm a) {
     }
 }
 
+// ------------------------------------------------ bootstrap tables (set-up) --
+// Once per fqlpop_emtrain_set_bootstrap*, for all K models at a time: fill (grid.y = model),
+// mark (likewise), compact (one block per model).  Nothing here is on the step's path.
+struct BootArgs {
+    long long* table;                   // [K][n]
+    unsigned char* seen;                // [K][n]
+    long long n;                        // n_units
+    uint64_t seeds[ENS_MAX];
+};
+
+// table[k][i] = (x1 << 32 | x0) mod n of Philox(key seeds[k], counter (lo32 i, hi32 i, SALT_BOOT, 0))
+__global__ __launch_bounds__(256) void em_boot_fill_kernel(const BootArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const uint64_t seed = a.seeds[blockIdx.y];
+    uint32_t c[4] = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32), SALT_BOOT, 0u};
+    philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    a.table[blockIdx.y * a.n + i] = (long long)((((uint64_t)c[1] << 32) | c[0]) % (uint64_t)a.n);
+}
+
+// seen[k][table[k][i]] = 1 (seen starts zeroed).  Every writer of a byte stores the same value,
+// so the stores need no order among themselves.  Table entries are in [0, n): drawn mod n, or
+// checked by the host before the upload.
+__global__ __launch_bounds__(256) void em_oob_mark_kernel(const BootArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const long long base = blockIdx.y * a.n;
+    a.seen[base + a.table[base + i]] = 1;
+}
+
+// oob[k] = the units with seen[k][.] == 0, ascending; n_oob[k] = how many.  One block per model
+// walks the units in chunks of OOB_NT x OOB_PER; a thread owns OOB_PER neighbours, and a
+// block-wide exclusive scan of the threads' counts (wave scan, then the wave totals) places
+// them.  At most n entries are written: the list cannot be longer than the units.
+constexpr int OOB_NT = 1024, OOB_PER = 4;
+__global__ __launch_bounds__(OOB_NT) void em_oob_compact_kernel(const unsigned char* seen, long long* oob,
+                                                                 long long* n_oob, long long n) {
+    __shared__ int wsum[OOB_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    seen += blockIdx.x * n;
+    oob += blockIdx.x * n;
+    long long base = 0;  // (every thread keeps the same count)
+    for (long long c0 = 0; c0 < n; c0 += OOB_NT * OOB_PER) {
+        const long long i0 = c0 + (long long)tid * OOB_PER;
+        bool out[OOB_PER];
+        int cnt = 0;
+#pragma unroll
+        for (int q = 0; q < OOB_PER; ++q) {
+            out[q] = i0 + q < n && seen[i0 + q] == 0;
+            cnt += out[q] ? 1 : 0;
+        }
+        int inc = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+        }
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int j = 0; j < OOB_NT / 64; ++j) {
+            const int s = wsum[j];
+            if (j < w) before += s;
+            total += s;
+        }
+        long long o = base + before + inc - cnt;
+#pragma unroll
+        for (int q = 0; q < OOB_PER; ++q)
+            if (out[q]) oob[o++] = i0 + q;
+        base += total;
+        __syncthreads();  // wsum is rewritten by the next chunk
+    }
+    if (tid == 0) n_oob[blockIdx.x] = base;
+}
+
+// One model's logs [FQLPOP_EM_LOG_STRIDE] from its per-block sums lg (layout: include/fqlpop.h).
+// On the host for the log reads, on the device for fqlpop_emtrain_eval_oob: the same double
+// arithmetic, every product and sum rounded on its own, so the two agree to the bit.
+struct LogShape {
+    int blocks, kind;
+    double B, D, tw;                    // scored predictions, obs_dim, termination_weight
+};
+__host__ __device__ inline void em_logs_calc(const LogShape& h, const float* lg, float* out) {
+#pragma clang fp contract(off)
+    double s[NLOG] = {0};
+    for (int b = 0; b < h.blocks; ++b)
+        for (int k = 0; k < NLOG; ++k) s[k] += lg[(size_t)b * NLOG + k];
+    const double B = h.B, D = h.D;
+    for (int k = 0; k < FQLPOP_EM_LOG_STRIDE; ++k) out[k] = 0.f;
+    if (h.kind != FQLPOP_EM_TERMINATION) {
+        const double mse = s[0] / (B * D), tw = h.tw;
+        const double tl = tw > 0 ? s[1] / B : 0.0;
+        out[0] = (float)((mse + tw * tl) / (1.0 + tw));
+        out[1] = (float)mse;
+        out[2] = (float)tl;
+        out[3] = (float)(s[4] > 0 ? s[2] / s[4] : NAN);
+        out[4] = (float)(s[5] > 0 ? s[3] / s[5] : NAN);
+    } else {
+        out[0] = (float)(s[1] / B);
+        out[1] = (float)(s[2] / (s[4] + 1e-8));
+        out[2] = (float)(s[3] / (s[5] + 1e-8));
+        out[3] = (float)(s[6] / B);
+        out[4] = (float)(s[8] > 0 ? s[7] / s[8] : 1.0);
+        out[5] = (float)(s[4] > 0 ? s[7] / s[4] : 1.0);
+    }
+}
+
+// fqlpop_emtrain_eval_oob, after batch j of n: thread k adds model k's logs of that batch to
+// acc[k] (float32, in batch order) and divides by n after the last.
+struct OobAccArgs {
+    LogShape shape;
+    const float* logs;                  // [K][blocks][NLOG] block sums of the batch just run
+    long long ens_logs;
+    float* acc;                         // [K][FQLPOP_EM_LOG_STRIDE]
+    int K, j, n;
+};
+__global__ __launch_bounds__(64) void em_oob_acc_kernel(const OobAccArgs a) {
+    const int k = threadIdx.x;
+    if (k >= a.K) return;
+    float out[FQLPOP_EM_LOG_STRIDE];
+    em_logs_calc(a.shape, a.logs + k * a.ens_logs, out);
+    float* acc = a.acc + k * FQLPOP_EM_LOG_STRIDE;
+    for (int i = 0; i < FQLPOP_EM_LOG_STRIDE; ++i) {
+        float v = a.j == 0 ? out[i] : acc[i] + out[i];
+        if (a.j == a.n - 1) v /= (float)a.n;
+        acc[i] = v;
+    }
+}
+
 }  // namespace em
 }  // namespace fq
 
@@ -1524,6 +1682,7 @@ struct fqlpop_emtrain {
         DevBuf<float> obs, act, rew, nobs;
         long long rows = 0;
     } data;
+    EmBootTables<> boot;                  // bootstrap tables over the dataset's units (empty: off)
     DevBuf<float> i_obs, i_act, i_rew, i_nobs;
     DevBuf<unsigned char> i_keep;
     long long count = 0;
@@ -1792,7 +1951,7 @@ int fqlpop_emtrain_set_dataset(fqlpop_emtrain_t* h, const float* obs, const floa
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->s));
         const long long D = h->cfg.obs_dim, A = h->cfg.action_dim;
-        replace_released(h->data, [&] {
+        replace_dataset(h->data, h->boot, [&] {
             fqlpop_emtrain::Data d;
             d.obs = DevBuf<float>(n_rows * D, "env-model dataset");
             d.act = DevBuf<float>(std::max(1LL, n_rows * A), "env-model dataset");
@@ -1838,6 +1997,10 @@ static StepArgs em_args(fqlpop_emtrain* h, bool train, bool injected, bool share
     } else {
         a.obs = h->data.obs; a.act = h->data.act; a.rew = h->data.rew; a.nobs = h->data.nobs;
         a.n_rows = h->data.rows;
+        if (h->boot) {
+            a.tab = h->boot.table;
+            a.tab_stride = h->boot.n_units;
+        }
     }
     a.step = h->count;
     a.B = c.batch_size; a.D = c.obs_dim; a.A = c.action_dim;
@@ -1972,28 +2135,12 @@ int fqlpop_emtrain_step_injected_ensemble(fqlpop_emtrain_t* h, const float* obs,
 }
 
 // one model's logs [FQLPOP_EM_LOG_STRIDE] from its per-block sums lg (layout: include/fqlpop.h)
+static LogShape em_log_shape(const fqlpop_emtrain* h) {
+    return LogShape{h->blocks, h->cfg.kind, (double)h->cfg.batch_size * h->T, (double)h->cfg.obs_dim,
+                    (double)h->cfg.termination_weight};
+}
 static void em_logs_model(const fqlpop_emtrain* h, const float* lg, float* out) {
-    double s[NLOG] = {0};
-    for (int b = 0; b < h->blocks; ++b)
-        for (int k = 0; k < NLOG; ++k) s[k] += lg[(size_t)b * NLOG + k];
-    const double B = (double)h->cfg.batch_size * h->T, D = h->cfg.obs_dim;  // scored predictions
-    for (int k = 0; k < FQLPOP_EM_LOG_STRIDE; ++k) out[k] = 0.f;
-    if (h->cfg.kind != FQLPOP_EM_TERMINATION) {
-        const double mse = s[0] / (B * D), tw = h->cfg.termination_weight;
-        const double tl = tw > 0 ? s[1] / B : 0.0;
-        out[0] = (float)((mse + tw * tl) / (1.0 + tw));
-        out[1] = (float)mse;
-        out[2] = (float)tl;
-        out[3] = (float)(s[4] > 0 ? s[2] / s[4] : NAN);
-        out[4] = (float)(s[5] > 0 ? s[3] / s[5] : NAN);
-    } else {
-        out[0] = (float)(s[1] / B);
-        out[1] = (float)(s[2] / (s[4] + 1e-8));
-        out[2] = (float)(s[3] / (s[5] + 1e-8));
-        out[3] = (float)(s[6] / B);
-        out[4] = (float)(s[8] > 0 ? s[7] / s[8] : 1.0);
-        out[5] = (float)(s[4] > 0 ? s[7] / s[4] : 1.0);
-    }
+    em_logs_calc(em_log_shape(h), lg, out);
 }
 // logs [K][FQLPOP_EM_LOG_STRIDE]: one copy and one synchronisation for all K models
 static void em_logs(fqlpop_emtrain* h, float* out) {
@@ -2083,6 +2230,130 @@ int fqlpop_emtrain_sync(fqlpop_emtrain_t* h) {
     return em_guard([&] {
         ARGCHK(h, "null handle");
         HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------- bootstrap ABI --
+static long long em_n_units(const fqlpop_emtrain* h) {
+    return h->cfg.kind == FQLPOP_EM_MULTISTEP ? h->data.rows / h->cfg.episode_length : h->data.rows;
+}
+
+// Fresh tables for the handle's dataset: `table` ([K][n_units], checked by the caller) uploaded,
+// or drawn on the device when null; then the out-of-bag lists and their host-side counts.
+static EmBootTables<> em_boot_build(fqlpop_emtrain* h, const int64_t* table) {
+    static_assert(sizeof(int64_t) == sizeof(long long), "the tables are int64 on both sides of the ABI");
+    const long long n = em_n_units(h);
+    const int K = h->K;
+    EmBootTables<> b = EmBootTables<>::make(K, n);
+    BootArgs a{};
+    a.table = b.table;
+    a.seen = b.seen;
+    a.n = n;
+    for (int k = 0; k < K; ++k) a.seeds[k] = h->seeds[k];
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)K);
+    if (table) {
+        HIPCHK(hipMemcpyAsync(b.table, table, 8 * (size_t)K * n, hipMemcpyHostToDevice, h->s));
+    } else {
+        hipLaunchKernelGGL(em_boot_fill_kernel, grid, dim3(256), 0, h->s, a);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemsetAsync(b.seen, 0, (size_t)K * n, h->s));
+    HIPCHK(hipMemsetAsync(b.oob, 0, 8 * (size_t)K * n, h->s));
+    hipLaunchKernelGGL(em_oob_mark_kernel, grid, dim3(256), 0, h->s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(em_oob_compact_kernel, dim3((unsigned)K), dim3(OOB_NT), 0, h->s, b.seen.get(), b.oob.get(),
+                       b.n_oob.get(), n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b.n_oob_h, b.n_oob, 8 * (size_t)K, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(hipStreamSynchronize(h->s));  // (also: the caller's table may be reused)
+    return b;
+}
+
+extern "C" {
+
+int fqlpop_emtrain_set_bootstrap(fqlpop_emtrain_t* h, int enable) {
+    return em_guard([&] {
+        ARGCHK(h, "null handle");
+        ARGCHK(enable == 0 || enable == 1, "enable must be 0 or 1");
+        if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));  // the current tables' last reader has run
+        if (!enable) {
+            h->boot = EmBootTables<>{};
+            return;
+        }
+        replace_built(h->boot, [&] { return em_boot_build(h, nullptr); });
+    });
+}
+
+int fqlpop_emtrain_set_bootstrap_table(fqlpop_emtrain_t* h, const int64_t* table, int64_t n) {
+    return em_guard([&] {
+        ARGCHK(h && table, "null argument");
+        if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
+        const long long nu = em_n_units(h);
+        ARGCHK(n == nu * h->K, "bootstrap table size mismatch: n must be n_models * n_units");
+        for (int64_t i = 0; i < n; ++i)
+            if (table[i] < 0 || table[i] >= nu)
+                throw Err{FQLPOP_E_ARG, "bootstrap table entry " + std::to_string(i) + " (" + std::to_string(table[i]) +
+                                            ") is outside [0, " + std::to_string(nu) + ")"};
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->s));
+        replace_built(h->boot, [&] { return em_boot_build(h, table); });
+    });
+}
+
+int fqlpop_emtrain_get_bootstrap(fqlpop_emtrain_t* h, int model, int64_t* table, int64_t n_units, int64_t* oob,
+                                 int64_t oob_cap, int64_t* n_oob) {
+    return em_guard([&] {
+        ARGCHK(h && table && n_oob, "null argument");
+        if (!h->boot) throw Err{FQLPOP_E_STATE, "no bootstrap tables: call fqlpop_emtrain_set_bootstrap"};
+        ARGCHK(model >= 0 && model < h->K, "model index out of range");
+        ARGCHK(n_units == h->boot.n_units, "n_units mismatch");
+        const long long no = h->boot.n_oob_h[model];
+        ARGCHK(!oob || oob_cap >= no, "oob_cap is smaller than the model's out-of-bag list");
+        HIPCHK(hipSetDevice(h->device));
+        const long long off = (long long)model * n_units;
+        HIPCHK(hipMemcpyAsync(table, h->boot.table + off, 8 * (size_t)n_units, hipMemcpyDeviceToHost, h->s));
+        if (oob && no > 0) HIPCHK(hipMemcpyAsync(oob, h->boot.oob + off, 8 * (size_t)no, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(hipStreamSynchronize(h->s));
+        *n_oob = no;
+    });
+}
+
+int fqlpop_emtrain_eval_oob(fqlpop_emtrain_t* h, int n_batches, uint64_t draw, float* logs) {
+    return em_guard([&] {
+        ARGCHK(h && logs, "null argument");
+        ARGCHK(n_batches >= 1, "n_batches must be >= 1");
+        if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
+        if (!h->boot) throw Err{FQLPOP_E_STATE, "no bootstrap tables: call fqlpop_emtrain_set_bootstrap"};
+        for (int k = 0; k < h->K; ++k)
+            if (h->boot.n_oob_h[k] == 0)
+                throw Err{FQLPOP_E_STATE, "model " + std::to_string(k) + " has no out-of-bag unit: its table holds every one"};
+        em_check_ready(h);
+        HIPCHK(hipSetDevice(h->device));
+        StepArgs a = em_args(h, false, false);
+        a.tab = h->boot.oob;
+        a.n_oob = h->boot.n_oob;
+        a.oob_eval = 1;
+        a.oob_draw = (uint32_t)draw;
+        OobAccArgs r{};
+        r.shape = em_log_shape(h);
+        r.logs = h->logs;
+        r.ens_logs = h->s_logs;
+        r.acc = h->boot.acc;
+        r.K = h->K;
+        r.n = n_batches;
+        for (int j = 0; j < n_batches; ++j) {
+            a.oob_batch = (uint32_t)j;
+            em_launch_step(h, a);
+            r.j = j;
+            hipLaunchKernelGGL(em_oob_acc_kernel, dim3(1), dim3(64), 0, h->s, r);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(logs, h->boot.acc, 4 * (size_t)h->K * FQLPOP_EM_LOG_STRIDE, hipMemcpyDeviceToHost, h->s));
         HIPCHK(hipStreamSynchronize(h->s));
     });
 }

@@ -4,7 +4,7 @@ shapes (obs 28, act 5, hidden (128, 256, 128), B = 256).
 
   python emtrain_ens_time.py [--kinds sp0,sp1,tp,ms0,ms1] [--K 1,2,5,8,16] [--steps 2000]
                              [--ms_steps 30] [--T 256] [--reps 1] [--single_only] [--train_loop 0]
-                             [--root TREE] [--label NAME]
+                             [--root TREE] [--label NAME] [--bootstrap] [--oob N] [--rows N]
 
 kinds: sp0 / sp1 the state predictor with termination_weight 0 / 1, tp the termination
 predictor, ms0 / ms1 the multistep model at sequence length T.  Every timed region is
@@ -20,7 +20,10 @@ end, after a warm-up of the same handle, so no host log read hides the kernels. 
 --root it measures another checkout of the project (its package and its libfqlpop.so), e.g.
 the parent commit as the baseline.  --train_loop N also times ``train()`` itself (N steps
 with the per-step log read and a logger per model) for the loop and for the default
-placement at every K asked for.  One JSON line per (kind, K, path, rep) with ms per step,
+placement at every K asked for.  --bootstrap creates every trainer with ``bootstrap=True`` (each
+model draws through its own resample table); --oob N also times, on one K-model trainer, the
+one-off table set-up (``what = boot_setup``), ``eval_oob(N)`` (``oob_eval``) and N host-loader
+``eval_step``s (``host_eval``); --rows sets the dataset size (200 000).  One JSON line per (kind, K, path, rep) with ms per step,
 model-steps/s and the GPU's clocks right after the timed region.
 """
 import argparse
@@ -41,6 +44,9 @@ ap.add_argument("--train_loop", type=int, default=0)
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(
     os.path.abspath(__file__))))))
 ap.add_argument("--label", default="")
+ap.add_argument("--bootstrap", action="store_true")
+ap.add_argument("--oob", type=int, default=0)
+ap.add_argument("--rows", type=int, default=200_000)
 args = ap.parse_args()
 sys.path[:0] = [args.root, os.path.join(args.root, "flow-q-learning_amd")]
 import numpy as np  # noqa: E402
@@ -51,7 +57,8 @@ import train_env_model as tem  # noqa: E402
 from envmodel import trainer as et  # noqa: E402
 
 D, A, B = 28, 5, 256
-data = bench.synthetic_dataset(200_000, D, A)
+data = bench.synthetic_dataset(args.rows, D, A)
+BOOT = {"bootstrap": True} if args.bootstrap else {}  # (another checkout's trainers may not take it)
 DS = {k: np.asarray(data[k], np.float32) for k in ("observations", "actions", "rewards", "next_observations")}
 SPEC = em.EnvModelSpec(D, A)
 TP = em.init_termination_predictor(SPEC, 1)
@@ -73,14 +80,15 @@ def make(kind, seeds, loggers=None, single=False, n=None):
     if single:
         if kind == "tp":
             return et.TerminationPredictorTrainer(SPEC, em.init_termination_predictor(SPEC, seeds[0]), *loaders, cfg,
-                                                  logger=loggers[0] if loggers else None)
+                                                  logger=loggers[0] if loggers else None, **BOOT)
         return et.StatePredictorTrainer(SPEC, em.init_state_predictor(SPEC, seeds[0]), *loaders, cfg,
-                                        logger=loggers[0] if loggers else None, tp_params=TP if tw > 0 else None)
+                                        logger=loggers[0] if loggers else None, tp_params=TP if tw > 0 else None,
+                                        **BOOT)
     if kind == "tp":
         return et.TerminationPredictorEnsembleTrainer(SPEC, [em.init_termination_predictor(SPEC, s) for s in seeds],
-                                                      *loaders, cfg, seeds, loggers=loggers)
+                                                      *loaders, cfg, seeds, loggers=loggers, **BOOT)
     return et.StatePredictorEnsembleTrainer(SPEC, [em.init_state_predictor(SPEC, s) for s in seeds], *loaders, cfg,
-                                            seeds, loggers=loggers, tp_params=TP if tw > 0 else None)
+                                            seeds, loggers=loggers, tp_params=TP if tw > 0 else None, **BOOT)
 
 
 def timed_steps(tr, n):
@@ -122,6 +130,24 @@ for kind in args.kinds.split(","):
                 sec = timed_steps(tr, n)
                 tr.close()
                 emit(kind, K, f"ens{xcd}", rep, n, sec)
+        if args.oob and not args.single_only:
+            # out-of-bag evaluation on the device against the host loader's eval batches
+            from fqlpop import reset_engine_options
+            reset_engine_options()
+            tr = make(kind, seeds)
+            tr.steps(2)
+            tr.sync()
+            t0 = time.perf_counter()
+            tr.set_bootstrap(True)  # (synchronises)
+            emit(kind, K, "ens", 0, 1, time.perf_counter() - t0, what="boot_setup")
+            for what, run in (("oob_eval", lambda: tr.eval_oob(args.oob, 1)),
+                              ("host_eval", lambda: [tr.eval_step(None, [tr._sample(tr.val_loader, k) for k in range(K)])
+                                                     for _ in range(args.oob)])):
+                run()  # warm-up
+                t0 = time.perf_counter()
+                run()
+                emit(kind, K, "ens", 0, args.oob, time.perf_counter() - t0, what=what)
+            tr.close()
         if args.train_loop:
             # train() itself: the val passes, one update and one log read per step, K log rows
             for path in ("loop",) if args.single_only else ("loop", "ens"):

@@ -14,6 +14,13 @@ that differ only in seed behind one handle (``fqlpop_emtrain_create_ensemble``):
 launches with a model axis, model k bitwise the single trainer of seed k [no reference
 counterpart: the reference loops over its trainer].
 
+``bootstrap=True`` on any of the four trainers (PETS / MBPO / MOPO) gives every model its own
+resample of the dataset's units -- rows, or episodes of the multistep model -- drawn on the
+device from the model's seed (``fqlpop_emtrain_set_bootstrap``): ``bootstrap_table(k)`` and
+``oob_rows(k)`` read it back, ``eval_oob(n_batches, draw)`` evaluates each model on the units
+its resample missed without an upload, and ``train()`` logs that under ``oob/`` at every
+validation interval (``draw`` = the step count).
+
 Differences to the reference, by necessity:
 
 * models are specified by ``EnvModelSpec`` + a parameter tree (flax is absent);
@@ -91,7 +98,8 @@ class _GpuEnvModelTrainer:
 
     def __init__(self, spec: em.EnvModelSpec, params: dict, train_loader, val_loader, config: EnvModelTrainerConfig,
                  logger=None, device: int = 0, tp_params: dict | None = None, focal_alpha=DEFAULT_FOCAL_ALPHA,
-                 focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT):
+                 focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT, bootstrap=False):
+        self.bootstrap = bool(bootstrap)
         flat = self._setup(spec, [params], train_loader, val_loader, config, focal_alpha, focal_gamma, dropout_rate)
         self.logger = logger
         h = ctypes.c_void_p()
@@ -156,6 +164,10 @@ class _GpuEnvModelTrainer:
         self._device_sampling = isinstance(ds, dict) and "observations" in ds
         if self._device_sampling:
             self._set_dataset(ds)
+        if getattr(self, "bootstrap", False):
+            if not self._device_sampling:
+                raise ValueError("bootstrap needs device sampling: a loader exposing its dataset dict")
+            self.set_bootstrap(True)
 
     def _set_dataset(self, ds: dict):
         # rows (a multistep loader holds [episodes][episode_length][..]: flattened back to rows)
@@ -165,6 +177,56 @@ class _GpuEnvModelTrainer:
         arrs = [obs, np.ascontiguousarray(act), _f32(ds["rewards"]).reshape(-1),
                 _f32(ds["next_observations"]).reshape(-1, D)]
         self._check(self._lib.fqlpop_emtrain_set_dataset(self._h, *[self._fptr(a) for a in arrs], len(arrs[0])))
+
+    # ------------------------------------------------------------ bootstrap
+    _n_models = 1
+
+    @property
+    def n_units(self) -> int:
+        """Units the device draw resamples: dataset rows, or episodes of the multistep model."""
+        ds = self.train_loader.dataset["observations"]
+        n = int(np.prod(np.shape(ds)[:-1]))
+        return n // self._cfg.episode_length if self._ms else n
+
+    def set_bootstrap(self, enable: bool = True, table=None):
+        """Draw every model's resample and out-of-bag list on the device (fqlpop_emtrain_set_bootstrap),
+        install the caller's ``table`` [K][n_units] instead, or drop them (``enable=False``)."""
+        if table is not None:
+            t = np.ascontiguousarray(np.asarray(table, np.int64))
+            self._check(self._lib.fqlpop_emtrain_set_bootstrap_table(
+                self._h, t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), t.size))
+        else:
+            self._check(self._lib.fqlpop_emtrain_set_bootstrap(self._h, 1 if enable else 0))
+        self.bootstrap = bool(enable) or table is not None
+
+    def _get_bootstrap(self, k: int):
+        n = self.n_units
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        table, oob, n_oob = np.zeros(n, np.int64), np.zeros(n, np.int64), ctypes.c_int64()
+        self._check(self._lib.fqlpop_emtrain_get_bootstrap(self._h, int(k), table.ctypes.data_as(i64), n,
+                                                           oob.ctypes.data_as(i64), n, ctypes.byref(n_oob)))
+        return table, oob[:n_oob.value].copy()
+
+    def bootstrap_table(self, k: int = 0) -> np.ndarray:
+        """Model k's resample [n_units]: a device-sampled step trains on unit table[u]."""
+        return self._get_bootstrap(k)[0]
+
+    def oob_rows(self, k: int = 0) -> np.ndarray:
+        """The units model k's resample misses (its out-of-bag set), ascending."""
+        return self._get_bootstrap(k)[1]
+
+    def _eval_oob_raw(self, n_batches: int, draw: int) -> np.ndarray:
+        out = np.zeros((self._n_models, 8), np.float32)
+        self._check(self._lib.fqlpop_emtrain_eval_oob(self._h, int(n_batches), int(draw) & 0xFFFFFFFFFFFFFFFF,
+                                                      self._fptr(out)))
+        return out
+
+    def eval_oob(self, n_batches: int, draw: int):
+        """eval_step averaged over n_batches out-of-bag batches drawn on the device (no upload, one
+        synchronisation): a log dict (K of them on an ensemble trainer)."""
+        out = self._eval_oob_raw(n_batches, draw)
+        logs = [self._logs(out[k], self._eval_keys()) for k in range(self._n_models)]
+        return logs if isinstance(self, _GpuEnvModelEnsembleTrainer) else logs[0]
 
     def _batch_ptrs(self, batch: dict):
         B = self.config.batch_size
@@ -234,12 +296,21 @@ class _GpuEnvModelTrainer:
 
     def _val(self, step: int):
         if self.val_loader is None:
-            return
+            return self._oob(step)
         logs = [self.eval_step(None, self.val_loader.sample(self.config.batch_size))
                 for _ in range(self.config.val_batches)]
         if self.logger:
             for k in logs[0]:
                 self.logger.log({f"val/{k}": float(np.mean([lg[k] for lg in logs]))}, step=step)
+        self._oob(step)
+
+    def _oob(self, step: int):
+        """Out-of-bag logs at a validation interval (bootstrap on): draw = the step count."""
+        if not self.bootstrap:
+            return
+        self.last_oob = self.eval_oob(self.config.val_batches, self.count)
+        if self.logger:
+            self.logger.log({f"oob/{k}": v for k, v in self.last_oob.items()}, step=step)
 
     def train(self) -> None:
         """The reference loop (state_predictor_trainer.py:119-170): val every 100
@@ -304,7 +375,9 @@ class _GpuEnvModelEnsembleTrainer(_GpuEnvModelTrainer):
 
     def __init__(self, spec: em.EnvModelSpec, params_list, train_loader, val_loader, config: EnvModelTrainerConfig,
                  seeds, loggers=None, device: int = 0, tp_params: dict | None = None, val_rngs=None,
-                 focal_alpha=DEFAULT_FOCAL_ALPHA, focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT):
+                 focal_alpha=DEFAULT_FOCAL_ALPHA, focal_gamma=DEFAULT_FOCAL_GAMMA, dropout_rate=DEFAULT_DROPOUT,
+                 bootstrap=False):
+        self.bootstrap = bool(bootstrap)
         self.K = len(params_list)
         self.seeds = [int(s) for s in seeds]
         if len(self.seeds) != self.K:
@@ -329,6 +402,10 @@ class _GpuEnvModelEnsembleTrainer(_GpuEnvModelTrainer):
     @property
     def logger(self):
         return self.loggers
+
+    @property
+    def _n_models(self):
+        return self.K
 
     # --------------------------------------------------------------- batches
     def _ens_batch(self, batches):
@@ -386,13 +463,22 @@ class _GpuEnvModelEnsembleTrainer(_GpuEnvModelTrainer):
 
     def _val(self, step: int):
         if self.val_loader is None:
-            return
+            return self._oob(step)
         logs = [self.eval_step(None, [self._sample(self.val_loader, k) for k in range(self.K)])
                 for _ in range(self.config.val_batches)]
         if self.loggers:
             for k in range(self.K):
                 for key in logs[0][k]:
                     self.loggers[k].log({f"val/{key}": float(np.mean([lg[k][key] for lg in logs]))}, step=step)
+        self._oob(step)
+
+    def _oob(self, step: int):
+        if not self.bootstrap:
+            return
+        self.last_oob = self.eval_oob(self.config.val_batches, self.count)
+        if self.loggers:
+            for k in range(self.K):
+                self.loggers[k].log({f"oob/{key}": v for key, v in self.last_oob[k].items()}, step=step)
 
     def train(self) -> None:
         """The reference loop once for all K models: val every 100 steps, one update of every

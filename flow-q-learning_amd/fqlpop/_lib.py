@@ -196,6 +196,12 @@ _SIGS = {
     "fqlpop_emtrain_ensemble_block_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                          ctypes.POINTER(ctypes.c_int)]),
+    "fqlpop_emtrain_set_bootstrap": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fqlpop_emtrain_set_bootstrap_table": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64]),
+    "fqlpop_emtrain_get_bootstrap": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                    ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                    ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_emtrain_eval_oob": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_uint64, _F]),
     "fqlpop_initobs_param_count": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_initobs_create": (ctypes.c_int, [ctypes.POINTER(InitObsConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

@@ -84,11 +84,39 @@ def ensemble_model_names(directory: Path, model: str, ensemble_size: int):
     return names
 
 
-def load_env_model_ensemble(save_directory: Path, env_name: str, model: str, ensemble_size: int):
-    """[(sp_tree, tp_tree)] * K from ``<save_directory>/<env_name>/env_models`` (ensemble_model_names)."""
+def load_env_model_ensemble(save_directory: Path, env_name: str, model: str, ensemble_size: int, members=None):
+    """[(sp_tree, tp_tree)] * K from ``<save_directory>/<env_name>/env_models`` (ensemble_model_names);
+    ``members``: the indices to load, in that order (``select_elites``), instead of all K."""
     d = Path(save_directory) / env_name / "env_models"
-    return [(em.load_flax_msgpack(d / f"{sp}.pt"), em.load_flax_msgpack(d / f"{tp}.pt"))
-            for sp, tp in ensemble_model_names(d, model, ensemble_size)]
+    names = ensemble_model_names(d, model, ensemble_size)
+    if members is not None:
+        names = [names[k] for k in members]
+    return [(em.load_flax_msgpack(d / f"{sp}.pt"), em.load_flax_msgpack(d / f"{tp}.pt")) for sp, tp in names]
+
+
+ELITE_LOSS = "next_observation_loss"  # the out-of-bag state loss of <model>_ens_oob.csv
+
+
+def select_elites(directory: Path, model: str, ensemble_size: int, elites: int) -> list:
+    """The ``elites`` of the K models that ``train_env_model.py --ensemble_size K --bootstrap``
+    ranks best (PETS / MBPO): the indices with the lowest final out-of-bag state loss in
+    ``<directory>/<model>_ens_oob.csv``, best first, ties to the lower index.  ValueError for
+    ``elites`` outside 1..K or a CSV that does not list the K models; FileNotFoundError names a
+    missing CSV."""
+    import csv
+    K, E = int(ensemble_size), int(elites)
+    if not 1 <= E <= K:
+        raise ValueError(f"--env_model_elites must be in 1..{K} (--env_model_ensemble), got {E}")
+    path = Path(directory) / f"{model}_ens_oob.csv"
+    if not path.exists():
+        raise FileNotFoundError(f"{path} not found: train the ensemble with train_env_model.py --ensemble_size "
+                                f"{K} --bootstrap")
+    with open(path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    loss = {int(r["model"]): float(r[ELITE_LOSS]) for r in rows if ELITE_LOSS in r}
+    if sorted(loss) != list(range(K)):
+        raise ValueError(f"{path} does not list the {ELITE_LOSS} of models 0..{K - 1}")
+    return sorted(range(K), key=lambda k: (loss[k], k))[:E]
 
 
 def ensemble_scores(per_model_success, per_model_length, score: str = "mean", mixed=None) -> dict:

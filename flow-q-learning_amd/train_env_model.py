@@ -20,9 +20,17 @@ models of the kinds in ``BATCHED_KINDS`` train as one launch per step
 (envmodel.trainer.*EnsembleTrainer; K <= 16) and the files are byte for byte those of K runs
 one after the other, which ``--ensemble_sequential`` still does.  Without
 ``--ensemble_size`` names and behaviour are the reference's.
+
+``--bootstrap`` (PETS / MBPO / MOPO; not for ``initial_observation``) trains every model on
+its own resample of the dataset, drawn on the device from the model's seed, and evaluates it
+on the rows (multistep: episodes) the resample missed: ``oob/`` rows join the log CSVs at every
+validation interval, and ``<model>_ens_oob.csv`` lists ``model, seed, n_units, n_oob`` and the
+final out-of-bag losses of every model -- what ``--env_model_elites`` of tune_alpha.py and
+evaluate_env_model.py ranks.  Without ``--bootstrap`` no file changes.
 """
 from __future__ import annotations
 
+import csv
 import os
 import sys
 from pathlib import Path
@@ -118,6 +126,9 @@ def build_parser():
     parser.add_argument("--ensemble_sequential", action="store_true",
                         help="train the --ensemble_size models one after the other (K runs) instead of "
                              "as one launch per step; the files are the same")
+    parser.add_argument("--bootstrap", action="store_true",
+                        help="train every model on its own bootstrap resample of the dataset and log its "
+                             "out-of-bag losses (oob/ rows, <model>_ens_oob.csv)")
     return parser
 
 
@@ -136,13 +147,31 @@ def main(argv=None):
         raise ValueError("--ensemble_size must be >= 0")
     if args.ensemble_size > 0 and args.model == "initial_observation":
         raise ValueError("--ensemble_size is for baseline, multistep and termination_predictor")
+    if args.bootstrap and args.model == "initial_observation":
+        raise ValueError("--bootstrap is for baseline, multistep and termination_predictor")
+    oob = [] if args.bootstrap else None  # one row per model, in model order
     if args.ensemble_size == 0:
-        return train_one(*member_config(args, None))
-    if args.ensemble_size >= 2 and not args.ensemble_sequential and args.model in BATCHED_KINDS:
-        return train_ensemble([member_config(args, k) for k in range(args.ensemble_size)])
-    for k in range(args.ensemble_size):
-        save_dir = train_one(*member_config(args, k))
+        save_dir = train_one(*member_config(args, None), oob=oob)
+    elif args.ensemble_size >= 2 and not args.ensemble_sequential and args.model in BATCHED_KINDS:
+        save_dir = train_ensemble([member_config(args, k) for k in range(args.ensemble_size)], oob=oob)
+    else:
+        for k in range(args.ensemble_size):
+            save_dir = train_one(*member_config(args, k), oob=oob)
+    if oob is not None:
+        write_oob_csv(save_dir / f"{args.model}_ens_oob.csv", oob)
     return save_dir
+
+
+def oob_row(k: int, seed: int, trainer, logs: dict, model: int = 0) -> dict:
+    """The ``<model>_ens_oob.csv`` row of saved model k: trainer-side model ``model``."""
+    return {"model": k, "seed": seed, "n_units": trainer.n_units, "n_oob": len(trainer.oob_rows(model)), **logs}
+
+
+def write_oob_csv(path, rows):
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=list(rows[0]))
+        w.writeheader()
+        w.writerows(rows)
 
 
 # the model kinds whose ensembles train batched by default (DESIGN.md section 5, the ensemble
@@ -183,7 +212,7 @@ def _save(save_dir, name, config, params):
         f.write(msgpack_serialize({"params": params}))
 
 
-def train_ensemble(members):
+def train_ensemble(members, oob=None):
     """The K runs ``train_one(config_k, name_k)`` as one batched trainer: model k starts from
     the tree of seed_k, draws its minibatches and dropout mask from seed_k on the device and
     its val batches from ``RandomState(seed_k)`` (what ``np.random.seed(seed_k)`` gives the
@@ -202,22 +231,25 @@ def train_ensemble(members):
         else:
             loaders = (StepLoader(train), StepLoader(val))
         trainer = StatePredictorEnsembleTrainer(spec, [em.init_state_predictor(spec, s) for s in seeds], *loaders,
-                                                config, seeds, loggers=loggers, tp_params=tp)
+                                                config, seeds, loggers=loggers, tp_params=tp,
+                                                bootstrap=oob is not None)
     elif config.model == "termination_predictor":
         spec = em.EnvModelSpec(D, A, em.DEFAULT_HIDDEN, hidden)
         trainer = TerminationPredictorEnsembleTrainer(spec, [em.init_termination_predictor(spec, s) for s in seeds],
                                                       StepLoader(train), StepLoader(val), config, seeds,
-                                                      loggers=loggers)
+                                                      loggers=loggers, bootstrap=oob is not None)
     else:
         raise ValueError(f"no batched ensemble trainer for model {config.model!r}")
     trainer.train()
     for cfg, name, params in zip(configs, names, trainer.params):
         _save(save_dir, name, cfg, params)
+    if oob is not None:
+        oob.extend(oob_row(k, s, trainer, trainer.last_oob[k], model=k) for k, s in enumerate(seeds))
     trainer.close()
     return save_dir
 
 
-def train_one(config, name: str):
+def train_one(config, name: str, oob=None):
     """One training run of config.model, saved under ``name``."""
     train, val, save_dir = _load_data(config)
     D, A = train["observations"].shape[-1], train["actions"].shape[-1]
@@ -231,11 +263,12 @@ def train_one(config, name: str):
         else:
             loaders = (StepLoader(train), StepLoader(val))
         trainer = StatePredictorTrainer(spec, em.init_state_predictor(spec, config.seed), *loaders, config,
-                                        logger=logger, tp_params=tp)
+                                        logger=logger, tp_params=tp, bootstrap=oob is not None)
     elif config.model == "termination_predictor":
         spec = em.EnvModelSpec(D, A, em.DEFAULT_HIDDEN, hidden)
         trainer = TerminationPredictorTrainer(spec, em.init_termination_predictor(spec, config.seed),
-                                              StepLoader(train), StepLoader(val), config, logger=logger)
+                                              StepLoader(train), StepLoader(val), config, logger=logger,
+                                              bootstrap=oob is not None)
     elif config.model == "initial_observation":
         io_spec = iobs.InitialObservationSpec(D, int(config.model_config.get("latent_dim", 4)), hidden)
         trainer = iobs.InitialObservationTrainer(io_spec, iobs.init_initial_observation(io_spec, config.seed),
@@ -250,6 +283,8 @@ def train_one(config, name: str):
                          "initial_observation)")
     trainer.train()
     _save(save_dir, name, config, trainer.params)
+    if oob is not None:
+        oob.append(oob_row(len(oob), config.seed, trainer, trainer.last_oob))
     trainer.close()
     return save_dir
 

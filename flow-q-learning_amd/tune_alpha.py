@@ -53,8 +53,19 @@ def make_task(args, config):
     if args.task == "simulated":
         # world-model evaluation on the GPU (BASELINE config 5): the reference's env-model files
         # under <save>/<env>/env_models if present, else a seeded synthetic model
-        from task.offline_task_simulated import OfflineTaskWithSimulatedEvaluations
+        from task.offline_task_simulated import (OfflineTaskWithSimulatedEvaluations, load_env_model_ensemble,
+                                                 select_elites)
         env_dir = config.save_directory / config.env_name / "env_models"
+        if args.env_model_elites:
+            # the E models with the lowest out-of-bag loss, handed over as if E had been trained
+            elites = select_elites(env_dir, args.env_model, args.env_model_ensemble, args.env_model_elites)
+            return OfflineTaskWithSimulatedEvaluations(
+                config.env_name, model=args.env_model, save_directory=config.save_directory,
+                n_rows=args.synthetic_rows, num_evaluation_envs=config.eval_episodes,
+                max_episode_steps=args.max_episode_steps, seed=config.seed,
+                initial_observations=args.initial_observations, ensemble_score=args.ensemble_score,
+                env_models=load_env_model_ensemble(config.save_directory, config.env_name, args.env_model,
+                                                   args.env_model_ensemble, members=elites))
         return OfflineTaskWithSimulatedEvaluations(
             config.env_name, model=args.env_model, save_directory=config.save_directory if env_dir.exists() else None,
             n_rows=args.synthetic_rows, num_evaluation_envs=config.eval_episodes,
@@ -102,6 +113,9 @@ def build_parser():
     # or mixed episodes that draw a model afresh at every step (task/offline_task_simulated.py)
     parser.add_argument("--env_model_ensemble", type=int, default=0)
     parser.add_argument("--ensemble_score", choices=("mean", "min", "mixed"), default="mean")
+    # keep only the E of the K models with the lowest out-of-bag loss (<model>_ens_oob.csv of
+    # train_env_model.py --bootstrap); 0: all K
+    parser.add_argument("--env_model_elites", type=int, default=0)
     return parser
 
 

@@ -601,6 +601,48 @@ int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, f
 int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xcd_mode, int linear_block,
                                       int* grid_blocks, int* model, int* block);
 
+/* Bootstrapped training (PETS / MBPO / MOPO): every model of a handle (one of a single-model
+ * handle) draws its minibatches through its own resample of the dataset, and is evaluated on
+ * the units its resample missed (out of bag).  The unit is what the device draw draws: a row
+ * (n_units = n_rows) for the state and termination predictors, an episode (n_units = n_rows /
+ * episode_length) for FQLPOP_EM_MULTISTEP, whose window start inside the episode is drawn as
+ * without a table.  A device-sampled step computes its unit index u as without a table (same
+ * Philox counter, salt and modulus) and then trains on unit table[model][u]; the injected
+ * calls ignore the table.  An identity table gives the bits of a handle without one.
+ *   table[k][i] (drawn on the device)  Philox4x32-10, key = seeds[k] (cfg.seed of a
+ *       single-model handle), counter (lo32(i), hi32(i), FQLPOP_EM_SALT_BOOT, 0):
+ *       (x1 << 32 | x0) mod n_units
+ *   oob[k]    the units that do not occur in table[k], ascending; n_oob[k] of them
+ *   out-of-bag batch j of a call with `draw`, batch position p:  counter (p, j,
+ *       FQLPOP_EM_SALT_OOB, lo32(draw)), key = seeds[k]: unit oob[k][(x1 << 32 | x0) mod
+ *       n_oob[k]]; multistep: window start x2 mod (episode_length - T), as in training
+ * The set-up (fill, mark, compact: three small launches for all K models, deterministic) runs
+ * once per call of a setter, not on the step's path.  Every refusal below comes before any
+ * launch and changes neither the tables nor the models.  fqlpop_emtrain_set_dataset drops the
+ * tables (they index the old rows): bootstrap is off until it is set again. */
+#define FQLPOP_EM_SALT_BOOT 0xB7u
+#define FQLPOP_EM_SALT_OOB 0xB5u
+/* enable = 1 draws the K tables and out-of-bag lists, 0 drops them (the handle trains as if
+ * they had never been set).  FQLPOP_E_STATE before fqlpop_emtrain_set_dataset; FQLPOP_E_ARG
+ * for another value of enable.  A failed allocation (FQLPOP_E_HIP) keeps the earlier tables. */
+int fqlpop_emtrain_set_bootstrap(fqlpop_emtrain_t* h, int enable);
+/* A caller's own resample or partition: table[n_models][n_units], n = n_models * n_units.
+ * FQLPOP_E_STATE before the dataset; FQLPOP_E_ARG for another n or an entry outside
+ * [0, n_units) (the host checks every entry). */
+int fqlpop_emtrain_set_bootstrap_table(fqlpop_emtrain_t* h, const int64_t* table, int64_t n);
+/* One model's table[n_units] and, when oob is not NULL, its out-of-bag list (oob_cap >=
+ * n_oob entries of room, else FQLPOP_E_ARG); *n_oob always.  FQLPOP_E_STATE without tables;
+ * FQLPOP_E_ARG for a model out of range or another n_units.  Synchronises. */
+int fqlpop_emtrain_get_bootstrap(fqlpop_emtrain_t* h, int model, int64_t* table, int64_t n_units, int64_t* oob,
+                                 int64_t oob_cap, int64_t* n_oob);
+/* eval_step of every model on n_batches out-of-bag batches drawn on the device (no dropout,
+ * no update, the update count unchanged): logs[n_models][FQLPOP_EM_LOG_STRIDE], each the
+ * float32 mean over the batches of the logs fqlpop_emtrain_eval_ensemble gives for that
+ * batch, summed in batch order on the device; no upload, one synchronisation.
+ * FQLPOP_E_ARG for n_batches < 1; FQLPOP_E_STATE without a dataset or tables, or when a
+ * model's out-of-bag list is empty (the text names the model). */
+int fqlpop_emtrain_eval_oob(fqlpop_emtrain_t* h, int n_batches, uint64_t draw, float* logs);
+
 /* ---------------------------------------------------------------------------
  * Initial-observation VAE (the decoder as a source of episode
  * starts): InitialObservationEnvModel and vae_loss (envmodel/initial_observation.py:8-78).
