@@ -2226,6 +2226,15 @@ int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count) {
     });
 }
 
+int fqlpop_emtrain_get_plan(fqlpop_emtrain_t* h, int* sweep, int* tchunks, int* blocks) {
+    return em_guard([&] {
+        ARGCHK(h, "null handle");
+        if (sweep) *sweep = h->sweep ? 1 : 0;
+        if (tchunks) *tchunks = h->tchunks;
+        if (blocks) *blocks = h->blocks;
+    });
+}
+
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h) {
     return em_guard([&] {
         ARGCHK(h, "null handle");

@@ -285,6 +285,15 @@ class _GpuEnvModelTrainer:
         self._check(self._lib.fqlpop_emtrain_get_count(self._h, ctypes.byref(c)))
         return c.value
 
+    @property
+    def plan(self) -> dict:
+        """The launch plan chosen at creation: ``sweep`` (the multistep step runs em_sweep_kernel +
+        em_seq_dw_kernel, not em_seq_grad_kernel), ``tchunks`` (T chunks of its dW GEMM) and
+        ``blocks`` (16-row blocks per model)."""
+        v = [ctypes.c_int() for _ in range(3)]
+        self._check(self._lib.fqlpop_emtrain_get_plan(self._h, *[ctypes.byref(x) for x in v]))
+        return {"sweep": bool(v[0].value), "tchunks": v[1].value, "blocks": v[2].value}
+
     def flat(self, which: int = 0) -> np.ndarray:
         out = np.zeros(self.n_params, np.float32)
         self._check(self._lib.fqlpop_emtrain_get_params(self._h, int(which), self._fptr(out), self.n_params))

@@ -184,6 +184,7 @@ _SIGS = {
     "fqlpop_emtrain_read_logs": (ctypes.c_int, [_P, _F]),
     "fqlpop_emtrain_get_params": (ctypes.c_int, [_P, ctypes.c_int, _F, ctypes.c_int64]),
     "fqlpop_emtrain_get_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    "fqlpop_emtrain_get_plan": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "fqlpop_emtrain_sync": (ctypes.c_int, [_P]),
     "fqlpop_emtrain_create_ensemble": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.c_int, _F, ctypes.c_int64,
                                                       ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,

@@ -558,6 +558,11 @@ int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs);
  * (train_env_model.py:132-134). Synchronises. */
 int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_t n);
 int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count);
+/* The launch plan chosen at creation (read-only, no GPU call): *sweep = 1 when the multistep
+ * step runs em_sweep_kernel + em_seq_dw_kernel, 0 for em_seq_grad_kernel (and for the
+ * single-step kinds); *tchunks = T chunks of the dW GEMM (1 off the sweep path); *blocks =
+ * 16-row blocks per model.  A null out pointer is skipped. */
+int fqlpop_emtrain_get_plan(fqlpop_emtrain_t* h, int* sweep, int* tchunks, int* blocks);
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h);
 
 /* World-model ensemble training: K models behind one handle, every train step one launch

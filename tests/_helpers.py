@@ -90,6 +90,117 @@ class OptimiserChecker:
         assert not bad, f"{tag}:\n" + "\n".join(bad[:20])
 
 
+def em_leaf_table(names, shapes):
+    """[(name, offset, size)] of a flat env-model vector from its leaf names and shapes."""
+    out, o = [], 0
+    for name, shp in zip(names, shapes):
+        n = int(np.prod(shp))
+        out.append(("/".join(name) if isinstance(name, tuple) else str(name), o, n))
+        o += n
+    return out
+
+
+EM_GRAD_REL = 1e-3          # a leaf's moment increments: this fraction of the leaf's largest one
+EM_DIFF_ULPS = 2 * 2.0 ** -23   # ... plus this much of |m1| (|v1|): the increment is a difference of two fp32 values
+
+
+class EmOptimiserChecker:
+    """OptimiserChecker for the env-model trainers (em_adam_kernel behind fqlpop_emtrain_* and
+    fqlpop_initobs_*), from ANY state: every step is judged from the trainer's own pre-step
+    (p0, m0, v0, count0), so moments need not start at zero and nothing has to be uploaded.
+
+    ``tr`` has ``flat(which)`` (``flat(model, which)`` with ``model`` given) and ``count``;
+    ``leaves`` is ``em_leaf_table(...)``.  ``before()`` ahead of the step, then
+    ``after(grads, lr_init, steps)`` with the float64 oracle's gradient at the trainer's own p0
+    as a flat vector:
+
+    1. gradients, through the moment increments: m1 - 0.9 m0 against 0.1 g and v1 - 0.999 v0
+       against 0.001 g^2, each element within EM_GRAD_REL of its leaf's largest expected
+       increment plus EM_DIFF_ULPS |m1| (|v1|).  From non-zero moments g is a tenth of m and a
+       thousandth of v: the increments, not the moments, carry it;
+    2. the optimiser, exactly: p1 against optax.adam in float64 on the trainer's own p0, m1, v1
+       with lr = cosine(lr_init, steps)(count0) and bias corrections at count0 + 1, within
+       1e-7 + 1e-6 |p|;
+    3. count == count0 + 1;
+    4. the schedule's clamp: at count0 >= steps the rate is exactly 0, so p1 == p0 bitwise
+       (m and v still move).
+
+    ``measure`` returns (ratios, messages): every check's largest error as a fraction of its
+    bound (``clamp`` and ``count``: 0 or inf) and one line per leaf that misses."""
+
+    def __init__(self, tr, leaves, model=None, b1=0.9, b2=0.999, eps=1e-8):
+        self.tr, self.leaves, self.model = tr, leaves, model
+        self.b1, self.b2, self.eps = b1, b2, eps
+        self.prev = None
+
+    def _flat32(self, which):
+        return self.tr.flat(which) if self.model is None else self.tr.flat(self.model, which)
+
+    def _state(self):
+        return tuple(np.asarray(self._flat32(w), np.float32) for w in (0, 1, 2))
+
+    def before(self):
+        """The trainer's (p0, m0, v0) as float32; keeps them for ``after``."""
+        self.prev = self._state()
+        self.count0 = int(self.tr.count)
+        return self.prev
+
+    def measure(self, grads, lr_init, steps):
+        import math
+        p0_32, m0_32, v0_32 = self.prev
+        p1_32, m1_32, v1_32 = self._state()
+        p0, m0, v0, p1, m1, v1 = (a.astype(np.float64) for a in (p0_32, m0_32, v0_32, p1_32, m1_32, v1_32))
+        g = np.asarray(grads, np.float64).reshape(-1)
+        assert g.shape == p0.shape, (g.shape, p0.shape)
+        c0, t = self.count0, self.count0 + 1
+        lr = lr_init * 0.5 * (1.0 + math.cos(math.pi * min(c0, steps) / steps))
+        bc1, bc2 = 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
+        ratios = {"m": 0.0, "v": 0.0, "opt": 0.0, "clamp": 0.0, "count": 0.0}
+        bad = []
+        if int(self.tr.count) != t:
+            ratios["count"] = float("inf")
+            bad.append(f"count {c0} -> {int(self.tr.count)}")
+        for name, off, n in self.leaves:
+            sl = slice(off, off + n)
+            for what, new, inc, want in (("m", m1[sl], m1[sl] - self.b1 * m0[sl], (1 - self.b1) * g[sl]),
+                                         ("v", v1[sl], v1[sl] - self.b2 * v0[sl], (1 - self.b2) * g[sl] ** 2)):
+                bound = EM_GRAD_REL * float(np.abs(want).max()) + EM_DIFF_ULPS * np.abs(new) + 1e-30
+                r = float((np.abs(inc - want) / bound).max())
+                ratios[what] = max(ratios[what], r)
+                if not r <= 1.0:
+                    bad.append(f"{name} adam {what} increment: {r:.3g} of its bound "
+                               f"(largest expected {float(np.abs(want).max()):.3g})")
+            want_p = p0[sl] - lr * (m1[sl] / bc1) / (np.sqrt(v1[sl] / bc2) + self.eps)
+            r = float((np.abs(p1[sl] - want_p) / (1e-7 + 1e-6 * np.abs(want_p))).max())
+            ratios["opt"] = max(ratios["opt"], r)
+            if not r <= 1.0:
+                bad.append(f"{name} optimiser: |p - adam(own p, m, v)| is {r:.3g} of its bound")
+            if c0 >= steps and not np.array_equal(p1_32[sl], p0_32[sl]):
+                ratios["clamp"] = float("inf")
+                bad.append(f"{name}: parameters moved at count {c0} >= steps {steps} "
+                           f"({int((p1_32[sl] != p0_32[sl]).sum())} elements)")
+        return ratios, bad
+
+    def after(self, grads, lr_init, steps, tag=""):
+        ratios, bad = self.measure(grads, lr_init, steps)
+        assert not bad, f"{tag}:\n" + "\n".join(bad[:20])
+        return ratios
+
+
+def em_logs_ratio(got: dict, want: dict, rel: float, abs_: float = 1e-7) -> float:
+    """Largest |got - want| over pytest.approx(want, rel=rel, abs=abs_)'s tolerance, over the
+    keys of ``got``; a nan matches only a nan (inf otherwise)."""
+    worst = 0.0
+    for k, g in got.items():
+        w = float(want[k])
+        if np.isnan(w) or np.isnan(g):
+            if not (np.isnan(w) and np.isnan(g)):
+                return float("inf")
+            continue
+        worst = max(worst, abs(g - w) / max(rel * abs(w), abs_))
+    return worst
+
+
 # ---------------------------------------------------------------------------
 # trained-like states (oracle.fql_oracle.trained_like_params / trained_like_opt_state)
 # ---------------------------------------------------------------------------

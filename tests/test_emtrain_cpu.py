@@ -253,3 +253,219 @@ def test_multistep_loader_windows_like_reference():
     np.testing.assert_array_equal(b["next_observations"][..., 0], b["rewards"] + 1)
     with pytest.raises(ValueError):
         tem.MultistepLoader({k: v[:2500] for k, v in ds.items()}, T)
+
+
+# ---------------------------------------------------------------------------
+# tests/test_gpu_emtrain_trained.py's checks, proven on the CPU: the case table fits the
+# kernels' plans, the cases are well-conditioned at the checked bounds, and the checks catch
+# the mistakes that steps from the constructor's state cannot see (tests/test_oracle.py's
+# pattern: a mutated oracle plays the device).
+# ---------------------------------------------------------------------------
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _emtrain_cases as C  # noqa: E402
+from _helpers import EM_GRAD_REL, EmOptimiserChecker, em_leaf_table, em_logs_ratio  # noqa: E402
+
+_MS = C.MULTISTEP_CASES + [C.MULTISTEP_FALLBACK]
+
+
+def test_case_table_fits_the_lds_budget_and_reaches_its_edges():
+    for shape, B in C.SINGLE_CASES:
+        for kind, tw in (("state", 0.0), ("state", 1.0), ("termination", 0.0)):
+            assert C.em_plan(shape, kind, tw, 1, B)["lds"] <= C.LDS_BUDGET, (shape, kind, tw)
+    assert C.em_plan("C", "state", 1.0, 1, 32)["lds"] > 0.85 * C.LDS_BUDGET      # C is near the budget
+    for shape, T_, B, option, sweep, tchunks in _MS:
+        for tw in (0.0, 1.0):
+            plan = C.em_plan(shape, "multistep", tw, T_, B, option != 0)
+            assert plan["lds"] <= C.LDS_BUDGET and plan["sweep_lds"] <= C.SWEEP_LDS_BUDGET, (shape, tw)
+            assert (plan["sweep"], plan["tchunks"], plan["blocks"]) == (sweep, tchunks, B // 16), (shape, T_, tw, plan)
+    # A: ops 20 -> 3 and 20 -> 4 split S = 4 over 5 k-steps in chunks of 2: 2, 2, 1 and an empty one
+    for No in (3, 4):
+        ntile, S, cks, nks = C.sw_op_plan(20, No)
+        assert (ntile, S, cks, nks) == (1, 4, 2, 5) and (S - 1) * cks >= nks
+    # B: op 50 -> 19 has S = 8 over 13 k-steps (uneven chunks); widths no multiple of 4; P % 64 != 0
+    assert C.sw_op_plan(50, 19)[1:] == (8, 2, 13)
+    offs = [o for _, o, _ in em_leaf_table(*C.layout("B", "state"))]
+    assert 50 % 4 and 17 % 4 and any(o % 4 for o in offs)      # leaves off the 16-byte grid
+    assert sum(int(np.prod(s)) for s in C.layout("B", "state")[1]) % 64 != 0
+    # D: two T chunks of odd and even length; 96 is a ragged 64-tile.  E: four chunks, 16 17 17 17
+    assert C.tchunk_lengths(35, 2) == [17, 18] and 96 % 64 != 0
+    assert C.tchunk_lengths(67, 4) == [16, 17, 17, 17]
+    # A: one block, one k-step of the first layer
+    assert C.SINGLE_CASES[0] == ("A", 16) and sum(C.SHAPES["A"][:2]) == 4
+
+
+def _case_step(kind, shape, tw, B, T_, seed):
+    """(names, flat float32 parameters, step_fn(flat) -> (logs, flat grads)) of one case at the
+    random-bias parameters, on one batch with a ReLU margin."""
+    spec = C.spec_of(shape)
+    D, A = spec.obs_dim, spec.action_dim
+    sp, tp = C.random_bias_params(shape, 11)
+    names, shapes = C.layout(shape, kind)
+    tree = tp if kind == "termination" else sp
+    flat = C.flat_of(names, tree).astype(np.float32)
+    rng = np.random.default_rng(seed)
+    keep = (rng.uniform(size=(B, D)) >= 0.1) if kind == "termination" else None
+
+    def step(fl, b):
+        return C.oracle_step(kind, C.tree_of(names, shapes, fl), b, tw, C.f64(tp), keep)
+
+    draw = (lambda: C.seq_batch(rng, B, T_, D, A)) if kind == "multistep" else (lambda: C.row_batch(rng, B, D, A))
+    b, _, _ = C.batch_with_margin(draw, lambda bb: step(flat, bb))
+    return names, flat, lambda fl: step(fl, b)[:2]
+
+
+_COND = [("state", s, tw, B, 1) for s, B in C.SINGLE_CASES for tw in (0.0, 1.0)] + \
+        [("termination", s, 0.0, B, 1) for s, B in C.SINGLE_CASES] + \
+        [("multistep", c[0], tw, c[2], c[1]) for c in _MS if c[3] != 0 for tw in (0.0, 1.0)]
+
+
+@pytest.mark.parametrize("kind,shape,tw,B,T_", _COND)
+def test_cases_are_well_conditioned(kind, shape, tw, B, T_):
+    """A one-ulp (2^-24 relative) perturbation of every float32 parameter moves the float64
+    loss and every gradient leaf by at most 1 / 100 of the bound the GPU test holds them to."""
+    names, flat, step = _case_step(kind, shape, tw, B, T_, 1)
+    logs0, g0 = step(flat.astype(np.float64))
+    sign = np.where(np.random.default_rng(2).uniform(size=flat.size) < 0.5, -1.0, 1.0)
+    logs1, g1 = step(flat.astype(np.float64) * (1.0 + sign * 2.0 ** -24))
+    rel = C.LOG_REL_MS if kind == "multistep" else C.LOG_REL
+    assert em_logs_ratio(logs1, logs0, rel, C.LOG_ABS) <= 0.01, (logs0, logs1)
+    for m, k in names:
+        d, scale = float(np.abs(g1[m][k] - g0[m][k]).max()), float(np.abs(g0[m][k]).max())
+        assert d <= 0.01 * EM_GRAD_REL * scale, (m, k, d / scale)
+
+
+class _OracleDevice:
+    """The float64 oracle played as the device, with named mistakes: float32 parameters and
+    moments, an update count, ``flat(which)`` / ``count`` / ``train_step`` as a trainer's."""
+
+    def __init__(self, kind, shape, tw, steps, flat, m, v, count, tp, mutations=()):
+        self.kind, self.tw, self.steps, self.count, self.tp, self.mut = kind, tw, steps, count, tp, set(mutations)
+        self.names, self.shapes = C.layout(shape, kind)
+        self.state = [np.asarray(a, np.float32).copy() for a in (flat, m, v)]
+
+    def flat(self, which=0):
+        return self.state[which].copy()
+
+    def train_step(self, batch, keep=None):
+        tree, tp = C.tree_of(self.names, self.shapes, self.state[0]), C.f64(self.tp)
+        if "tp_hidden_bias" in self.mut:
+            tp["Dense_0"]["bias"] = np.zeros_like(tp["Dense_0"]["bias"])
+        if "tp_head_bias" in self.mut:
+            last = f"Dense_{T._n_dense(tp) - 1}"
+            tp[last]["bias"] = np.zeros_like(tp[last]["bias"])
+        if "dense_bias" in self.mut:
+            tree["Dense_1"]["bias"] = np.zeros_like(tree["Dense_1"]["bias"])
+        if "ln_bias" in self.mut:
+            tree["LayerNorm_0"]["bias"] = np.zeros_like(tree["LayerNorm_0"]["bias"])
+        logs, grads, _ = C.oracle_step(self.kind, tree, batch, self.tw, tp, keep)
+        g = C.flat_of(self.names, grads)
+        p, m, v = (a.astype(np.float64) for a in self.state)
+        c = self.count if "no_clamp" in self.mut else min(self.count, self.steps)
+        lr = C.LR if "const_lr" in self.mut else C.LR * 0.5 * (1.0 + math.cos(math.pi * c / self.steps))
+        t = self.count if "bc_count" in self.mut else self.count + 1
+        b2 = 0.99 if "b2" in self.mut else 0.999
+        m = 0.9 * m + 0.1 * g
+        if "v_frozen" not in self.mut:
+            v = b2 * v + (1 - b2) * g * g
+        mh, vh = m / (1 - 0.9 ** t), v / (1 - b2 ** t)
+        den = np.sqrt(vh + 1e-8) if "eps_in_sqrt" in self.mut else np.sqrt(vh) + 1e-8
+        self.state = [a.astype(np.float32) for a in (p - lr * mh / den, m, v)]
+        self.count += 1
+        return logs
+
+
+_MUT_SHAPE, _MUT_B = "B", 48
+
+
+def _trained_like(kind, shape, B, count, zero_bias=False):
+    """(flat, m, v, frozen predictor) on the CPU: random biases (or the constructor's zeros),
+    moments as three oracle steps leave them, rescaled to ``count`` updates."""
+    spec = C.spec_of(shape)
+    sp, tp = C.random_bias_params(shape, 11)
+    if zero_bias:
+        sp, tp = em.init_state_predictor(spec, 11), em.init_termination_predictor(spec, 12)
+    names, shapes = C.layout(shape, kind)
+    tree = C.f64(tp if kind == "termination" else sp)
+    m, v = T.zeros_like_tree(tree), T.zeros_like_tree(tree)
+    rng = np.random.default_rng(3)
+    p = tree
+    for i in range(3):
+        _, grads, _ = C.oracle_step(kind, p, C.row_batch(rng, B, spec.obs_dim, spec.action_dim), 1.0, C.f64(tp),
+                                    np.ones((B, spec.obs_dim)))
+        p, m, v = T.adam_update(p, grads, m, v, i, C.LR)
+    flat = C.flat_of(names, tree)     # the parameters stay the random-bias ones
+    return (flat, C.flat_of(names, m) / (1 - 0.9 ** 3) * (1 - 0.9 ** count),
+            C.flat_of(names, v) / (1 - 0.999 ** 3) * (1 - 0.999 ** count), tp)
+
+
+def _play(mutations, count=1000, steps=2000, zero_bias=False, n_steps=2):
+    """Two checked steps of the (mutated) oracle device from a trained-like state through the
+    GPU test's checks: the largest error / bound of each."""
+    kind, shape, B = "state", _MUT_SHAPE, _MUT_B
+    spec = C.spec_of(shape)
+    flat, m, v, tp = _trained_like(kind, shape, B, max(count, 1), zero_bias)
+    if count == 0:
+        m, v = np.zeros_like(m), np.zeros_like(v)
+    dev = _OracleDevice(kind, shape, 1.0, steps, flat, m, v, count, tp, mutations)
+    ck = EmOptimiserChecker(dev, em_leaf_table(dev.names, dev.shapes))
+    rng = np.random.default_rng(4)
+    acc = {}
+    for _ in range(n_steps):
+        tree = C.tree_of(dev.names, dev.shapes, ck.before()[0])
+        b, want_logs, grads = C.batch_with_margin(
+            lambda: C.row_batch(rng, B, spec.obs_dim, spec.action_dim),
+            lambda bb: C.oracle_step(kind, tree, bb, 1.0, C.f64(tp)))
+        logs = dev.train_step(b)
+        ratios, _ = ck.measure(C.flat_of(dev.names, grads), C.LR, steps)
+        ratios["logs"] = em_logs_ratio(logs, want_logs, C.LOG_REL, C.LOG_ABS)
+        for k, r in ratios.items():
+            acc[k] = max(acc.get(k, 0.0), r)
+    return acc, dev
+
+
+def test_checks_pass_on_the_unmutated_oracle():
+    for kw in (dict(), dict(count=0), dict(count=1000, steps=1000), dict(count=200, steps=400)):
+        acc, _ = _play((), **kw)
+        assert max(acc.values()) <= 0.5, (kw, acc)
+
+
+@pytest.mark.parametrize("mutation,caught_by", [("tp_hidden_bias", "m"), ("tp_head_bias", "m"), ("dense_bias", "m"),
+                                                ("ln_bias", "m"), ("const_lr", "opt"), ("b2", "v"),
+                                                ("eps_in_sqrt", "opt"), ("v_frozen", "v")])
+def test_checks_catch_mutations_from_a_trained_state(mutation, caught_by):
+    """Each mistake exceeds the named bound by >= 10x from random biases, non-zero moments and
+    count 1000 of 2000."""
+    acc, _ = _play((mutation,))
+    print(mutation, acc)
+    assert acc[caught_by] >= 10.0, acc
+
+
+def test_checks_catch_a_missing_clamp():
+    """count 1000 past steps = 500: without the clamp the cosine is back at its full rate; at
+    steps = count - 1 the rate is ~1e-8 of the initial one and only the bitwise check sees it."""
+    acc, _ = _play(("no_clamp",), count=1000, steps=500)
+    assert acc["opt"] >= 10.0 and acc["clamp"] == float("inf"), acc
+    acc, _ = _play(("no_clamp",), count=1000, steps=999)
+    assert acc["clamp"] == float("inf"), acc
+
+
+def test_checks_catch_bias_correction_with_count():
+    """At count 1000 both corrections have all but converged (1 - 0.999^t moves by 6e-4 per
+    step: 1.5e-7 of a parameter, the size of the bound).  The GPU tests also run from count 200
+    (multistep) and from count 0: there the mistake is >= 10x the optimiser's bound."""
+    acc, _ = _play(("bc_count",), count=200, steps=400)
+    print(acc)
+    assert acc["opt"] >= 10.0, acc
+    acc, _ = _play(("bc_count",), count=1, steps=2000)
+    assert acc["opt"] >= 10.0, acc
+
+
+@pytest.mark.parametrize("mutation", ["tp_hidden_bias", "tp_head_bias"])
+def test_frozen_predictor_biases_are_invisible_from_the_constructor_state(mutation):
+    """The converse, and the reason for these tests: with the constructor's zero biases a kernel
+    that drops a bias of the frozen termination predictor computes exactly the right thing."""
+    _, good = _play((), count=0, zero_bias=True)
+    acc, bad = _play((mutation,), count=0, zero_bias=True)
+    assert max(acc.values()) <= 0.5, acc
+    for which in range(3):
+        np.testing.assert_array_equal(good.flat(which), bad.flat(which))

@@ -31,16 +31,20 @@ def _assert_tree_close(got, want, rtol, atol):
             np.testing.assert_allclose(got[m][k], want[m][k], rtol=rtol, atol=atol, err_msg=f"{m}/{k}")
 
 
-def _assert_moments_close(tr, want_m):
+def _assert_moments_close(tr, want_m, want_v=None):
     """Adam's first moment is linear in the gradients: the gradient check.
-    Tolerance 1e-3 of each leaf's scale (fp32 sums over the minibatch)."""
+    Tolerance 1e-3 of each leaf's scale (fp32 sums over the minibatch).  The second moment,
+    where the caller has the oracle's, likewise."""
     from envmodel.trainer import unflatten
-    got = unflatten(tr._names, tr._shapes, tr.flat(1))
-    for m in want_m:
-        for k in want_m[m]:
-            w = want_m[m][k]
-            np.testing.assert_allclose(got[m][k], w, rtol=1e-3, atol=1e-3 * float(np.abs(w).max()) + 1e-12,
-                                       err_msg=f"m {m}/{k}")
+    for what, which, want in (("m", 1, want_m), ("v", 2, want_v)):
+        if want is None:
+            continue
+        got = unflatten(tr._names, tr._shapes, tr.flat(which))
+        for m in want:
+            for k in want[m]:
+                w = want[m][k]
+                np.testing.assert_allclose(got[m][k], w, rtol=1e-3, atol=1e-3 * float(np.abs(w).max()) + 1e-12,
+                                           err_msg=f"{what} {m}/{k}")
 
 
 def _assert_params_close(got, want, steps, lr=1e-3):
@@ -76,7 +80,7 @@ def test_state_predictor_steps_match_oracle(tw, shape):
         for k in logs:
             assert logs[k] == pytest.approx(want_logs[k], rel=1e-4, abs=1e-7), (step, k)
         ref, m, v = T.adam_update(ref, grads, m, v, step, T.cosine_lr(1e-3, 50, step))
-        _assert_moments_close(tr, m)
+        _assert_moments_close(tr, m, v)
         _assert_params_close(tr.params, ref, step + 1)
     assert tr.count == 3
     # eval_step: logs of the current parameters, no update
@@ -104,7 +108,7 @@ def test_termination_predictor_steps_match_oracle():
         for k in logs:
             assert logs[k] == pytest.approx(want_logs[k], rel=1e-4, abs=1e-7), (step, k)
         ref, m, v = T.adam_update(ref, grads, m, v, step, T.cosine_lr(1e-3, 40, step))
-        _assert_moments_close(tr, m)
+        _assert_moments_close(tr, m, v)
         _assert_params_close(tr.params, ref, step + 1)
     b = _batch(rng, 128, D, 5, p_term=0.3)
     logs = tr.eval_step(None, b)
@@ -187,7 +191,7 @@ def test_multistep_steps_match_oracle(tw, T):
         for k in logs:
             assert logs[k] == pytest.approx(want_logs[k], rel=2e-4, abs=1e-7), (step, k)
         ref, m, v = T_.adam_update(ref, grads, m, v, step, T_.cosine_lr(1e-3, 50, step))
-        _assert_moments_close(tr, m)
+        _assert_moments_close(tr, m, v)
         _assert_params_close(tr.params, ref, step + 1)
     logs = tr.eval_step(None, _seq_batch(rng, 32, T, D, A))
     assert np.isfinite(logs["loss"])
@@ -350,7 +354,9 @@ def test_multistep_sweep_matches_round5_kernel(tw, T):
     within 1e-4, Adam moments within 1e-3 of each leaf's scale and parameters as against the
     oracle (only the order of the fp32 sums differs).  One step: an untrained cell rolled over
     T steps diverges, so later steps amplify rounding differences (4 steps at T = 48 differed by
-    6.5e-4 in the loss).  Both paths are oracle-checked on injected batches above."""
+    6.5e-4 in the loss).  The sweep path is oracle-checked on injected batches above at the default
+    widths; both paths are in tests/test_gpu_emtrain_trained.py, at edge shapes and from trained-like
+    states."""
     from _helpers import engine_options
     from envmodel.trainer import unflatten
     D, A = 28, 5
