@@ -1621,15 +1621,6 @@ using namespace fq;
 using namespace fq::em;
 
 namespace {
-// fqlpop_last_error's text lives in runtime.cpp, which does not use hostmem.h yet: the shared
-// guard's text is handed on (an empty text after a success)
-template <class F>
-int em_guard(F&& f) {
-    const int rc = guard(std::forward<F>(f));
-    fq::set_last_error(g_last_error.c_str());
-    return rc;
-}
-
 // flax leaf order (path-sorted): Dense_i/bias, Dense_i/kernel ..., LayerNorm_0/bias, LayerNorm_0/scale
 Net layout(int in, int nh, const int* hid, int out, bool ln, long long* total) {
     Net n{};
@@ -1745,7 +1736,7 @@ static bool sw_fits(const Net& n, const Net& tpn, bool tp, int D) {
 extern "C" {
 
 int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_params) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(cfg && n_params, "null argument");
         Net a, b;
         long long P, PT;
@@ -1868,7 +1859,7 @@ extern "C" {
 
 int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params, int64_t n_params, int device,
                           fqlpop_emtrain_t** out) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(cfg && params && out, "null argument");
         em_create(cfg, 1, params, n_params, &cfg->seed, 0, device, out);
     });
@@ -1876,7 +1867,7 @@ int fqlpop_emtrain_create(const fqlpop_emtrain_config* cfg, const float* params,
 
 int fqlpop_emtrain_create_ensemble(const fqlpop_emtrain_config* cfg, int n_models, const float* params,
                                    int64_t n_params, const uint64_t* seeds, int device, fqlpop_emtrain_t** out) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(cfg && params && out, "null argument");
         ARGCHK(seeds, "null seeds: an ensemble takes one seed per model");
         ARGCHK(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
@@ -1885,7 +1876,7 @@ int fqlpop_emtrain_create_ensemble(const fqlpop_emtrain_config* cfg, int n_model
 }
 
 int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && n_models, "null argument");
         *n_models = h->K;
     });
@@ -1893,7 +1884,7 @@ int fqlpop_emtrain_num_models(fqlpop_emtrain_t* h, int* n_models) {
 
 int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xcd_mode, int linear_block,
                                       int* grid_blocks, int* model, int* block) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(grid_blocks && model && block, "null argument");
         ARGCHK(n_models >= 1 && n_models <= ENS_MAX, "n_models must be 1..16");
         ARGCHK(blocks_per_model >= 1 && blocks_per_model <= (1 << 20), "blocks_per_model must be 1..2^20");
@@ -1909,7 +1900,7 @@ int fqlpop_emtrain_ensemble_block_map(int n_models, int blocks_per_model, int xc
 }
 
 int fqlpop_emtrain_destroy(fqlpop_emtrain_t* h) {
-    return em_guard([&] {
+    return guard([&] {
         if (!h) return;
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
@@ -1925,7 +1916,7 @@ int fqlpop_emtrain_destroy(fqlpop_emtrain_t* h) {
 }
 
 int fqlpop_emtrain_set_frozen_termination(fqlpop_emtrain_t* h, const float* tp_params, int64_t n) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && tp_params, "null argument");
         ARGCHK(h->PT > 0, "no frozen termination predictor in this config (termination_weight == 0)");
         ARGCHK(n == h->PT, "termination predictor size mismatch");
@@ -1943,7 +1934,7 @@ int fqlpop_emtrain_set_frozen_termination(fqlpop_emtrain_t* h, const float* tp_p
 
 int fqlpop_emtrain_set_dataset(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                const float* next_obs, int64_t n_rows) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && obs && rew && next_obs && (act || h->cfg.action_dim == 0), "null argument");
         ARGCHK(n_rows > 0, "n_rows must be > 0");
         if (h->cfg.kind == FQLPOP_EM_MULTISTEP)  // MultistepLoader reshapes to [n / episode_length][episode_length]
@@ -2070,7 +2061,7 @@ static void em_check_ready(fqlpop_emtrain* h) {
 }
 
 int fqlpop_emtrain_step(fqlpop_emtrain_t* h, int n_steps) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && n_steps >= 0, "bad argument");
         ARGCHK(h->data.rows > 0, "no dataset: call fqlpop_emtrain_set_dataset");
         em_check_ready(h);
@@ -2097,7 +2088,7 @@ static void em_upload_batch(fqlpop_emtrain* h, const float* obs, const float* ac
 
 int fqlpop_emtrain_step_injected(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                  const float* next_obs, const uint8_t* keep_mask) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         EM_SINGLE(h, "fqlpop_emtrain_step_injected_ensemble");
         em_check_ready(h);
@@ -2116,7 +2107,7 @@ int fqlpop_emtrain_step_injected(fqlpop_emtrain_t* h, const float* obs, const fl
 
 int fqlpop_emtrain_step_injected_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                           const float* next_obs, const uint8_t* keep_mask, int shared) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         ARGCHK(shared == 0 || shared == 1, "shared must be 0 or 1");
         em_check_ready(h);
@@ -2152,7 +2143,7 @@ static void em_logs(fqlpop_emtrain* h, float* out) {
 }
 
 int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_read_logs_ensemble");
         HIPCHK(hipSetDevice(h->device));
@@ -2161,7 +2152,7 @@ int fqlpop_emtrain_read_logs(fqlpop_emtrain_t* h, float* logs) {
 }
 
 int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         HIPCHK(hipSetDevice(h->device));
         em_logs(h, logs);
@@ -2170,7 +2161,7 @@ int fqlpop_emtrain_read_logs_ensemble(fqlpop_emtrain_t* h, float* logs) {
 
 int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                         const float* next_obs, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_eval_ensemble");
         em_check_ready(h);
@@ -2183,7 +2174,7 @@ int fqlpop_emtrain_eval(fqlpop_emtrain_t* h, const float* obs, const float* act,
 
 int fqlpop_emtrain_eval_ensemble(fqlpop_emtrain_t* h, const float* obs, const float* act, const float* rew,
                                  const float* next_obs, int shared, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         ARGCHK(shared == 0 || shared == 1, "shared must be 0 or 1");
         em_check_ready(h);
@@ -2204,7 +2195,7 @@ static void em_get_params(fqlpop_emtrain* h, int model, int which, float* out, i
 }
 
 int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_t n) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && out, "null argument");
         EM_SINGLE(h, "fqlpop_emtrain_get_params_model");
         em_get_params(h, 0, which, out, n);
@@ -2212,7 +2203,7 @@ int fqlpop_emtrain_get_params(fqlpop_emtrain_t* h, int which, float* out, int64_
 }
 
 int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, float* out, int64_t n) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && out, "null argument");
         ARGCHK(model >= 0 && model < h->K, "model index out of range");
         em_get_params(h, model, which, out, n);
@@ -2220,14 +2211,14 @@ int fqlpop_emtrain_get_params_model(fqlpop_emtrain_t* h, int model, int which, f
 }
 
 int fqlpop_emtrain_get_count(fqlpop_emtrain_t* h, int64_t* count) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && count, "null argument");
         *count = h->count;
     });
 }
 
 int fqlpop_emtrain_get_plan(fqlpop_emtrain_t* h, int* sweep, int* tchunks, int* blocks) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         if (sweep) *sweep = h->sweep ? 1 : 0;
         if (tchunks) *tchunks = h->tchunks;
@@ -2236,7 +2227,7 @@ int fqlpop_emtrain_get_plan(fqlpop_emtrain_t* h, int* sweep, int* tchunks, int* 
 }
 
 int fqlpop_emtrain_sync(fqlpop_emtrain_t* h) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->s));
@@ -2284,7 +2275,7 @@ static EmBootTables<> em_boot_build(fqlpop_emtrain* h, const int64_t* table) {
 extern "C" {
 
 int fqlpop_emtrain_set_bootstrap(fqlpop_emtrain_t* h, int enable) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         ARGCHK(enable == 0 || enable == 1, "enable must be 0 or 1");
         if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
@@ -2299,7 +2290,7 @@ int fqlpop_emtrain_set_bootstrap(fqlpop_emtrain_t* h, int enable) {
 }
 
 int fqlpop_emtrain_set_bootstrap_table(fqlpop_emtrain_t* h, const int64_t* table, int64_t n) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && table, "null argument");
         if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
         const long long nu = em_n_units(h);
@@ -2316,7 +2307,7 @@ int fqlpop_emtrain_set_bootstrap_table(fqlpop_emtrain_t* h, const int64_t* table
 
 int fqlpop_emtrain_get_bootstrap(fqlpop_emtrain_t* h, int model, int64_t* table, int64_t n_units, int64_t* oob,
                                  int64_t oob_cap, int64_t* n_oob) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && table && n_oob, "null argument");
         if (!h->boot) throw Err{FQLPOP_E_STATE, "no bootstrap tables: call fqlpop_emtrain_set_bootstrap"};
         ARGCHK(model >= 0 && model < h->K, "model index out of range");
@@ -2333,7 +2324,7 @@ int fqlpop_emtrain_get_bootstrap(fqlpop_emtrain_t* h, int model, int64_t* table,
 }
 
 int fqlpop_emtrain_eval_oob(fqlpop_emtrain_t* h, int n_batches, uint64_t draw, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         ARGCHK(n_batches >= 1, "n_batches must be >= 1");
         if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_emtrain_set_dataset"};
@@ -2749,7 +2740,7 @@ void vae_upload(fqlpop_initobs* h, const float* obs, const float* eps) {
 extern "C" {
 
 int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_params) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(cfg && n_params, "null argument");
         VaeArgs a;
         long long P;
@@ -2760,7 +2751,7 @@ int fqlpop_initobs_param_count(const fqlpop_initobs_config* cfg, int64_t* n_para
 
 int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params, int64_t n_params, int device,
                           fqlpop_initobs_t** out) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(cfg && params && out, "null argument");
         auto h = std::make_unique<fqlpop_initobs>();
         h->cfg = *cfg;
@@ -2831,7 +2822,7 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
 }
 
 int fqlpop_initobs_destroy(fqlpop_initobs_t* h) {
-    return em_guard([&] {
+    return guard([&] {
         if (!h) return;
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
@@ -2840,7 +2831,7 @@ int fqlpop_initobs_destroy(fqlpop_initobs_t* h) {
 }
 
 int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_rows) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && obs, "null argument");
         ARGCHK(n_rows > 0, "n_rows must be > 0");
         HIPCHK(hipSetDevice(h->device));
@@ -2854,7 +2845,7 @@ int fqlpop_initobs_set_dataset(fqlpop_initobs_t* h, const float* obs, int64_t n_
 }
 
 int fqlpop_initobs_step(fqlpop_initobs_t* h, int n_steps) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && n_steps >= 0, "bad argument");
         if (h->data.rows <= 0) throw Err{FQLPOP_E_STATE, "no dataset: call fqlpop_initobs_set_dataset first"};
         HIPCHK(hipSetDevice(h->device));
@@ -2863,7 +2854,7 @@ int fqlpop_initobs_step(fqlpop_initobs_t* h, int n_steps) {
 }
 
 int fqlpop_initobs_step_injected(fqlpop_initobs_t* h, const float* obs, const float* eps) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && obs, "null argument");
         HIPCHK(hipSetDevice(h->device));
         vae_upload(h, obs, eps);
@@ -2873,7 +2864,7 @@ int fqlpop_initobs_step_injected(fqlpop_initobs_t* h, const float* obs, const fl
 }
 
 int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && obs && logs, "null argument");
         ARGCHK(eps, "fqlpop_initobs_eval needs eps (an evaluation is a function of its inputs)");
         HIPCHK(hipSetDevice(h->device));
@@ -2884,7 +2875,7 @@ int fqlpop_initobs_eval(fqlpop_initobs_t* h, const float* obs, const float* eps,
 }
 
 int fqlpop_initobs_read_logs(fqlpop_initobs_t* h, float* logs) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && logs, "null argument");
         HIPCHK(hipSetDevice(h->device));
         vae_logs(h, logs);
@@ -2892,7 +2883,7 @@ int fqlpop_initobs_read_logs(fqlpop_initobs_t* h, float* logs) {
 }
 
 int fqlpop_initobs_get_params(fqlpop_initobs_t* h, int which, float* out, int64_t n) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && out, "null argument");
         ARGCHK(n == h->P, "params size mismatch");
         ARGCHK(which >= 0 && which <= 2, "which must be FQLPOP_STATE_PARAMS/ADAM_M/ADAM_V");
@@ -2904,14 +2895,14 @@ int fqlpop_initobs_get_params(fqlpop_initobs_t* h, int which, float* out, int64_
 }
 
 int fqlpop_initobs_get_count(fqlpop_initobs_t* h, int64_t* count) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && count, "null argument");
         *count = h->count;
     });
 }
 
 int fqlpop_initobs_sync(fqlpop_initobs_t* h) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h, "null handle");
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->s));
@@ -2919,7 +2910,7 @@ int fqlpop_initobs_sync(fqlpop_initobs_t* h) {
 }
 
 int fqlpop_initobs_sample(fqlpop_initobs_t* h, int64_t n, uint64_t seed, const float* z, float* out) {
-    return em_guard([&] {
+    return guard([&] {
         ARGCHK(h && out, "null argument");
         ARGCHK(n >= 1 && n <= (1LL << 31) - R, "n must be in 1..2^31 - 16");
         HIPCHK(hipSetDevice(h->device));

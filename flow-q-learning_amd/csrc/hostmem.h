@@ -1,12 +1,12 @@
 // Host-side plumbing of the C ABI: one error type, its check macros and guard, and move-only
-// owners of device memory, mapped / pinned host memory, events and streams.  emtrain.hip (the
-// fqlpop_emtrain and fqlpop_initobs handles) is built on it: every hipMalloc / hipFree /
-// hipHostMalloc / hipHostFree and stream creation and destruction of that file is here.
-// runtime.cpp (the fqlpop handle) still manages its memory by hand.
+// owners of device memory, mapped / pinned host memory, events and streams.  Every handle of
+// the library is built on it, emtrain.hip (fqlpop_emtrain, fqlpop_initobs) and runtime.cpp
+// (fqlpop, through the structs of popmem.h): every hipMalloc / hipFree / hipHostMalloc /
+// hipHostFree and event and stream creation and destruction of those files is here.
 //
 // The owners take their back end (allocate / release) as one template policy, HipBackend by
-// default; tests/cpp/hostmem_test.cpp defines FQ_HOSTMEM_NO_HIP and runs them over a counting
-// heap that fails the N-th allocation.
+// default; tests/cpp/hostmem_test.cpp (and emboot_test.cpp, popmem_test.cpp) define
+// FQ_HOSTMEM_NO_HIP and run them over a counting heap that fails the N-th allocation.
 #pragma once
 
 #include <cstddef>

@@ -26,29 +26,11 @@
 
 #include "../../include/fqlpop.h"
 #include "kernels.h"
+#include "popmem.h"
 
 using namespace fq;
 
 namespace {
-
-thread_local std::string g_err;
-
-struct FqErr {
-    int code;
-    std::string msg;
-};
-
-#define HIPCHK(x)                                                                                 \
-    do {                                                                                          \
-        hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess)                                                                     \
-            throw FqErr{FQLPOP_E_HIP, std::string(#x) + " failed: " + hipGetErrorString(e_)};     \
-    } while (0)
-
-#define ARGCHK(c, m)                                         \
-    do {                                                     \
-        if (!(c)) throw FqErr{FQLPOP_E_ARG, std::string(m)}; \
-    } while (0)
 
 constexpr long long kAlign = 64;  // floats (256 B)
 long long align_up(long long x) { return (x + kAlign - 1) / kAlign * kAlign; }
@@ -199,8 +181,12 @@ struct Leaf {
     long long size;
 };
 
+void release_graph(hipGraph_t g) { (void)hipGraphDestroy(g); }
+void release_graph_exec(hipGraphExec_t g) { (void)hipGraphExecDestroy(g); }
+using Graph = Owned<hipGraph_t, &release_graph>;
+
 struct Graphs {
-    hipGraphExec_t exec = nullptr;
+    Owned<hipGraphExec_t, &release_graph_exec> exec;
     int nz = -1;
 };
 
@@ -241,7 +227,11 @@ struct Net {
 
 }  // namespace
 
-struct fqlpop {
+// Every stream, event, graph, mapped host buffer and device buffer of the handle is held by an
+// owner of hostmem.h / popmem.h, so `delete h` releases them all (fqlpop_destroy, and a
+// fqlpop_create that throws); the raw pointers beside them are views.  The step's streams
+// (sM, sF, sB, sX) are a base: released last, after everything that was used on them.
+struct fqlpop : StepStreams<> {
     fqlpop_config cfg{};
     EngineOptions opt{};  // g_engine_opts at create
     int n = 0;          // slots
@@ -257,26 +247,27 @@ struct fqlpop {
     // `params` and its optimiser writes `params_nx`; the host swaps the pair
     // after enqueueing a train step (flip_params).  So no kernel of a step has
     // to wait for another's last read of a parameter before updating it.
-    float* params_buf[2] = {nullptr, nullptr};
+    DevBuf<float> params_buf[2];
     Buf paramsT_buf[2];
     int cur = 0;
-    float *params = nullptr, *params_nx = nullptr;
-    float *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr, *target = nullptr;
-    int* count = nullptr;
-    uint64_t* seeds = nullptr;
-    uint64_t* skeys = nullptr;  // per-member sampler key: sample_key(seed, alpha)
-    float* alpha = nullptr;
-    int* slots = nullptr;
-    float* stats = nullptr;
-    Chunk* chunks = nullptr;
-    int* chunk_leaf = nullptr;
-    int* leaf_first = nullptr;
+    float *params = nullptr, *params_nx = nullptr;  // views of params_buf: current / next
+    DevBuf<float> grads, adam_m, adam_v, target_buf;
+    float* target = nullptr;  // view of target_buf (Net::arena points at it, as at params)
+    DevBuf<int> count;
+    DevBuf<uint64_t> seeds;
+    DevBuf<uint64_t> skeys;  // per-member sampler key: sample_key(seed, alpha)
+    DevBuf<float> alpha;
+    DevBuf<int> slots;
+    DevBuf<float> stats;
+    DevBuf<Chunk> chunks;
+    DevBuf<int> chunk_leaf;
+    DevBuf<int> leaf_first;
     int n_chunks_net[3] = {0, 0, 0}, chunk_base_net[3] = {0, 0, 0}, n_chunks_total = 0;
     // fused optimiser (Adam in the dW epilogue): stats chunk id of each net's
     // W_l tiles, and the remaining (small-leaf) chunks the adam kernel runs
     bool fused_adam = false;
     int w_stat_base[3][EF_MAX_LAYERS] = {};
-    int* res_ids = nullptr;
+    DevBuf<int> res_ids;
     int res_base[3] = {0, 0, 0}, res_n[3] = {0, 0, 0};
     int n_train_leaves = 0;
 
@@ -287,14 +278,11 @@ struct fqlpop {
     std::vector<int> h_slots;
     int nz = 0;
 
-    // datasets
-    struct Dataset {
-        float *obs = nullptr, *act = nullptr, *rew = nullptr, *mask = nullptr, *nobs = nullptr;
-        long long rows = 0;
-    } ds[2];
+    // datasets: train, validation
+    PopDataset<> ds[2];
 
     // activations (slot-strided)
-    std::vector<float*> allocs;
+    std::vector<DevBuf<float>> allocs;
     Buf os_in, bc_in, eu_in, cr_in, tg_in;
     Buf cr_in_buf[2];  // cr_in per parameter buffer (cr_in = cr_in_buf[cur])
     Net n_cr, n_tg, n_bc, n_eu, n_os;  // critic, target critic, BC flow, per-layer Euler flow, one-step actor
@@ -302,10 +290,9 @@ struct fqlpop {
     Buf info, vinfo;
     Buf inj_batch, inj_noise;
 
-    hipStream_t sM = nullptr, sF = nullptr, sB = nullptr, sX = nullptr;  // sX: small-population schedule
-    hipEvent_t ev_sample, ev_bcfwd, ev_bcloss, ev_flow, ev_bdone;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // fqlpop_time_dominant_kernel
-    std::vector<hipEvent_t> ev_pool;
+    Event<> ev_sample, ev_bcfwd, ev_bcloss, ev_flow, ev_bdone;
+    Event<> ev_t0, ev_t1;  // fqlpop_time_dominant_kernel
+    std::vector<Event<>> ev_pool;
     int ev_next = 0;
     // in-step timing probe of the dominant kernel (Euler hidden-layer GEMM):
     // its blocks stamp s_memrealtime into per-launch slots; two slot sets are
@@ -314,18 +301,18 @@ struct fqlpop {
     // split launches (engine option split): per launch site an exchange area and a block of
     // arrival counters (zeroed by a memset node before every launch), and one error word
     struct SplitSite {
-        unsigned long long* xch = nullptr;
-        unsigned* cnt = nullptr;
-        unsigned* gen = nullptr;
+        DevBuf<unsigned long long> xch;
+        DevBuf<unsigned> cnt;
+        DevBuf<unsigned> gen;
         long long clusters = 0;    // capacity
     } split_site[8];
     unsigned* split_err = nullptr;       // device pointer of split_err_host (mapped, coherent host memory)
-    unsigned* split_err_host = nullptr;  // the host reads it without a copy or a synchronisation
+    HostBuf<unsigned> split_err_host;    // the host reads it without a copy or a synchronisation
     // members whose state a failed split launch may have written (sticky until restored): bit
     // w of restored[i] is set by fqlpop_set_state(i, w); all three restore the member, and so
     // does fqlpop_set_member(i, ..., reinit = 1)
     std::vector<unsigned char> poisoned, restored;
-    float* euler_pre0 = nullptr;        // the split Euler flow's layer-0 accumulators (SplitFwdArgs::pre0)
+    DevBuf<float> euler_pre0;           // the split Euler flow's layer-0 accumulators (SplitFwdArgs::pre0)
     long long euler_pre0_blocks = 0;     // its capacity in blocks
     bool split_ok = false;
     bool stream_fwd = false;       // whole-network forward launches (stream_fwd_kernel)
@@ -336,51 +323,43 @@ struct fqlpop {
     long long wt_net_off[3] = {0, 0, 0};
     bool wt_dirty = true;          // params changed on the host side: re-transpose before the next step
     // world-model rollout evaluator (fqlpop_set_env_model / fqlpop_rollout)
-    fqlpop_envmodel_config em{};
-    float *sp_params = nullptr, *tp_params = nullptr;
-    RolloutArgs em_args{};
-    bool em_set = false;
+    PopEnvModel<RolloutArgs> em;     // (false: none set)
     double replay_kernel_us = -1.0;  // replay_kernel's time in the last fqlpop_envmodel_replay (HIP events)
     // env-model ensemble (fqlpop_set_env_model_ensemble / fqlpop_rollout_ensemble): its own
     // storage, apart from the single model's above
-    float *ens_sp = nullptr, *ens_tp = nullptr;   // [ens_n][n_sp], [ens_n][n_tp]
-    EnvModelNet* ens_nets = nullptr;              // device [ens_n]: the layout with model k's pointers
-    RolloutArgs ens_args{};                       // the shared leaf layout
-    int ens_n = 0;
+    PopEnvModelEnsemble<RolloutArgs, EnvModelNet> ens;  // (ens.n == 0: none set)
     double ens_kernel_us = -1.0;   // rollout_ens_kernel's time in the last fqlpop_rollout_ensemble (HIP events)
     // synthetic-transition rings (fqlpop_synth_create; synth.obs null: none) and what a
     // collect needs between its launches: one workspace (start observations, the rollout's
     // out / out_obs / traces for all slots), grown on first use, and a few pinned buffers the
     // start rows of the collects in flight are read from
-    SynthRing synth{};
-    float* synth_ratio = nullptr;
-    float* synth_ws = nullptr;
-    long long synth_ws_floats = 0;
+    PopSynthRings<> synth_rings;
+    SynthRing synth{};  // the kernels' view of synth_rings and synth_ratio
+    DevBuf<float> synth_ratio;
+    PopCollectWs<> synth_ws;
     static constexpr int kSynthStage = 4;
-    long long* synth_start_host[kSynthStage] = {};
-    hipEvent_t synth_start_ev[kSynthStage] = {};
-    bool synth_start_used[kSynthStage] = {};
-    long long synth_start_cap = 0;
+    PopStartStage<kSynthStage> synth_start;
+    Event<> synth_start_ev[kSynthStage];  // buffer i's last reader (made with the first stage)
     int synth_start_next = 0;
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
     long long probe_step = 0;
     unsigned long long* probe_slots = nullptr;   // [2 sets][pairs][probe_blocks][2] (device view)
-    unsigned long long* probe_host = nullptr;    // the same slots: mapped coherent host memory
+    HostBuf<unsigned long long> probe_host;      // the same slots: mapped coherent host memory
     // FQLPOP_PHASE_PROBE=1 (diagnostics): the critic backward's per-block phase stamps (mapped
     // host memory, overwritten by every launch; summarised on stderr at destroy)
-    unsigned long long* phase_host = nullptr;
+    HostBuf<unsigned long long> phase_host;
     unsigned long long* phase_dev = nullptr;
     long long phase_blocks = 0;
-    unsigned long long* ephase_host = nullptr;  // the same for the persistent Euler launch
+    HostBuf<unsigned long long> ephase_host;    // the same for the persistent Euler launch
     unsigned long long* ephase_dev = nullptr;
     long long ephase_blocks = 0;
     int probe_pairs = 0;
     long long probe_blocks = 0;                  // max blocks of one dominant-kernel launch
     long long probe_nb[2] = {0, 0};              // blocks of the dominant launch of the step that used each set
-    hipEvent_t probe_done[2] = {nullptr, nullptr};
-    hipStream_t probe_stream = nullptr;
+    Event<> probe_done[2];
+    Stream<> probe_stream;
     bool probe_pending[2] = {false, false};
     double probe_total_ms = 0.0;
     long long probe_launches = 0;
@@ -391,10 +370,10 @@ struct fqlpop {
     // `per_slot` floats per slot, zeroed; `stride` is the slot stride its users address it by
     // (the five input buffers: allocated rounded up, strided by their unrounded size)
     Buf alloc(long long per_slot, long long stride = -1) {
-        float* p = nullptr;
-        HIPCHK(hipMalloc(&p, sizeof(float) * std::max<long long>(1, per_slot * n)));
-        HIPCHK(hipMemset(p, 0, sizeof(float) * std::max<long long>(1, per_slot * n)));
-        allocs.push_back(p);
+        const size_t count = (size_t)std::max<long long>(1, per_slot * n);
+        allocs.emplace_back(count, "workspace buffer");
+        float* p = allocs.back();
+        HIPCHK(hipMemset(p, 0, sizeof(float) * count));
         return Buf{p, stride < 0 ? per_slot : stride};
     }
 };
@@ -515,23 +494,23 @@ void build_chunks(fqlpop* h) {
         h->n_chunks_net[ni] = (int)all.size() - h->chunk_base_net[ni];
         h->res_n[ni] = (int)res.size() - h->res_base[ni];
     }
-    HIPCHK(hipMalloc(&h->res_ids, sizeof(int) * std::max<size_t>(1, res.size())));
+    h->res_ids = DevBuf<int>(std::max<size_t>(1, res.size()), "optimiser chunk ids");
     if (!res.empty()) HIPCHK(hipMemcpy(h->res_ids, res.data(), sizeof(int) * res.size(), hipMemcpyHostToDevice));
     h->n_chunks_total = (int)all.size();
     h->n_train_leaves = leaf_id;
     ARGCHK(leaf_id <= 128, "too many leaves");
-    HIPCHK(hipMalloc(&h->chunks, sizeof(Chunk) * all.size()));
+    h->chunks = DevBuf<Chunk>(all.size(), "optimiser chunks");
     HIPCHK(hipMemcpy(h->chunks, all.data(), sizeof(Chunk) * all.size(), hipMemcpyHostToDevice));
     std::vector<int> first(leaf_id + 1, 0);
     for (size_t c = all_leaf.size(); c-- > 0;) first[all_leaf[c]] = (int)c;
     first[leaf_id] = (int)all_leaf.size();
     for (size_t c = 1; c < all_leaf.size(); ++c)
         ARGCHK(all_leaf[c] >= all_leaf[c - 1], "chunks of a leaf must be contiguous");
-    HIPCHK(hipMalloc(&h->leaf_first, sizeof(int) * first.size()));
+    h->leaf_first = DevBuf<int>(first.size(), "leaf chunk ranges");
     HIPCHK(hipMemcpy(h->leaf_first, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->chunk_leaf, sizeof(int) * all_leaf.size()));
+    h->chunk_leaf = DevBuf<int>(all_leaf.size(), "chunk leaves");
     HIPCHK(hipMemcpy(h->chunk_leaf, all_leaf.data(), sizeof(int) * all_leaf.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->stats, sizeof(float) * 3 * all.size() * h->n));
+    h->stats = DevBuf<float>(3 * all.size() * h->n, "gradient statistics");
     HIPCHK(hipMemset(h->stats, 0, sizeof(float) * 3 * all.size() * h->n));
 }
 
@@ -600,7 +579,7 @@ TRef pref(fqlpop* h, float* arena, const NetLayout& N, long long off) {
 // Fork/join events of one enqueued step come from a pool (a distinct event per
 // record keeps graph capture dependencies unambiguous).
 hipEvent_t next_event(fqlpop* h) {
-    if (h->ev_next >= (int)h->ev_pool.size()) throw FqErr{FQLPOP_E_STATE, "event pool exhausted"};
+    if (h->ev_next >= (int)h->ev_pool.size()) throw Err{FQLPOP_E_STATE, "event pool exhausted"};
     return h->ev_pool[h->ev_next++];
 }
 
@@ -1590,6 +1569,10 @@ void flip_params(fqlpop* h) {
 
 Graphs& graph_for(fqlpop* h, bool train, bool inj_batch, bool inj_noise, bool recapture);
 
+// Every captured step goes (the caller has synchronised): whatever changes a pointer or a
+// launch that the graphs bake in calls this; graph_for captures again on demand.
+void drop_graphs(fqlpop* h) { h->graphs.clear(); }
+
 void run(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     if (h->nz == 0) return;
     if (h->stream_bwd && h->wt_dirty) {  // params set on the host side since the last step
@@ -1615,30 +1598,32 @@ Graphs& graph_for(fqlpop* h, bool train, bool inj_batch, bool inj_noise, bool re
     const long long key = ((train ? 4 : 0) + (inj_batch ? 2 : 0) + (inj_noise ? 1 : 0)) + 8LL * h->nz +
                           (1LL << 32) * (h->probe_set + 1) + (1LL << 36) * h->cur;
     Graphs& gr = h->graphs[key];
-    if (recapture || gr.exec == nullptr || gr.nz != h->nz) {
-        if (gr.exec) HIPCHK(hipGraphExecDestroy(gr.exec));
-        gr.exec = nullptr;
-        hipGraph_t graph;
+    if (recapture || !gr.exec || gr.nz != h->nz) {
+        gr.exec.reset();
         {   // the hardware-queue invariant: no more branches than the runtime has queues
             std::vector<hipStream_t> ss;
             for (hipStream_t s : {h->sM, h->sF, h->sB, h->sX})
                 if (std::find(ss.begin(), ss.end(), s) == ss.end()) ss.push_back(s);
             if ((int)ss.size() > 1 && (int)ss.size() > h->opt.hw_queues)
-                throw FqErr{FQLPOP_E_STATE, "step graph would have " + std::to_string(ss.size()) +
+                throw Err{FQLPOP_E_STATE, "step graph would have " + std::to_string(ss.size()) +
                                                 " parallel branches on " + std::to_string(h->opt.hw_queues) +
                                                 " hardware queues (hipGraphLaunch is unsafe then)"};
         }
         HIPCHK(hipStreamBeginCapture(h->sM, hipStreamCaptureModeRelaxed));
+        hipGraph_t captured = nullptr;
         try {
             enqueue(h, train, inj_batch, inj_noise);
         } catch (...) {
-            (void)hipStreamEndCapture(h->sM, &graph);
+            (void)hipStreamEndCapture(h->sM, &captured);
+            Graph(captured).reset();
             throw;
         }
-        HIPCHK(hipStreamEndCapture(h->sM, &graph));
-        HIPCHK(hipGraphInstantiate(&gr.exec, graph, nullptr, nullptr, 0));
+        HIPCHK(hipStreamEndCapture(h->sM, &captured));
+        const Graph graph(captured);  // (released here, also when the instantiation fails)
+        hipGraphExec_t exec = nullptr;
+        HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        gr.exec.reset(exec);
         HIPCHK(hipGraphUpload(gr.exec, h->sM));  // (else the first launch uploads it)
-        HIPCHK(hipGraphDestroy(graph));
         gr.nz = h->nz;
     }
     return gr;
@@ -1705,23 +1690,8 @@ void update_slots(fqlpop* h) {
     if (h->nz) HIPCHK(hipMemcpy(h->slots, h->h_slots.data(), sizeof(int) * h->nz, hipMemcpyHostToDevice));
 }
 
-template <typename F>
-int guard(F&& f) {
-    try {
-        f();
-        g_err.clear();
-        return FQLPOP_OK;
-    } catch (const FqErr& e) {
-        g_err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return FQLPOP_E_STATE;
-    }
-}
-
 bool split_error_pending(const fqlpop* h) {
-    return h->split_err_host && __atomic_load_n(h->split_err_host, __ATOMIC_ACQUIRE) != 0;
+    return h->split_err_host && __atomic_load_n(h->split_err_host.get(), __ATOMIC_ACQUIRE) != 0;
 }
 
 // A split launch whose hand-off wait gave up (kernels.hip, sp_fail) left invalid results.
@@ -1733,7 +1703,7 @@ bool split_error_pending(const fqlpop* h) {
 // The pending error word, if set, becomes the poison flags of the active members (returns true).
 bool absorb_split_error(fqlpop* h) {
     if (!split_error_pending(h)) return false;
-    __atomic_store_n(h->split_err_host, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(h->split_err_host.get(), 0u, __ATOMIC_RELEASE);
     for (auto& st : h->split_site)  // a launch that gave up may have left its counters set
         if (st.cnt) HIPCHK(hipMemset(st.cnt, 0, sizeof(unsigned) * split_counter_stride() * (st.clusters + 2)));
     for (int i = 0; i < h->n; ++i)
@@ -1750,10 +1720,10 @@ const char* const kSplitFailMsg =
 // only_active: whole-population training calls refuse for poisoned ACTIVE members only (a
 // pruned member does not step)
 void check_split_error(fqlpop* h, int member = -1, bool only_active = false) {
-    if (absorb_split_error(h)) throw FqErr{FQLPOP_E_STATE, kSplitFailMsg};
+    if (absorb_split_error(h)) throw Err{FQLPOP_E_STATE, kSplitFailMsg};
     for (int i = member < 0 ? 0 : member; i < (member < 0 ? h->n : member + 1); ++i)
         if (h->poisoned[i] && (!only_active || h->active[i]))
-            throw FqErr{FQLPOP_E_STATE, "member " + std::to_string(i) + "'s state was written by a failed split "
+            throw Err{FQLPOP_E_STATE, "member " + std::to_string(i) + "'s state was written by a failed split "
                                         "launch; restore it first (fqlpop_set_state of params, Adam m and v, or "
                                         "fqlpop_set_member with reinit)"};
 }
@@ -1770,14 +1740,13 @@ void check_member(fqlpop* h, int member) {
 
 }  // namespace
 
-void fq::set_last_error(const char* msg) { g_err = msg ? msg : ""; }
 int fq::engine_option_em_seq_sweep() { return g_engine_opts.em_seq_sweep; }
 int fq::engine_option_em_ens_xcd() { return g_engine_opts.em_ens_xcd; }
 
 // =================================================================== C ABI ==
 extern "C" {
 
-const char* fqlpop_last_error(void) { return g_err.c_str(); }
+const char* fqlpop_last_error(void) { return g_last_error.c_str(); }
 
 int fqlpop_set_engine_option(const char* name, int value) {
     return guard([&] {
@@ -1790,7 +1759,7 @@ int fqlpop_set_engine_option(const char* name, int value) {
                 g_engine_opts.*o.field = value;
                 return;
             }
-        throw FqErr{FQLPOP_E_ARG, std::string("unknown engine option ") + name};
+        throw Err{FQLPOP_E_ARG, std::string("unknown engine option ") + name};
     });
 }
 
@@ -1802,7 +1771,7 @@ int fqlpop_get_engine_option(const char* name, int* value) {
                 *value = g_engine_opts.*o.field;
                 return;
             }
-        throw FqErr{FQLPOP_E_ARG, std::string("unknown engine option ") + name};
+        throw Err{FQLPOP_E_ARG, std::string("unknown engine option ") + name};
     });
 }
 
@@ -1871,7 +1840,7 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         ARGCHK(cfg->num_qs >= 1 && cfg->num_qs <= 4, "num_qs must be in [1, 4]");
         ARGCHK(cfg->flow_steps >= 2, "flow_steps must be >= 2");
         if (cfg->actor_layer_norm)
-            throw FqErr{FQLPOP_E_UNSUPPORTED, "actor_layer_norm is not supported yet (reference default False)"};
+            throw Err{FQLPOP_E_UNSUPPORTED, "actor_layer_norm is not supported yet (reference default False)"};
         auto h = std::make_unique<fqlpop>();
         h->cfg = *cfg;
         h->n = n_members;
@@ -1898,14 +1867,7 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         // hands a graph's parallel branches to a pool of streams and can index past that pool
         // when more than one of them shares the launch stream's hardware queue (a crash inside
         // hipGraphLaunch)
-        HIPCHK(hipStreamCreateWithFlags(&h->sM, hipStreamNonBlocking));
-        if (step_streams(eo) == 1) {
-            h->sF = h->sB = h->sX = h->sM;
-        } else {
-            HIPCHK(hipStreamCreateWithFlags(&h->sF, hipStreamNonBlocking));
-            HIPCHK(hipStreamCreateWithFlags(&h->sB, hipStreamNonBlocking));
-            HIPCHK(hipStreamCreateWithFlags(&h->sX, hipStreamNonBlocking));
-        }
+        h->make_streams(step_streams(eo));
         h->ev_pool.resize(64);
         h->euler_fused = euler_flow_supported(H, L, D, A, B) && !h->bc.ln && eo.euler_fused;
         h->stream_fwd = stream_fwd_supported(H, L, D + A + 1, A, B) && eo.stream_fwd;
@@ -1923,19 +1885,21 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         // the stamps go straight to mapped host memory: the host reads them after the step's
         // event, with no device-to-host copy (a copy kernel) interleaved with the steps
         const size_t pb = sizeof(unsigned long long) * 4 * h->probe_blocks * h->probe_pairs;
-        HIPCHK(hipHostMalloc((void**)&h->probe_host, pb, hipHostMallocMapped | hipHostMallocCoherent));
+        constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
+        using Stamps = HostBuf<unsigned long long>;
+        h->probe_host = Stamps(4 * h->probe_blocks * h->probe_pairs, kMapped, "probe stamps");
 #ifdef FQ_PHASE_PROBE  // the kernels write the phase stamps only in this build (make PHASE=1)
         if (const char* e = diag_env("FQLPOP_PHASE_PROBE"); e != nullptr && e[0] == '1') {
             // the critic backward's blocks: 2B columns in 16-column tiles per ensemble member
             h->phase_blocks = (long long)(2 * cfg->batch_size / 16) * E * n_members;
             const size_t phb = sizeof(unsigned long long) * SB_PHASE_STRIDE * h->phase_blocks;
-            HIPCHK(hipHostMalloc((void**)&h->phase_host, phb, hipHostMallocMapped | hipHostMallocCoherent));
+            h->phase_host = Stamps(SB_PHASE_STRIDE * h->phase_blocks, kMapped, "phase stamps");
             std::memset(h->phase_host, 0, phb);
             HIPCHK(hipHostGetDevicePointer((void**)&h->phase_dev, h->phase_host, 0));
             if (h->euler_fused && cfg->flow_steps <= 11) {
                 h->ephase_blocks = (long long)(cfg->batch_size / 16) * n_members * 8;  // (split: up to 8 per tile)
                 const size_t eb = sizeof(unsigned long long) * EF_PHASE_STRIDE * h->ephase_blocks;
-                HIPCHK(hipHostMalloc((void**)&h->ephase_host, eb, hipHostMallocMapped | hipHostMallocCoherent));
+                h->ephase_host = Stamps(EF_PHASE_STRIDE * h->ephase_blocks, kMapped, "Euler phase stamps");
                 std::memset(h->ephase_host, 0, eb);
                 HIPCHK(hipHostGetDevicePointer((void**)&h->ephase_dev, h->ephase_host, 0));
             }
@@ -1943,31 +1907,33 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
 #endif
         std::memset(h->probe_host, 0, pb);
         HIPCHK(hipHostGetDevicePointer((void**)&h->probe_slots, h->probe_host, 0));
-        for (auto& e : h->probe_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHK(hipStreamCreateWithFlags(&h->probe_stream, hipStreamNonBlocking));
-        for (auto& e : h->ev_pool) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t* e : {&h->ev_sample, &h->ev_bcfwd, &h->ev_bcloss, &h->ev_flow, &h->ev_bdone})
-            HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        HIPCHK(hipEventCreate(&h->ev_t0));
-        HIPCHK(hipEventCreate(&h->ev_t1));
+        for (auto& e : h->probe_done) e = Event<>(hipEventDisableTiming);
+        h->probe_stream = Stream<>::create();
+        for (auto& e : h->ev_pool) e = Event<>(hipEventDisableTiming);
+        for (Event<>* e : {&h->ev_sample, &h->ev_bcfwd, &h->ev_bcloss, &h->ev_flow, &h->ev_bdone})
+            *e = Event<>(hipEventDisableTiming);
+        h->ev_t0 = Event<>(hipEventDefault);
+        h->ev_t1 = Event<>(hipEventDefault);
 
         const int n = h->n;
-        for (float*& pb : h->params_buf) {
-            HIPCHK(hipMalloc(&pb, sizeof(float) * h->P * n));
-            HIPCHK(hipMemset(pb, 0, sizeof(float) * h->P * n));
+        const size_t Pn = (size_t)h->P * n;
+        for (auto& pb : h->params_buf) {
+            pb = DevBuf<float>(Pn, "parameters");
+            HIPCHK(hipMemset(pb, 0, sizeof(float) * Pn));
         }
         h->params = h->params_buf[0];
         h->params_nx = h->params_buf[1];
-        HIPCHK(hipMalloc(&h->grads, sizeof(float) * h->P * n));
-        HIPCHK(hipMalloc(&h->adam_m, sizeof(float) * h->P * n));
-        HIPCHK(hipMalloc(&h->adam_v, sizeof(float) * h->P * n));
-        HIPCHK(hipMalloc(&h->target, sizeof(float) * h->PT * n));
-        HIPCHK(hipMemset(h->grads, 0, sizeof(float) * h->P * n));
-        HIPCHK(hipMalloc(&h->count, sizeof(int) * n));
-        HIPCHK(hipMalloc(&h->seeds, sizeof(uint64_t) * n));
-        HIPCHK(hipMalloc(&h->skeys, sizeof(uint64_t) * n));
-        HIPCHK(hipMalloc(&h->alpha, sizeof(float) * n));
-        HIPCHK(hipMalloc(&h->slots, sizeof(int) * n));
+        h->grads = DevBuf<float>(Pn, "gradients");
+        h->adam_m = DevBuf<float>(Pn, "Adam first moments");
+        h->adam_v = DevBuf<float>(Pn, "Adam second moments");
+        h->target_buf = DevBuf<float>((size_t)h->PT * n, "target critic");
+        h->target = h->target_buf;
+        HIPCHK(hipMemset(h->grads, 0, sizeof(float) * Pn));
+        h->count = DevBuf<int>(n, "step counts");
+        h->seeds = DevBuf<uint64_t>(n, "member seeds");
+        h->skeys = DevBuf<uint64_t>(n, "sampler keys");
+        h->alpha = DevBuf<float>(n, "member alphas");
+        h->slots = DevBuf<int>(n, "active slots");
         build_chunks(h.get());
 
         const int Kc = D + A, Kb = D + A + 1, B2 = 2 * B, B3 = 3 * B;
@@ -2043,11 +2009,12 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
             for (int si = 0; si < SITE_N; ++si) {
                 auto& st = h->split_site[si];
                 st.clusters = std::min(kSplitMaxClusters, tiles_per_member[si] * n);
-                HIPCHK(hipMalloc(&st.xch, split_cluster_bytes() * st.clusters));
+                st.xch = DevBuf<unsigned long long>(split_cluster_bytes() * st.clusters / sizeof(unsigned long long),
+                                                    "split exchange area");
                 HIPCHK(hipMemset(st.xch, 0, split_cluster_bytes() * st.clusters));  // tag 0 matches no hand-off
-                HIPCHK(hipMalloc(&st.cnt, sizeof(unsigned) * split_counter_stride() * (st.clusters + 2)));
+                st.cnt = DevBuf<unsigned>(split_counter_stride() * (st.clusters + 2), "split arrival counters");
                 HIPCHK(hipMemset(st.cnt, 0, sizeof(unsigned) * split_counter_stride() * (st.clusters + 2)));
-                HIPCHK(hipMalloc(&st.gen, 64));
+                st.gen = DevBuf<unsigned>(64 / sizeof(unsigned), "split generation word");
                 HIPCHK(hipMemset(st.gen, 0, 64));
             }
             // the split Euler flow's layer-0 accumulators: 32 KB per block, for the largest split
@@ -2058,11 +2025,12 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
                     if (F > 1) h->euler_pre0_blocks = std::max(h->euler_pre0_blocks, (long long)(B / 16) * nz * F);
                 }
                 if (h->euler_pre0_blocks > 0)
-                    HIPCHK(hipMalloc(&h->euler_pre0, sizeof(float) * split_euler_pre0_floats() * h->euler_pre0_blocks));
+                    h->euler_pre0 = DevBuf<float>(split_euler_pre0_floats() * h->euler_pre0_blocks,
+                                                  "split Euler layer-0 accumulators");
             }
             // the error word lives in host memory so that every entry point can test it without a
             // device-to-host copy (fqlpop_step does, before it enqueues more steps)
-            HIPCHK(hipHostMalloc((void**)&h->split_err_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+            h->split_err_host = HostBuf<unsigned>(64 / sizeof(unsigned), kMapped, "split error word");
             std::memset(h->split_err_host, 0, 64);
             HIPCHK(hipHostGetDevicePointer((void**)&h->split_err, h->split_err_host, 0));
         }
@@ -2099,40 +2067,7 @@ int fqlpop_destroy(fqlpop_t* h) {
         if (!h) return;
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (auto& kv : h->graphs)
-            if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        for (float* p : h->allocs) (void)hipFree(p);
-        for (void* p : {(void*)h->params_buf[0], (void*)h->params_buf[1], (void*)h->res_ids, (void*)h->grads, (void*)h->adam_m, (void*)h->adam_v, (void*)h->target,
-                        (void*)h->count, (void*)h->seeds, (void*)h->skeys, (void*)h->alpha, (void*)h->slots, (void*)h->stats,
-                        (void*)h->chunks, (void*)h->chunk_leaf, (void*)h->leaf_first, (void*)h->sp_params,
-                        (void*)h->tp_params, (void*)h->ens_sp, (void*)h->ens_tp, (void*)h->ens_nets})
-            if (p) (void)hipFree(p);
-        for (auto& d : h->ds)
-            for (float* p : {d.obs, d.act, d.rew, d.mask, d.nobs})
-                if (p) (void)hipFree(p);
-        for (auto& st : h->split_site) {
-            if (st.xch) (void)hipFree(st.xch);
-            if (st.cnt) (void)hipFree(st.cnt);
-            if (st.gen) (void)hipFree(st.gen);
-        }
-        if (h->euler_pre0) (void)hipFree(h->euler_pre0);
-        for (void* p : {(void*)h->synth.obs, (void*)h->synth.act, (void*)h->synth.rew, (void*)h->synth.mask,
-                        (void*)h->synth.nobs, (void*)h->synth.ctr, (void*)h->synth_ratio, (void*)h->synth_ws})
-            if (p) (void)hipFree(p);
-        for (int i = 0; i < fqlpop::kSynthStage; ++i) {
-            if (h->synth_start_host[i]) (void)hipHostFree(h->synth_start_host[i]);
-            if (h->synth_start_ev[i]) (void)hipEventDestroy(h->synth_start_ev[i]);
-        }
-        if (h->split_err_host) (void)hipHostFree(h->split_err_host);
-        for (hipEvent_t e : {h->ev_sample, h->ev_bcfwd, h->ev_bcloss, h->ev_flow, h->ev_bdone, h->ev_t0, h->ev_t1})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->probe_done)
-            if (e) (void)hipEventDestroy(e);
-        if (h->probe_stream) (void)hipStreamDestroy(h->probe_stream);
-        if (h->probe_host) (void)hipHostFree(h->probe_host);
-        if (h->phase_host) {
-            (void)hipDeviceSynchronize();
+        if (h->phase_host) {  // the diagnostic reports read the mapped buffers: before the release
             if (const char* f = diag_env("FQLPOP_PHASE_DUMP")) {  // raw stamps for offline analysis
                 if (FILE* fp = std::fopen(f, "wb")) {
                     std::fwrite(h->phase_host, sizeof(unsigned long long), (size_t)SB_PHASE_STRIDE * h->phase_blocks, fp);
@@ -2142,19 +2077,13 @@ int fqlpop_destroy(fqlpop_t* h) {
             const NetLayout* nets[3] = {&h->critic, &h->bc, &h->os};
             const char* const names[3] = {"critic", "BC", "one-step"};
             phase_report(h->phase_host, h->phase_blocks, h->L, nets[phase_net()]->ln, names[phase_net()]);
-            (void)hipHostFree(h->phase_host);
         }
         if (h->ephase_host) {
             if (split_plan(h, h->nz).F[SITE_EULER] > 1)
                 split_euler_phase_report(h->ephase_host, h->ephase_blocks, h->L, h->S - 1);
             else
                 euler_phase_report(h->ephase_host, h->ephase_blocks, h->L, h->S - 1);
-            (void)hipHostFree(h->ephase_host);
         }
-        if (h->sX && h->sX != h->sM) (void)hipStreamDestroy(h->sX);
-        if (h->sF && h->sF != h->sM) (void)hipStreamDestroy(h->sF);
-        if (h->sB && h->sB != h->sM) (void)hipStreamDestroy(h->sB);
-        if (h->sM) (void)hipStreamDestroy(h->sM);
         delete h;
     });
 }
@@ -2167,24 +2096,19 @@ int fqlpop_set_dataset(fqlpop_t* h, int which, const float* obs, const float* ac
         ARGCHK(n_rows > 0 && n_rows < (1LL << 32), "n_rows out of range");
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipDeviceSynchronize());
-        auto& d = h->ds[which];
-        for (float* p : {d.obs, d.act, d.rew, d.mask, d.nobs})
-            if (p) HIPCHK(hipFree(p));
+        drop_graphs(h);  // graphs bake dataset pointers in
         const long long n = n_rows;
         const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        auto up = [&](float** dst, const float* src, long long cnt) {
-            HIPCHK(hipMalloc(dst, sizeof(float) * cnt));
-            HIPCHK(hipMemcpy(*dst, src, sizeof(float) * cnt, kind));
-        };
-        up(&d.obs, obs, n * h->D);
-        up(&d.act, act, n * h->A);
-        up(&d.rew, rew, n);
-        up(&d.mask, mask, n);
-        up(&d.nobs, next_obs, n * h->D);
-        d.rows = n;
-        // graphs bake dataset pointers in: drop them
-        for (auto& kv : h->graphs)
-            if (kv.second.exec) { HIPCHK(hipGraphExecDestroy(kv.second.exec)); kv.second.exec = nullptr; }
+        // a failed upload leaves no dataset (rows 0): the step and the collects refuse that
+        replace_released(h->ds[which], [&] {
+            auto d = PopDataset<>::make(n, h->D, h->A);
+            HIPCHK(hipMemcpy(d.obs, obs, sizeof(float) * n * h->D, kind));
+            HIPCHK(hipMemcpy(d.act, act, sizeof(float) * n * h->A, kind));
+            HIPCHK(hipMemcpy(d.rew, rew, sizeof(float) * n, kind));
+            HIPCHK(hipMemcpy(d.mask, mask, sizeof(float) * n, kind));
+            HIPCHK(hipMemcpy(d.nobs, next_obs, sizeof(float) * n * h->D, kind));
+            return d;
+        });
     });
 }
 
@@ -2207,7 +2131,7 @@ int fqlpop_step(fqlpop_t* h, int n_steps) {
         ARGCHK(n_steps >= 0, "n_steps must be >= 0");
         if (split_error_pending(h)) sync_all_streams(h);  // (no copy, no sync when clear)
         check_split_error(h, -1, true);  // a failed split launch stops training until restored
-        if (h->ds[0].rows == 0) throw FqErr{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
+        if (h->ds[0].rows == 0) throw Err{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
         HIPCHK(hipSetDevice(h->device));
         for (int i = 0; i < n_steps; ++i) {
             if (h->probe) {
@@ -2256,7 +2180,7 @@ int fqlpop_total_loss(fqlpop_t* h, const float* batch, const float* noise) {
         ARGCHK(batch != nullptr || noise == nullptr, "noise without batch is not supported");
         HIPCHK(hipSetDevice(h->device));
         if (h->nz == 0) return;
-        if (!batch && h->ds[0].rows == 0 && h->ds[1].rows == 0) throw FqErr{FQLPOP_E_STATE, "no dataset set"};
+        if (!batch && h->ds[0].rows == 0 && h->ds[1].rows == 0) throw Err{FQLPOP_E_STATE, "no dataset set"};
         stage_injected(h, batch, noise);
         run(h, false, batch != nullptr, noise != nullptr);
         if (batch) HIPCHK(hipStreamSynchronize(h->sM));
@@ -2306,12 +2230,10 @@ int fqlpop_sample_actions(fqlpop_t* h, int member, const float* obs, int64_t n, 
                 if (j + 1 < A) x[(size_t)(D + j + 1) * M + r] = z1;
             }
         }
-        float *dx = nullptr, *dout = nullptr, *dg = nullptr;
-        int* dslot = nullptr;
-        HIPCHK(hipMalloc(&dx, sizeof(float) * x.size()));
-        HIPCHK(hipMalloc(&dout, sizeof(float) * A * M));
-        HIPCHK(hipMalloc(&dg, sizeof(float) * 2 * H * M));
-        HIPCHK(hipMalloc(&dslot, sizeof(int)));
+        const DevBuf<float> dx(x.size(), "sample_actions input");
+        const DevBuf<float> dout((size_t)A * M, "sample_actions output");
+        const DevBuf<float> dg((size_t)2 * H * M, "sample_actions activations");
+        const DevBuf<int> dslot(1, "sample_actions slot");
         HIPCHK(hipMemcpy(dx, x.data(), sizeof(float) * x.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dslot, &member, sizeof(int), hipMemcpyHostToDevice));
         const NetLayout& N = h->os;
@@ -2326,7 +2248,7 @@ int fqlpop_sample_actions(fqlpop_t* h, int member, const float* obs, int64_t n, 
             g.lda = H; g.ldb = (int)M; g.ldc = (int)M;
             g.ny = 1; g.nz = 1; g.slots = dslot;
             if (N.ln) {
-                throw FqErr{FQLPOP_E_UNSUPPORTED, "sample_actions with actor_layer_norm is not supported"};
+                throw Err{FQLPOP_E_UNSUPPORTED, "sample_actions with actor_layer_norm is not supported"};
             }
             gemm(LAYOUT_FWD, EPI_BIAS_GELU, g, h->sM);
         }
@@ -2344,7 +2266,6 @@ int fqlpop_sample_actions(fqlpop_t* h, int member, const float* obs, int64_t n, 
         HIPCHK(hipMemcpy(o.data(), dout, sizeof(float) * o.size(), hipMemcpyDeviceToHost));
         for (long long r = 0; r < n; ++r)
             for (int j = 0; j < A; ++j) out[r * A + j] = o[(size_t)j * M + r];
-        (void)hipFree(dx); (void)hipFree(dout); (void)hipFree(dg); (void)hipFree(dslot);
     });
 }
 
@@ -2487,7 +2408,7 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
         (void)absorb_split_error(h);
         for (int i = 0; i < n_pairs; ++i)
             if (h->poisoned[src[i]])
-                throw FqErr{FQLPOP_E_STATE, "member " + std::to_string(src[i]) + "'s state was written by a failed "
+                throw Err{FQLPOP_E_STATE, "member " + std::to_string(src[i]) + "'s state was written by a failed "
                                             "split launch; restore it before cloning from it"};
         CloneArgs base{};
         auto arena = [&](const float* s, const float* s_idle, float* d, long long stride) {
@@ -2560,7 +2481,7 @@ int fqlpop_sync(fqlpop_t* h) {
         HIPCHK(hipSetDevice(h->device));
         sync_all_streams(h);
         // reported once here; the members stay poisoned for step / get_state / get_count / read_info
-        if (absorb_split_error(h)) throw FqErr{FQLPOP_E_STATE, kSplitFailMsg};
+        if (absorb_split_error(h)) throw Err{FQLPOP_E_STATE, kSplitFailMsg};
     });
 }
 
@@ -2568,9 +2489,9 @@ int fqlpop_debug_fail_split(fqlpop_t* h) {
     return guard([&] {
         ARGCHK(h, "null handle");
         HIPCHK(hipSetDevice(h->device));
-        if (!h->split_err_host) throw FqErr{FQLPOP_E_STATE, "this population runs no split launch"};
+        if (!h->split_err_host) throw Err{FQLPOP_E_STATE, "this population runs no split launch"};
         sync_all_streams(h);
-        __atomic_store_n(h->split_err_host, 1u, __ATOMIC_RELEASE);
+        __atomic_store_n(h->split_err_host.get(), 1u, __ATOMIC_RELEASE);
     });
 }
 
@@ -2737,8 +2658,7 @@ int fqlpop_set_env_model(fqlpop_t* h, const fqlpop_envmodel_config* cfg, const f
         ARGCHK(cfg->obs_dim == h->D && cfg->action_dim == h->A, "env-model obs/action dims differ from the agent's");
         std::vector<int> sp, tp;
         envmodel_dims(cfg, sp, tp);
-        RolloutArgs& r = h->em_args;
-        r = RolloutArgs{};
+        RolloutArgs r{};
         const long long nsp = envmodel_layout(sp, true, r.sp_w, r.sp_b, &r.sp_ln_bias, &r.sp_ln_scale);
         long long lb = 0, ls = 0;
         const long long ntp = envmodel_layout(tp, false, r.tp_w, r.tp_b, &lb, &ls);
@@ -2748,16 +2668,14 @@ int fqlpop_set_env_model(fqlpop_t* h, const fqlpop_envmodel_config* cfg, const f
         for (size_t i = 0; i < sp.size(); ++i) r.sp_dims[i] = sp[i];
         for (size_t i = 0; i < tp.size(); ++i) r.tp_dims[i] = tp[i];
         HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipDeviceSynchronize());
-        if (h->sp_params) (void)hipFree(h->sp_params);
-        if (h->tp_params) (void)hipFree(h->tp_params);
-        h->sp_params = h->tp_params = nullptr;
-        HIPCHK(hipMalloc(&h->sp_params, sizeof(float) * nsp));
-        HIPCHK(hipMalloc(&h->tp_params, sizeof(float) * ntp));
-        HIPCHK(hipMemcpy(h->sp_params, sp_params, sizeof(float) * nsp, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->tp_params, tp_params, sizeof(float) * ntp, hipMemcpyHostToDevice));
-        h->em = *cfg;
-        h->em_set = true;
+        // a refusal above and a failure below leave the earlier model as it was
+        replace_built(h->em, [&] {
+            auto m = PopEnvModel<RolloutArgs>::make(r, *cfg, nsp, ntp);
+            HIPCHK(hipMemcpy(m.sp, sp_params, sizeof(float) * nsp, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(m.tp, tp_params, sizeof(float) * ntp, hipMemcpyHostToDevice));
+            HIPCHK(hipDeviceSynchronize());  // the earlier model's last reader is done before it goes
+            return m;
+        });
     });
 }
 
@@ -2765,20 +2683,20 @@ namespace {
 // What every rollout of the active members under fqlpop_set_env_model's model needs
 // (fqlpop_rollout, _rollout_record, fqlpop_synth_collect).
 void rollout_check(fqlpop_t* h) {
-    if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
+    if (!h->em) throw Err{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
     if (!rollout_supported(h->H, h->L, h->D, h->A))
-        throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
-    if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+    if (h->os.ln) throw Err{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
 }
 // The launch arguments of such a rollout but for its buffers (init_obs, noise and the
 // outputs: device pointers the caller sets): the current parameters, the env model, the
 // active members.
 RolloutArgs rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed) {
-    RolloutArgs r = h->em_args;
+    RolloutArgs r = h->em.args;
     r.params = h->params; r.P = h->P; r.os_off = h->os.off;
     for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
     r.D = h->D; r.A = h->A; r.L = h->L;
-    r.sp = h->sp_params; r.tp = h->tp_params;
+    r.sp = h->em.sp; r.tp = h->em.tp;
     r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
     r.nz = h->nz; r.slots = h->slots;
     return r;
@@ -2786,23 +2704,23 @@ RolloutArgs rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed) 
 // What every rollout under the ensemble needs (fqlpop_rollout_ensemble, _record,
 // fqlpop_synth_collect_ensemble).
 void ens_check(fqlpop_t* h) {
-    if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
+    if (h->ens.n == 0) throw Err{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
     if (!rollout_supported(h->H, h->L, h->D, h->A))
-        throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
-    if (h->os.ln) throw FqErr{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
+        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+    if (h->os.ln) throw Err{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
 }
 // The launch arguments of such a rollout but for its buffers (init_obs, noise, choice and
 // the outputs: device pointers the caller sets), as rollout_args for the single model.
 RolloutEnsArgs ens_rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed, int mode) {
     RolloutEnsArgs e{};
     RolloutArgs& r = e.base;
-    r = h->ens_args;
+    r = h->ens.args;
     r.params = h->params; r.P = h->P; r.os_off = h->os.off;
     for (int l = 0; l <= h->L; ++l) { r.w_off[l] = h->os.W[l]; r.b_off[l] = h->os.b[l]; }
     r.D = h->D; r.A = h->A; r.L = h->L;
     r.n_envs = n_envs; r.max_steps = max_steps; r.seed = seed; r.member_seeds = h->skeys;
     r.nz = h->nz; r.slots = h->slots;
-    e.nets = h->ens_nets; e.n_models = h->ens_n; e.mode = mode;
+    e.nets = h->ens.nets; e.n_models = h->ens.n; e.mode = mode;
     return e;
 }
 // fqlpop_rollout / fqlpop_rollout_record (the latter with both trace outputs)
@@ -2817,21 +2735,21 @@ void rollout_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, 
         const int nz = h->nz, D = h->D, A = h->A;
         if (nz == 0) return;
         RolloutArgs r = rollout_args(h, n_envs, max_steps, seed);
-        float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_tobs = nullptr,
-              *d_tact = nullptr;
+        using Scratch = DevBuf<float>;  // per call; null where an optional input / output is absent
+        Scratch d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact;
         const size_t n_traj = (size_t)nz * max_steps * n_envs;
         const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
-        HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
-        HIPCHK(hipMalloc(&d_out, sizeof(float) * nz * n_envs * 2));
+        d_obs = Scratch((size_t)n_envs * D, "rollout start observations");
+        d_out = Scratch((size_t)nz * n_envs * 2, "rollout outputs");
         HIPCHK(hipMemcpy(d_obs, init_obs, sizeof(float) * n_envs * D, hipMemcpyHostToDevice));
         if (noise) {
-            HIPCHK(hipMalloc(&d_noise, sizeof(float) * n_noise));
+            d_noise = Scratch(n_noise, "rollout noise");
             HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
         }
-        if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * nz * n_envs * D));
+        if (out_obs) d_oobs = Scratch((size_t)nz * n_envs * D, "rollout final observations");
         if (out_traj_obs) {
-            HIPCHK(hipMalloc(&d_tobs, sizeof(float) * n_traj * D));
-            HIPCHK(hipMalloc(&d_tact, sizeof(float) * n_traj * A));
+            d_tobs = Scratch(n_traj * D, "rollout observation trace");
+            d_tact = Scratch(n_traj * A, "rollout action trace");
             HIPCHK(hipMemsetAsync(d_tobs, 0, sizeof(float) * n_traj * D, h->sM));
             HIPCHK(hipMemsetAsync(d_tact, 0, sizeof(float) * n_traj * A, h->sM));
         }
@@ -2846,8 +2764,6 @@ void rollout_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, 
             HIPCHK(hipMemcpy(out_traj_obs, d_tobs, sizeof(float) * n_traj * D, hipMemcpyDeviceToHost));
             HIPCHK(hipMemcpy(out_traj_act, d_tact, sizeof(float) * n_traj * A, hipMemcpyDeviceToHost));
         }
-        for (float* p : {d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact})
-            if (p) (void)hipFree(p);
     }
 }
 }  // namespace
@@ -2869,13 +2785,7 @@ int fqlpop_rollout_record(fqlpop_t* h, const float* init_obs, int n_envs, int ma
 namespace {
 void need_rings(fqlpop_t* h) {
     ARGCHK(h != nullptr, "null handle");
-    if (!h->synth.obs) throw FqErr{FQLPOP_E_STATE, "no synthetic-transition rings (fqlpop_synth_create)"};
-}
-// floats per ring row over the five fields
-long long synth_row_floats(const fqlpop* h) { return 2LL * h->D + h->A + 2; }
-void drop_graphs(fqlpop* h) {
-    for (auto& kv : h->graphs)
-        if (kv.second.exec) { HIPCHK(hipGraphExecDestroy(kv.second.exec)); kv.second.exec = nullptr; }
+    if (!h->synth.obs) throw Err{FQLPOP_E_STATE, "no synthetic-transition rings (fqlpop_synth_create)"};
 }
 }  // namespace
 
@@ -2883,32 +2793,18 @@ int fqlpop_synth_create(fqlpop_t* h, int64_t capacity_rows) {
     return guard([&] {
         ARGCHK(h != nullptr, "null handle");
         ARGCHK(capacity_rows >= 1 && capacity_rows < (1LL << 32), "capacity_rows must be in 1..2^32-1");
-        if (h->synth.obs) throw FqErr{FQLPOP_E_STATE, "the synthetic-transition rings exist already"};
+        if (h->synth.obs) throw Err{FQLPOP_E_STATE, "the synthetic-transition rings exist already"};
         HIPCHK(hipSetDevice(h->device));
         sync_all_streams(h);
         const long long cap = capacity_rows, n = h->n;
-        const unsigned long long bytes = sizeof(float) * (unsigned long long)n * cap * synth_row_floats(h);
-        SynthRing r{};
-        r.cap = cap;
-        float** fields[5] = {&r.obs, &r.act, &r.rew, &r.mask, &r.nobs};
-        const long long width[5] = {h->D, h->A, 1, 1, h->D};
-        bool ok = true;
-        for (int i = 0; i < 5 && ok; ++i) ok = hipMalloc(fields[i], sizeof(float) * n * cap * width[i]) == hipSuccess;
-        ok = ok && hipMalloc(&r.ctr, sizeof(long long) * SYNTH_CTR * n) == hipSuccess;
-        if (ok && !h->synth_ratio) ok = hipMalloc(&h->synth_ratio, sizeof(float)) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (float** f : fields)
-                if (*f) (void)hipFree(*f);
-            if (r.ctr) (void)hipFree(r.ctr);
-            throw FqErr{FQLPOP_E_HIP, "synthetic-transition rings: allocating " + std::to_string(bytes) + " bytes (" +
-                                          std::to_string(n) + " members x " + std::to_string(cap) + " rows) failed"};
-        }
-        r.ratio = h->synth_ratio;
+        auto rings = PopSynthRings<>::make(n, cap, h->D, h->A, SYNTH_CTR);  // aside: a failure leaves none
+        if (!h->synth_ratio) h->synth_ratio = DevBuf<float>(1, "synthetic-transition ratio");
         const float one = 1.0f;
-        HIPCHK(hipMemset(r.ctr, 0, sizeof(long long) * SYNTH_CTR * n));
+        HIPCHK(hipMemset(rings.ctr, 0, sizeof(long long) * SYNTH_CTR * n));
         HIPCHK(hipMemcpy(h->synth_ratio, &one, sizeof(float), hipMemcpyHostToDevice));
-        h->synth = r;
+        h->synth_rings = std::move(rings);
+        const auto& r = h->synth_rings;
+        h->synth = SynthRing{r.obs, r.act, r.rew, r.mask, r.nobs, r.cap, r.ctr, h->synth_ratio};
         drop_graphs(h);  // a captured training step has the ring-less sampler baked in
     });
 }
@@ -2932,7 +2828,7 @@ void synth_collect_run(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, 
                        bool ensemble, float penalty) {
     {
         need_rings(h);
-        if (h->ds[0].rows == 0) throw FqErr{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
+        if (h->ds[0].rows == 0) throw Err{FQLPOP_E_STATE, "no training dataset set (fqlpop_set_dataset)"};
         if (ensemble) ens_check(h);
         else rollout_check(h);
         ARGCHK(std::isfinite(penalty) && penalty >= 0.0f, "penalty must be finite and >= 0");
@@ -2949,46 +2845,30 @@ void synth_collect_run(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, 
         const long long nb = n_branches, T = horizon, n = h->n, D = h->D, A = h->A;
         const bool unc = ensemble && penalty > 0.0f;
         const long long need = nb * D + n * nb * (2 + D) + n * T * nb * (D + A + (unc ? 1 : 0));
-        if (need > h->synth_ws_floats) {  // grown on first use (the earlier collects read the old one)
+        if (need > h->synth_ws.floats) {  // grown on first use (the earlier collects read the old one)
             HIPCHK(hipStreamSynchronize(h->sM));
-            if (h->synth_ws) (void)hipFree(h->synth_ws);
-            h->synth_ws = nullptr;
-            h->synth_ws_floats = 0;
-            if (hipMalloc(&h->synth_ws, sizeof(float) * need) != hipSuccess) {
-                (void)hipGetLastError();
-                throw FqErr{FQLPOP_E_HIP, "collect workspace: allocating " + std::to_string(sizeof(float) * need) +
-                                              " bytes failed"};
-            }
-            h->synth_ws_floats = need;
+            replace_released(h->synth_ws, [&] { return PopCollectWs<>::make(need); });
         }
         const long long* d_start = nullptr;
         int stage = -1;
         if (start_rows) {
-            if (nb > h->synth_start_cap) {
+            auto& st = h->synth_start;
+            if (nb > st.cap) {
                 HIPCHK(hipStreamSynchronize(h->sM));
-                for (int i = 0; i < fqlpop::kSynthStage; ++i) {
-                    if (h->synth_start_host[i]) (void)hipHostFree(h->synth_start_host[i]);
-                    h->synth_start_host[i] = nullptr;
-                    h->synth_start_used[i] = false;
-                }
-                h->synth_start_cap = 0;
-                for (int i = 0; i < fqlpop::kSynthStage; ++i) {
-                    HIPCHK(hipHostMalloc((void**)&h->synth_start_host[i], sizeof(long long) * nb, hipHostMallocMapped));
-                    if (!h->synth_start_ev[i])
-                        HIPCHK(hipEventCreateWithFlags(&h->synth_start_ev[i], hipEventDisableTiming));
-                }
-                h->synth_start_cap = nb;
+                for (auto& ev : h->synth_start_ev)
+                    if (!ev) ev = Event<>(hipEventDisableTiming);
+                replace_released(st, [&] { return PopStartStage<fqlpop::kSynthStage>::make(nb, hipHostMallocMapped); });
             }
             stage = h->synth_start_next;
             h->synth_start_next = (stage + 1) % fqlpop::kSynthStage;
             // the buffer's last reader (the start gather of kSynthStage collects ago) has run
-            if (h->synth_start_used[stage]) HIPCHK(hipEventSynchronize(h->synth_start_ev[stage]));
-            for (int e = 0; e < n_branches; ++e) h->synth_start_host[stage][e] = start_rows[e];
+            if (st.used[stage]) HIPCHK(hipEventSynchronize(h->synth_start_ev[stage]));
+            for (int e = 0; e < n_branches; ++e) st.host[stage][e] = start_rows[e];
             long long* dp = nullptr;
-            HIPCHK(hipHostGetDevicePointer((void**)&dp, h->synth_start_host[stage], 0));
+            HIPCHK(hipHostGetDevicePointer((void**)&dp, st.host[stage], 0));
             d_start = dp;
         }
-        float* w = h->synth_ws;
+        float* w = h->synth_ws.buf;
         float* d_init = w; w += nb * D;
         float* d_out = w; w += n * nb * 2;
         float* d_oobs = w; w += n * nb * D;
@@ -2999,7 +2879,7 @@ void synth_collect_run(fqlpop_t* h, int n_branches, int horizon, uint64_t seed, 
         launch_synth_starts(h->ds[0].obs, h->ds[0].rows, h->D, d_start, seed, n_branches, d_init, s);
         if (stage >= 0) {
             HIPCHK(hipEventRecord(h->synth_start_ev[stage], s));
-            h->synth_start_used[stage] = true;
+            h->synth_start.used[stage] = true;
         }
         // fqlpop_rollout_record's launch on the handle's buffers (noise NULL).  The traces are
         // not zeroed: the append reads only the entries the rollout wrote (t < episode length).
@@ -3089,23 +2969,22 @@ int fqlpop_synth_clear(fqlpop_t* h, int member) {
 int fqlpop_envmodel_step(fqlpop_t* h, const float* obs, const float* actions, int n, float* next_obs, float* logits) {
     return guard([&] {
         ARGCHK(h && obs && actions && next_obs && logits && n > 0, "bad argument");
-        if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
+        if (!h->em) throw Err{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
         ARGCHK(h->D + h->A <= 64 && h->D <= 64 && h->A <= 8, "obs_dim + action_dim must be <= 64");
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->sM));
         const int D = h->D, A = h->A;
-        RolloutArgs r = h->em_args;
+        RolloutArgs r = h->em.args;
         r.params = h->params; r.P = h->P; r.os_off = h->os.off;
         r.D = D; r.A = A; r.L = h->L;
-        r.sp = h->sp_params; r.tp = h->tp_params;
+        r.sp = h->em.sp; r.tp = h->em.tp;
         r.n_envs = n; r.max_steps = 1; r.seed = 0; r.member_seeds = h->skeys;
         r.nz = 1; r.slots = h->slots;  // any slot: the actor is not run
-        float *d_obs = nullptr, *d_act = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_logit = nullptr;
-        HIPCHK(hipMalloc(&d_obs, sizeof(float) * n * D));
-        HIPCHK(hipMalloc(&d_act, sizeof(float) * n * A));
-        HIPCHK(hipMalloc(&d_out, sizeof(float) * n * 2));
-        HIPCHK(hipMalloc(&d_oobs, sizeof(float) * n * D));
-        HIPCHK(hipMalloc(&d_logit, sizeof(float) * n));
+        const DevBuf<float> d_obs((size_t)n * D, "env-model step observations");
+        const DevBuf<float> d_act((size_t)n * A, "env-model step actions");
+        const DevBuf<float> d_out((size_t)n * 2, "env-model step outputs");
+        const DevBuf<float> d_oobs((size_t)n * D, "env-model step next observations");
+        const DevBuf<float> d_logit((size_t)n, "env-model step logits");
         HIPCHK(hipMemcpy(d_obs, obs, sizeof(float) * n * D, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_act, actions, sizeof(float) * n * A, hipMemcpyHostToDevice));
         r.init_obs = d_obs; r.actions = d_act; r.out = d_out; r.out_obs = d_oobs; r.out_logit = d_logit;
@@ -3114,7 +2993,6 @@ int fqlpop_envmodel_step(fqlpop_t* h, const float* obs, const float* actions, in
         HIPCHK(hipStreamSynchronize(h->sM));
         HIPCHK(hipMemcpy(next_obs, d_oobs, sizeof(float) * n * D, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(logits, d_logit, sizeof(float) * n, hipMemcpyDeviceToHost));
-        for (float* p : {d_obs, d_act, d_out, d_oobs, d_logit}) (void)hipFree(p);
     });
 }
 
@@ -3125,7 +3003,7 @@ int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* acti
         ARGCHK(h && init_obs && actions && out_logits, "null argument");
         ARGCHK(n > 0 && T > 0, "n and T must be positive");
         ARGCHK(anchor_every >= 0, "anchor_every must be >= 0");
-        if (!h->em_set) throw FqErr{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
+        if (!h->em) throw Err{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
         ARGCHK(h->D + h->A <= 64 && h->D <= 64 && h->A <= 8, "obs_dim + action_dim must be <= 64");
         ARGCHK(anchor_every == 0 || anchor_obs, "anchor_every > 0 needs anchor_obs");
         ARGCHK(!out_err || next_obs, "out_err needs next_obs");
@@ -3135,31 +3013,31 @@ int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* acti
         HIPCHK(hipStreamSynchronize(h->sM));
         const size_t D = h->D, A = h->A, nT = (size_t)n * T;
         ReplayArgs r{};
-        r.em = h->em_args;
-        r.em.sp = h->sp_params; r.em.tp = h->tp_params;
+        r.em = h->em.args;
+        r.em.sp = h->em.sp; r.em.tp = h->em.tp;
         r.D = h->D; r.A = h->A; r.n = n; r.T = T; r.anchor_every = anchor_every;
-        float *d_obs = nullptr, *d_act = nullptr, *d_next = nullptr, *d_anchor = nullptr, *d_logit = nullptr,
-              *d_err = nullptr, *d_oobs = nullptr;
-        int* d_len = nullptr;
-        auto up = [&](float** d, const float* src, size_t cnt) {
-            HIPCHK(hipMalloc(d, sizeof(float) * cnt));
-            HIPCHK(hipMemcpy(*d, src, sizeof(float) * cnt, hipMemcpyHostToDevice));
+        // per-call scratch; null where an optional input / output is absent
+        DevBuf<float> d_obs, d_act, d_next, d_anchor, d_logit, d_err, d_oobs;
+        DevBuf<int> d_len;
+        auto up = [&](DevBuf<float>& d, const float* src, size_t cnt) {
+            d = DevBuf<float>(cnt, "replay input");
+            HIPCHK(hipMemcpy(d, src, sizeof(float) * cnt, hipMemcpyHostToDevice));
         };
-        auto zeros = [&](float** d, size_t cnt) {  // the kernel writes the steps t < length only
-            HIPCHK(hipMalloc(d, sizeof(float) * cnt));
-            HIPCHK(hipMemsetAsync(*d, 0, sizeof(float) * cnt, h->sM));
+        auto zeros = [&](DevBuf<float>& d, size_t cnt) {  // the kernel writes the steps t < length only
+            d = DevBuf<float>(cnt, "replay output");
+            HIPCHK(hipMemsetAsync(d, 0, sizeof(float) * cnt, h->sM));
         };
-        up(&d_obs, init_obs, n * D);
-        up(&d_act, actions, nT * A);
-        if (next_obs) up(&d_next, next_obs, nT * D);
-        if (anchor_every > 0) up(&d_anchor, anchor_obs, nT * D);
+        up(d_obs, init_obs, n * D);
+        up(d_act, actions, nT * A);
+        if (next_obs) up(d_next, next_obs, nT * D);
+        if (anchor_every > 0) up(d_anchor, anchor_obs, nT * D);
         if (lengths) {
-            HIPCHK(hipMalloc(&d_len, sizeof(int) * n));
+            d_len = DevBuf<int>((size_t)n, "replay lengths");
             HIPCHK(hipMemcpy(d_len, lengths, sizeof(int) * n, hipMemcpyHostToDevice));
         }
-        zeros(&d_logit, nT);
-        if (out_err) zeros(&d_err, nT * 2);
-        if (out_obs) zeros(&d_oobs, nT * D);
+        zeros(d_logit, nT);
+        if (out_err) zeros(d_err, nT * 2);
+        if (out_obs) zeros(d_oobs, nT * D);
         r.init_obs = d_obs; r.actions = d_act; r.next_obs = d_next; r.anchor_obs = d_anchor; r.lengths = d_len;
         r.out_logits = d_logit; r.out_err = d_err; r.out_obs = d_oobs;
         HIPCHK(hipEventRecord(h->ev_t0, h->sM));
@@ -3173,16 +3051,13 @@ int fqlpop_envmodel_replay(fqlpop_t* h, const float* init_obs, const float* acti
         HIPCHK(hipMemcpy(out_logits, d_logit, sizeof(float) * nT, hipMemcpyDeviceToHost));
         if (out_err) HIPCHK(hipMemcpy(out_err, d_err, sizeof(float) * nT * 2, hipMemcpyDeviceToHost));
         if (out_obs) HIPCHK(hipMemcpy(out_obs, d_oobs, sizeof(float) * nT * D, hipMemcpyDeviceToHost));
-        for (float* p : {d_obs, d_act, d_next, d_anchor, d_logit, d_err, d_oobs})
-            if (p) (void)hipFree(p);
-        if (d_len) (void)hipFree(d_len);
     });
 }
 
 int fqlpop_envmodel_replay_time(fqlpop_t* h, double* kernel_us) {
     return guard([&] {
         ARGCHK(h && kernel_us, "null argument");
-        if (h->replay_kernel_us < 0) throw FqErr{FQLPOP_E_STATE, "no fqlpop_envmodel_replay call yet"};
+        if (h->replay_kernel_us < 0) throw Err{FQLPOP_E_STATE, "no fqlpop_envmodel_replay call yet"};
         *kernel_us = h->replay_kernel_us;
     });
 }
@@ -3206,25 +3081,21 @@ int fqlpop_set_env_model_ensemble(fqlpop_t* h, const fqlpop_envmodel_config* cfg
         for (size_t i = 0; i < sp.size(); ++i) r.sp_dims[i] = sp[i];
         for (size_t i = 0; i < tp.size(); ++i) r.tp_dims[i] = tp[i];
         HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipDeviceSynchronize());
-        for (void* p : {(void*)h->ens_sp, (void*)h->ens_tp, (void*)h->ens_nets})
-            if (p) (void)hipFree(p);
-        h->ens_sp = h->ens_tp = nullptr;
-        h->ens_nets = nullptr;
-        h->ens_n = 0;
-        HIPCHK(hipMalloc(&h->ens_sp, sizeof(float) * nsp * n_models));
-        HIPCHK(hipMalloc(&h->ens_tp, sizeof(float) * ntp * n_models));
-        HIPCHK(hipMalloc(&h->ens_nets, sizeof(EnvModelNet) * n_models));
-        HIPCHK(hipMemcpy(h->ens_sp, sp_params, sizeof(float) * nsp * n_models, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->ens_tp, tp_params, sizeof(float) * ntp * n_models, hipMemcpyHostToDevice));
-        std::vector<EnvModelNet> nets((size_t)n_models, static_cast<const EnvModelNet&>(r));
-        for (int k = 0; k < n_models; ++k) {
-            nets[k].sp = h->ens_sp + (long long)k * nsp;
-            nets[k].tp = h->ens_tp + (long long)k * ntp;
-        }
-        HIPCHK(hipMemcpy(h->ens_nets, nets.data(), sizeof(EnvModelNet) * n_models, hipMemcpyHostToDevice));
-        h->ens_args = r;
-        h->ens_n = n_models;
+        // a refusal above and a failure below leave the earlier ensemble as it was
+        replace_built(h->ens, [&] {
+            auto e = PopEnvModelEnsemble<RolloutArgs, EnvModelNet>::make(r, n_models, nsp, ntp);
+            HIPCHK(hipMemcpy(e.sp, sp_params, sizeof(float) * nsp * n_models, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(e.tp, tp_params, sizeof(float) * ntp * n_models, hipMemcpyHostToDevice));
+            // (the move into the handle keeps the buffers' addresses)
+            std::vector<EnvModelNet> nets((size_t)n_models, static_cast<const EnvModelNet&>(r));
+            for (int k = 0; k < n_models; ++k) {
+                nets[k].sp = e.sp + (long long)k * nsp;
+                nets[k].tp = e.tp + (long long)k * ntp;
+            }
+            HIPCHK(hipMemcpy(e.nets, nets.data(), sizeof(EnvModelNet) * n_models, hipMemcpyHostToDevice));
+            HIPCHK(hipDeviceSynchronize());  // the earlier ensemble's last reader is done before it goes
+            return e;
+        });
     });
 }
 
@@ -3239,8 +3110,8 @@ void ens_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint
     ARGCHK(mode == FQLPOP_ENS_PER_MODEL || mode == FQLPOP_ENS_MIXED, "mode must be FQLPOP_ENS_PER_MODEL or FQLPOP_ENS_MIXED");
     ARGCHK(!(choice && mode == FQLPOP_ENS_PER_MODEL), "choice is for FQLPOP_ENS_MIXED only");
     ARGCHK(!(out_traj_obs && mode == FQLPOP_ENS_PER_MODEL), "record is for FQLPOP_ENS_MIXED only");
-    if (h->ens_n == 0) throw FqErr{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
-    const int K = h->ens_n;
+    if (h->ens.n == 0) throw Err{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
+    const int K = h->ens.n;
     const size_t n_choice = (size_t)max_steps * n_envs;
     if (choice)
         for (size_t i = 0; i < n_choice; ++i)
@@ -3255,32 +3126,32 @@ void ens_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint
     const size_t rows = (size_t)nz * (mode == FQLPOP_ENS_PER_MODEL ? K : 1) * n_envs;
     const size_t n_noise = (size_t)nz * max_steps * n_envs * A;
     const size_t n_traj = (size_t)nz * max_steps * n_envs;
-    float *d_obs = nullptr, *d_noise = nullptr, *d_out = nullptr, *d_oobs = nullptr, *d_tobs = nullptr,
-          *d_tact = nullptr, *d_tunc = nullptr;
-    int *d_choice = nullptr, *d_tmodel = nullptr;
-    HIPCHK(hipMalloc(&d_obs, sizeof(float) * n_envs * D));
-    HIPCHK(hipMalloc(&d_out, sizeof(float) * rows * 2));
+    using Scratch = DevBuf<float>;  // per call; null where an optional input / output is absent
+    Scratch d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact, d_tunc;
+    DevBuf<int> d_choice, d_tmodel;
+    d_obs = Scratch((size_t)n_envs * D, "rollout start observations");
+    d_out = Scratch(rows * 2, "rollout outputs");
     HIPCHK(hipMemcpy(d_obs, init_obs, sizeof(float) * n_envs * D, hipMemcpyHostToDevice));
     if (noise) {
-        HIPCHK(hipMalloc(&d_noise, sizeof(float) * n_noise));
+        d_noise = Scratch(n_noise, "rollout noise");
         HIPCHK(hipMemcpy(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice));
     }
     if (choice) {
-        HIPCHK(hipMalloc(&d_choice, sizeof(int) * n_choice));
+        d_choice = DevBuf<int>(n_choice, "rollout model choice");
         HIPCHK(hipMemcpy(d_choice, choice, sizeof(int) * n_choice, hipMemcpyHostToDevice));
     }
-    if (out_obs) HIPCHK(hipMalloc(&d_oobs, sizeof(float) * rows * D));
+    if (out_obs) d_oobs = Scratch(rows * D, "rollout final observations");
     if (out_traj_obs) {  // zeroed: the kernel writes the steps an env ran only
-        HIPCHK(hipMalloc(&d_tobs, sizeof(float) * n_traj * D));
-        HIPCHK(hipMalloc(&d_tact, sizeof(float) * n_traj * A));
+        d_tobs = Scratch(n_traj * D, "rollout observation trace");
+        d_tact = Scratch(n_traj * A, "rollout action trace");
         HIPCHK(hipMemsetAsync(d_tobs, 0, sizeof(float) * n_traj * D, h->sM));
         HIPCHK(hipMemsetAsync(d_tact, 0, sizeof(float) * n_traj * A, h->sM));
         if (out_traj_model) {
-            HIPCHK(hipMalloc(&d_tmodel, sizeof(int) * n_traj));
+            d_tmodel = DevBuf<int>(n_traj, "rollout model trace");
             HIPCHK(hipMemsetAsync(d_tmodel, 0, sizeof(int) * n_traj, h->sM));
         }
         if (out_traj_unc) {
-            HIPCHK(hipMalloc(&d_tunc, sizeof(float) * n_traj));
+            d_tunc = Scratch(n_traj, "rollout disagreement trace");
             HIPCHK(hipMemsetAsync(d_tunc, 0, sizeof(float) * n_traj, h->sM));
         }
     }
@@ -3303,10 +3174,6 @@ void ens_run(fqlpop_t* h, const float* init_obs, int n_envs, int max_steps, uint
         if (out_traj_model) HIPCHK(hipMemcpy(out_traj_model, d_tmodel, sizeof(int) * n_traj, hipMemcpyDeviceToHost));
         if (out_traj_unc) HIPCHK(hipMemcpy(out_traj_unc, d_tunc, sizeof(float) * n_traj, hipMemcpyDeviceToHost));
     }
-    for (float* p : {d_obs, d_noise, d_out, d_oobs, d_tobs, d_tact, d_tunc})
-        if (p) (void)hipFree(p);
-    for (int* p : {d_choice, d_tmodel})
-        if (p) (void)hipFree(p);
 }
 }  // namespace
 
@@ -3332,7 +3199,7 @@ int fqlpop_rollout_ensemble_record(fqlpop_t* h, const float* init_obs, int n_env
 int fqlpop_rollout_ensemble_time(fqlpop_t* h, double* kernel_us) {
     return guard([&] {
         ARGCHK(h && kernel_us, "null argument");
-        if (h->ens_kernel_us < 0) throw FqErr{FQLPOP_E_STATE, "no fqlpop_rollout_ensemble call yet"};
+        if (h->ens_kernel_us < 0) throw Err{FQLPOP_E_STATE, "no fqlpop_rollout_ensemble call yet"};
         *kernel_us = h->ens_kernel_us;
     });
 }

@@ -1,15 +1,20 @@
-"""The env-model trainer handles on the GPU (csrc/hostmem.h's owners behind fqlpop_emtrain_*
-and fqlpop_initobs_*).  Lifecycle: create -> set_dataset -> one step -> read -> close, three
-times over in one process, for an ensemble trainer with K = 2 (with a frozen termination
-predictor) and for the initial-observation VAE (whose sample staging also grows once); the
-third round's outputs equal the first's.  Replacement: a handle whose dataset (and frozen
-predictor) A was in use and then replaced by B, with refused setter calls in between, trains
-bit for bit like a fresh handle that only ever saw B.
+"""The handles of the C ABI on the GPU, all of them on csrc/hostmem.h's owners: the env-model
+trainer handles (fqlpop_emtrain_*, fqlpop_initobs_*) and the population handle (fqlpop_*, whose
+setters replace the structs of csrc/popmem.h).
 
-The population handle is not on the owners and has no test here.
+Lifecycle: create -> set up -> use -> read -> close, three times over in one process; the third
+round's outputs equal the first's.  For an ensemble trainer with K = 2 (with a frozen
+termination predictor), for the initial-observation VAE (whose sample staging also grows once)
+and for the population at the set-up of tests/test_gpu_synth.py with a dataset, an env model,
+a K = 2 ensemble and rings: one collect from start rows, two train steps, one recorded
+rollout; with and without the step's graph.
+
+Replacement: a handle whose dataset and model A were in use and then replaced by B, with
+refused setter calls in between, goes on bit for bit like a handle that only ever saw B.  A
+refused fqlpop_set_env_model leaves the model that is set intact: the same rollout as before.
 
 No test here makes a device allocation fail: the failure paths run on the host, over a
-counting heap (tests/test_hostmem_cpu.py)."""
+counting heap (tests/test_hostmem_cpu.py, tests/test_popmem_cpu.py)."""
 import ctypes
 
 import numpy as np
@@ -18,6 +23,9 @@ import pytest
 import envmodel as em
 from envmodel import initial_observation as io
 from envmodel.trainer import EnvModelTrainerConfig, StatePredictorEnsembleTrainer
+import test_gpu_synth as SY
+from _helpers import synthetic_rows
+from test_gpu_ensemble import SPEC as POP_SPEC, _env_model, _set_ensemble, _set_single
 
 pytestmark = pytest.mark.gpu
 D, A = 5, 2
@@ -138,3 +146,120 @@ def test_initobs_replacement_is_complete_and_refusals_change_nothing():
     got = state(tr)
     tr.close()
     _assert_same(got, want)
+
+
+# ------------------------------------------------------------------ the population handle
+def _pop_models(seeds):
+    return [_env_model(POP_SPEC, tp_bias=-12.0, tp_scale=1.0, seed=s) for s in seeds]
+
+
+def _pop_outputs(pop):
+    """One recorded rollout from ROWS1, then every member's state, train info and ring."""
+    out = list(pop.rollout(SY._data()["observations"][SY.ROWS1], SY.T, seed=SY.SEED1, record=True, return_obs=True))
+    for m in range(pop.n):
+        out += SY._state(pop, m) + [SY._info_row(pop, m)]
+        ring, info = pop.synth_read(m), pop.synth_info(m)
+        out += [np.array([info[k] for k in sorted(info)])] + [ring[k] for k in sorted(ring)]
+    return out
+
+
+def _population_round(use_graph):
+    pop = SY._pop(2, use_graph=use_graph)  # create, set_dataset, set_env_model
+    _set_ensemble(pop, _pop_models((11, 12)))
+    pop.synth_create(1000)
+    pop.collect(SY.E, SY.T, SY.SEED1, start_rows=SY.ROWS1)
+    pop.step(2)
+    out = _pop_outputs(pop)
+    pop.close()
+    return out
+
+
+@pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])
+def test_population_lifecycle_three_times(use_graph):
+    rounds = [_population_round(use_graph) for _ in range(3)]
+    _assert_same(rounds[2], rounds[0])
+    assert all(np.isfinite(a).all() for a in rounds[0])
+    assert rounds[0][1].min() >= 1 and np.abs(rounds[0][2]).max() > 0  # the rollout ran: lengths, final observations
+    per_member = (len(rounds[0]) - 5) // 2  # (after the rollout's five: params, m, v, count, info, ring info, ring)
+    for m in range(2):
+        state = rounds[0][5 + m * per_member:]
+        assert np.abs(state[1]).max() > 0 and np.abs(state[2]).max() > 0  # Adam m, v: the steps ran
+        assert state[3] == 2                                             # the step count
+        assert state[5].min() > 0 and len(state[6]) > 0                  # the collect filled the ring
+
+
+def _pop_refused(pop, rc, text):
+    assert rc == -1 and text.encode() in pop.lib.fqlpop_last_error(), (rc, pop.lib.fqlpop_last_error())
+
+
+def _rollout_a(pop):
+    return pop.rollout(SY._data()["observations"][SY.ROWS1], SY.T, seed=SY.SEED1, record=True, return_obs=True)
+
+
+def _refused_set_env_model(pop):
+    """fqlpop_set_env_model with one state-predictor parameter too few (another model's values)."""
+    from fqlpop._lib import fptr
+    sp, tp = _pop_models((13,))[0]
+    sp, tp = em.flatten_state_predictor(POP_SPEC, sp), em.flatten_termination_predictor(POP_SPEC, tp)
+    rc = pop.lib.fqlpop_set_env_model(pop._h, ctypes.byref(pop._em_cfg), fptr(sp), sp.size - 1, fptr(tp), tp.size)
+    _pop_refused(pop, rc, "parameter count mismatch")
+
+
+def test_population_refused_set_env_model_keeps_the_model():
+    pop = SY._pop(2)
+    pop.step(1)
+    before = _rollout_a(pop)
+    _refused_set_env_model(pop)
+    after = _rollout_a(pop)
+    pop.close()
+    _assert_same(after, before)
+    assert before[1].min() >= 1 and np.abs(before[2]).max() > 0 and np.abs(before[3]).max() > 0  # the rollout ran
+
+
+def test_population_replacement_is_complete_and_refusals_change_nothing():
+    from fqlpop._lib import STATE_ADAM_M, STATE_ADAM_V, STATE_PARAMS, fptr
+    data_b, model_b, ens_b = synthetic_rows(1501, SY.D, SY.A, 6), _pop_models((12,))[0], _pop_models((13, 12))
+    obs0 = data_b["observations"][:SY.E]
+
+    def use_b(pop):
+        outs = list(pop.rollout(obs0, SY.T, seed=3, record=True, return_obs=True))
+        outs += list(pop.rollout_ensemble(obs0, SY.T, seed=4, mode="mixed", return_obs=True))
+        pop.step(2)
+        for m in range(2):
+            outs += SY._state(pop, m) + [SY._info_row(pop, m)]
+        return outs
+
+    pop = SY._pop(2)  # dataset A, model A
+    _set_ensemble(pop, _pop_models((11, 12)))
+    pop.step(1)
+    _rollout_a(pop)
+    pop.rollout_ensemble(obs0, SY.T, seed=4, mode="mixed")  # A's model and ensemble are in use
+    first = [SY._state(pop, m) for m in range(2)]
+
+    a = SY._data()
+    keys = ("observations", "actions", "rewards", "masks", "next_observations")
+    rc = pop.lib.fqlpop_set_dataset(pop._h, 0, *[a[k].ctypes.data_as(ctypes.c_void_p) for k in keys], 0, 0)
+    _pop_refused(pop, rc, "n_rows out of range")
+    _refused_set_env_model(pop)
+    sp = np.stack([em.flatten_state_predictor(POP_SPEC, m[0]) for m in ens_b])
+    tp = np.stack([em.flatten_termination_predictor(POP_SPEC, m[1]) for m in ens_b])
+    rc = pop.lib.fqlpop_set_env_model_ensemble(pop._h, ctypes.byref(pop._em_cfg), 0, fptr(sp), sp.shape[1], fptr(tp),
+                                               tp.shape[1])
+    _pop_refused(pop, rc, "n_models must be in 1..16")
+    pop.set_dataset(data_b)
+    _set_single(pop, model_b)
+    _set_ensemble(pop, ens_b)
+    got = use_b(pop)
+    pop.close()
+
+    twin = SY._pop(2, env_model=False, data=data_b)  # only ever B, at the state after the same first step
+    _set_single(twin, model_b)
+    _set_ensemble(twin, ens_b)
+    for m in range(2):
+        for which, flat in zip((STATE_PARAMS, STATE_ADAM_M, STATE_ADAM_V), first[m]):
+            twin.set_flat(m, flat, which)
+        twin.set_count(m, int(first[m][3]))
+    want = use_b(twin)
+    twin.close()
+    _assert_same(got, want)
+    assert np.abs(first[0][1]).max() > 0 and np.abs(got[-4]).max() > 0  # Adam's first moment: the steps ran
