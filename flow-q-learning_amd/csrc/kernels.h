@@ -51,6 +51,15 @@ void launch_gemm_variant(int layout, int epi, int tile, int variant, const GemmA
 // Up to GEMM_GROUP_MAX independent dW-layout problems (A and B both
 // r-contiguous, EPI_STORE) in one launch; N % BN == 0 for every problem.
 constexpr int GEMM_GROUP_MAX = 8;
+// Per-member hyper-parameters of the update: hparams[slot][HP_COUNT] in device memory
+// (fqlpop_set_member_hparams; the indices are FQLPOP_HP_* of the C ABI).  The kernels
+// that use them read their member's row by SLOT with a scalar load (s_load_dword; in the
+// fused dW epilogue through the constant address space, uni_load in kernels.hip): the loss
+// (discount), adam_chunk and the fused dW epilogue (lr, tau).
+// They are the only copy the step reads: a captured graph sees a change without
+// recapture.
+constexpr int HP_COUNT = 3;
+enum { HP_LR = 0, HP_DISCOUNT = 1, HP_TAU = 2 };
 struct Chunk { long long off; int len; int leaf; };  // element offset into a net's param block
 struct AdamArgs {
     const float* p_in;            // parameters read (current buffer, slot stride P)
@@ -65,7 +74,7 @@ struct AdamArgs {
     float* stats;                 // [slots][n_total_chunks][3] (max, min, sumsq)
     int n_total_chunks;
     const int* count;
-    float lr, tau;
+    const float* hparams;         // [slots][HP_COUNT]: lr and tau of the block's member
     int nz;
     const int* slots;
 };
@@ -86,7 +95,7 @@ struct AdamEpi {
     float* stats;                     // [slots][n_total_chunks][3]
     int n_total_chunks;
     const int* count;
-    float lr, tau;
+    const float* hparams;             // [slots][HP_COUNT]: lr and tau of the tile's member
     int mode;                         // 0; timing probes (FQLPOP_DW_MODE): 1 = no optimiser pass, 2 = one k-slice,
                                       // 3 = no W^T pass
     int nt;                           // non-temporal optimiser streams: 1 m/v, 2 target, 4 p_in, 8 p_out/W^T
@@ -415,7 +424,7 @@ struct LossArgs {
     const float* alpha;           // per slot
     int B, A, E, da_n;
     int q_min, normq;
-    float discount;
+    const float* hparams;         // [slots][HP_COUNT]: the critic loss reads its member's discount
     int nz;
     const int* slots;
 };
@@ -454,7 +463,7 @@ void launch_init(const InitArgs& a, hipStream_t s);
 // dst[p] for every pair of the call in ONE launch, grid (chunk, pair), 16 bytes per lane
 // and access.  Every arena's slot stride is a multiple of 64 floats (align_up), so a slot's
 // block is float4-aligned.  The block with chunk 0 of a pair also writes dst's update count,
-// alpha, seed and sampling key.
+// alpha, seed and sampling key, and copies src's hparams row to dst.
 constexpr int CLONE_MAX_ARENAS = 8;
 constexpr int CLONE_MAX_PAIRS = 16;   // per launch; the host loops for more
 struct CloneArena {
@@ -474,6 +483,7 @@ struct CloneArgs {
     uint64_t seeds[CLONE_MAX_PAIRS], skeys[CLONE_MAX_PAIRS];
     int* count;
     float* alpha;
+    float* hparams;               // [slots][HP_COUNT]
     uint64_t* seed;
     uint64_t* skey;
 };

@@ -138,6 +138,14 @@ template <class T>
 DEV T* uniptr(T* p) {
     return reinterpret_cast<T*>(uni64(reinterpret_cast<long long>(p)));
 }
+// A block-uniform float that no kernel of the launch writes (a member's hparams row), read
+// through the constant address space: an s_load_dword into an SGPR wherever it stands.  A
+// plain load that follows stores of the same kernel (the fused dW epilogue's) is not
+// scalarised by the compiler and would take a VGPR per value.
+DEV float uni_load(const float* p) {
+    typedef const __attribute__((address_space(4))) float cfloat_t;
+    return *(cfloat_t*)reinterpret_cast<unsigned long long>(uniptr(p));
+}
 
 // Bijective XCD-aware remap: blocks b and b+8 share an XCD under round-robin
 // dispatch, so give each XCD a contiguous range of logical work ids (members'
@@ -188,7 +196,8 @@ DEV void adam_chunk_t(const AdamArgs& a, int bx, int z) {
     const float t = (float)(a.count[slot] + 1);
     const float bc1 = 1.0f - powf(0.9f, t), bc2 = 1.0f - powf(0.999f, t);
     float mx = -INFINITY, mn = INFINITY, ss = 0.f;
-    const float lr = a.lr, tau = a.tau;
+    const float* hp = a.hparams + (long long)slot * HP_COUNT;
+    const float lr = hp[HP_LR], tau = hp[HP_TAU];
     const bool hasT = a.target != nullptr;
     if (NT == 256 || threadIdx.x < 256) {
         const float* __restrict__ Pin = a.p_in + base;
@@ -438,7 +447,8 @@ DEV void adam_epilogue(const AdamEpi& e, int gi, const GemmArgs& g, f32x16 (&acc
     const float t = (float)(e.count[slot] + 1);
     const float bc1 = 1.0f - powf(0.9f, t), bc2 = 1.0f - powf(0.999f, t);
     const float rbc1 = 1.0f / bc1, rbc2 = 1.0f / bc2;
-    const float lr = e.lr, tau = e.tau;
+    const float* hp = e.hparams + (long long)slot * HP_COUNT;
+    const float lr = uni_load(hp + HP_LR), tau = uni_load(hp + HP_TAU);
     float mx = -INFINITY, mn = INFINITY, ss = 0.f;
     const int rows = min(BM, gM - i0);
     const bool run = e.mode != 1;  // mode 1: timing probe only (no optimiser traffic)
@@ -3581,6 +3591,7 @@ __global__ __launch_bounds__(256) void loss_critic_kernel(const LossArgs a) {
     const float* mk = at(a.mask, slot);
     float* dq = at(a.dq, slot);
     const float invEB = 1.0f / (float)(E * B);
+    const float discount = a.hparams[(long long)slot * HP_COUNT + HP_DISCOUNT];
     float sq = 0.f, qs = 0.f, qmx = -INFINITY, qmn = INFINITY, qpi_s = 0.f, qpi_abs = 0.f;
     float sdq[4] = {0.f, 0.f, 0.f, 0.f};
     for (int b = threadIdx.x; b < B; b += 256) {
@@ -3590,7 +3601,7 @@ __global__ __launch_bounds__(256) void loss_critic_kernel(const LossArgs a) {
             agg = a.q_min ? fminf(agg, v) : agg + v;
         }
         if (!a.q_min) agg /= (float)E;
-        const float y = rw[b] + a.discount * mk[b] * agg;
+        const float y = rw[b] + discount * mk[b] * agg;
         float qp = 0.f;
         for (int e = 0; e < E; ++e) {
             const float qv = q[e * a.q.sy + b];
@@ -3835,6 +3846,7 @@ __global__ __launch_bounds__(256) void clone_members_kernel(const CloneArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.count[dn] = a.count[so];
         a.alpha[dn] = a.alphas[p];
+        for (int k = 0; k < HP_COUNT; ++k) a.hparams[dn * HP_COUNT + k] = a.hparams[so * HP_COUNT + k];
         a.seed[dn] = a.seeds[p];
         a.skey[dn] = a.skeys[p];
     }

@@ -130,7 +130,11 @@ void philox_host(uint32_t c[4], uint32_t k0, uint32_t k1) {
 // that share a seed but not an alpha see different batches there; keying the device
 // sampler by the seed alone would give them identical minibatches, flow times and
 // noises.  Independent of the slot, so a resumed or re-slotted member draws the same
-// stream.
+// stream.  The member's lr, discount and tau (fqlpop_set_member_hparams) are NOT part of the
+// key: members that share (seed, alpha) and differ only in those draw the same minibatches
+// and noises, a controlled comparison of the three values.
+static_assert(HP_COUNT == FQLPOP_HP_COUNT && HP_LR == FQLPOP_HP_LR && HP_DISCOUNT == FQLPOP_HP_DISCOUNT &&
+                  HP_TAU == FQLPOP_HP_TAU, "kernels.h and fqlpop.h disagree on the hparams row");
 uint64_t sample_key(uint64_t seed, float alpha) {
     uint32_t ab;
     std::memcpy(&ab, &alpha, sizeof(ab));
@@ -257,6 +261,9 @@ struct fqlpop : StepStreams<> {
     DevBuf<uint64_t> seeds;
     DevBuf<uint64_t> skeys;  // per-member sampler key: sample_key(seed, alpha)
     DevBuf<float> alpha;
+    // per-member lr, discount, tau [n][FQLPOP_HP_COUNT]: the only copy the step's kernels read
+    // (by slot), so a captured graph sees fqlpop_set_member_hparams without recapture
+    DevBuf<float> hparams;
     DevBuf<int> slots;
     DevBuf<float> stats;
     DevBuf<Chunk> chunks;
@@ -273,6 +280,7 @@ struct fqlpop : StepStreams<> {
 
     // host mirror
     std::vector<float> h_alpha;
+    std::vector<float> h_hparams;  // [n][FQLPOP_HP_COUNT]
     std::vector<uint64_t> h_seeds;
     std::vector<uint8_t> active;
     std::vector<int> h_slots;
@@ -960,7 +968,7 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const Net& n, const BwdCols& k,
         }
         ae.stats = h->stats; ae.n_total_chunks = h->n_chunks_total;
         ae.count = h->count;
-        ae.lr = h->cfg.lr; ae.tau = h->cfg.tau;
+        ae.hparams = h->hparams;
         {
             // FQLPOP_DW_MODE (diagnostic builds only, timing probes with wrong results):
             // 1 / 2 one phase of the launch, 3 no W^T pass, 4 no W^T pass for the actor nets
@@ -1033,7 +1041,7 @@ AdamArgs adam_args(const Ctx& c, int ni) {
     }
     a.stats = h->stats; a.n_total_chunks = h->n_chunks_total;
     a.count = h->count;
-    a.lr = h->cfg.lr; a.tau = h->cfg.tau;
+    a.hparams = h->hparams;
     a.nz = c.nz; a.slots = h->slots;
     return a;
 }
@@ -1393,7 +1401,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     la.alpha = h->alpha;
     la.B = B; la.A = A; la.E = h->E;
     la.q_min = h->cfg.q_agg_min; la.normq = h->cfg.normalize_q_loss;
-    la.discount = h->cfg.discount;
+    la.hparams = h->hparams;
     la.nz = c.nz; la.slots = h->slots;
 
     // ---- sF: BC-flow forward (train rows) fused with Euler step 0 --------
@@ -1933,6 +1941,7 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         h->seeds = DevBuf<uint64_t>(n, "member seeds");
         h->skeys = DevBuf<uint64_t>(n, "sampler keys");
         h->alpha = DevBuf<float>(n, "member alphas");
+        h->hparams = DevBuf<float>((size_t)n * FQLPOP_HP_COUNT, "member hparams");
         h->slots = DevBuf<int>(n, "active slots");
         build_chunks(h.get());
 
@@ -2051,6 +2060,12 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         h->h_seeds.assign(seeds_in, seeds_in + n);
         HIPCHK(hipMemcpy(h->alpha, alphas, sizeof(float) * n, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->seeds, seeds_in, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+        h->h_hparams.resize((size_t)n * FQLPOP_HP_COUNT);
+        for (int i = 0; i < n; ++i) {
+            float* hp = &h->h_hparams[(size_t)i * FQLPOP_HP_COUNT];
+            hp[FQLPOP_HP_LR] = cfg->lr; hp[FQLPOP_HP_DISCOUNT] = cfg->discount; hp[FQLPOP_HP_TAU] = cfg->tau;
+        }
+        HIPCHK(hipMemcpy(h->hparams, h->h_hparams.data(), sizeof(float) * h->h_hparams.size(), hipMemcpyHostToDevice));
         for (int i = 0; i < n; ++i) upload_skey(h.get(), i);
         for (int i = 0; i < n; ++i) init_member(h.get(), i, seeds_in[i]);
         h->active.assign(n, 1);
@@ -2375,8 +2390,37 @@ int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int r
     });
 }
 
+// The member's lr, discount and tau.  The arguments are checked before any GPU call; the
+// device row is written after a synchronise (as fqlpop_set_member), so the steps enqueued
+// before the call ran with the old values and every later one, a captured graph's replay
+// included, reads the new ones.
+int fqlpop_set_member_hparams(fqlpop_t* h, int member, const float* hp) {
+    return guard([&] {
+        check_member(h, member);
+        ARGCHK(hp, "null argument");
+        const float lr = hp[FQLPOP_HP_LR], discount = hp[FQLPOP_HP_DISCOUNT], tau = hp[FQLPOP_HP_TAU];
+        ARGCHK(std::isfinite(lr) && lr >= 0.0f, "lr must be finite and >= 0");
+        ARGCHK(discount >= 0.0f && discount <= 1.0f, "discount must be in [0, 1]");  // false for NaN
+        ARGCHK(tau >= 0.0f && tau <= 1.0f, "tau must be in [0, 1]");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(h->hparams + (long long)member * FQLPOP_HP_COUNT, hp, sizeof(float) * FQLPOP_HP_COUNT,
+                         hipMemcpyHostToDevice));
+        std::copy(hp, hp + FQLPOP_HP_COUNT, h->h_hparams.begin() + (size_t)member * FQLPOP_HP_COUNT);
+    });
+}
+
+int fqlpop_get_member_hparams(fqlpop_t* h, int member, float* hp) {
+    return guard([&] {
+        check_member(h, member);
+        ARGCHK(hp, "null argument");
+        std::copy_n(h->h_hparams.begin() + (size_t)member * FQLPOP_HP_COUNT, FQLPOP_HP_COUNT, hp);
+    });
+}
+
 // Per-slot buffers of struct fqlpop and what the clone does with them:
-//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count; the member's
+//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count, hparams (and
+//            its mirror h_hparams); the member's
 //            synthetic-transition ring and its counters (synth, when created: its own launch);
 //   written  alpha, seeds, skeys (the values given for dst), h_alpha / h_seeds;
 //   scratch  grads, stats, the network inputs (os_in .. tg_in, cr_in_buf), every Net's U / G /
@@ -2425,7 +2469,7 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
         arena(h->target, h->target, h->target, h->PT);
         arena(h->adam_m, h->adam_m, h->adam_m, h->P);
         arena(h->adam_v, h->adam_v, h->adam_v, h->P);
-        base.count = h->count; base.alpha = h->alpha; base.seed = h->seeds; base.skey = h->skeys;
+        base.count = h->count; base.alpha = h->alpha; base.hparams = h->hparams; base.seed = h->seeds; base.skey = h->skeys;
         // on sM, the stream the step graphs are launched on: after the steps enqueued so far,
         // before the later ones; every side stream of a step forks from and joins into sM
         for (int p0 = 0; p0 < n_pairs; p0 += CLONE_MAX_PAIRS) {
@@ -2449,6 +2493,8 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
         for (int i = 0; i < n_pairs; ++i) {
             h->h_alpha[dst[i]] = alphas[i];
             h->h_seeds[dst[i]] = seeds[i];
+            std::copy_n(h->h_hparams.begin() + (size_t)src[i] * FQLPOP_HP_COUNT, FQLPOP_HP_COUNT,
+                        h->h_hparams.begin() + (size_t)dst[i] * FQLPOP_HP_COUNT);
             h->poisoned[dst[i]] = 0;  // every arena a failed launch may have written is overwritten
             h->restored[dst[i]] = 0;
         }

@@ -28,6 +28,7 @@ TRAIN_INFO_KEYS = (
 )
 VAL_INFO_KEYS = TRAIN_INFO_KEYS[:10]
 STATE_PARAMS, STATE_ADAM_M, STATE_ADAM_V = 0, 1, 2
+HP_KEYS = ("lr", "discount", "tau")  # FQLPOP_HP_LR, _DISCOUNT, _TAU: the per-member hparams row
 
 
 class FqlpopError(RuntimeError):
@@ -123,6 +124,8 @@ _SIGS = {
     "fqlpop_set_count": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int32]),
     "fqlpop_set_member": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_float, ctypes.c_uint64,
                                          ctypes.c_int]),
+    "fqlpop_set_member_hparams": (ctypes.c_int, [_P, ctypes.c_int, _F]),
+    "fqlpop_get_member_hparams": (ctypes.c_int, [_P, ctypes.c_int, _F]),
     "fqlpop_clone_members": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_int), _F,
                                             ctypes.POINTER(ctypes.c_uint64)]),
@@ -227,14 +230,19 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     global _lib
     if _lib is not None and path is None:
         return _lib
-    p = path or os.environ.get("FQLPOP_LIB") or LIB_PATH  # FQLPOP_LIB: A/B builds (developer)
+    override = None if path else os.environ.get("FQLPOP_LIB")
+    p = path or override or LIB_PATH  # FQLPOP_LIB: A/B builds (developer)
     if not os.path.exists(p):
         raise FqlpopError(
             f"{p} not found: build the HIP extension first "
             "(python -c 'import __graft_entry__ as g; g.build()')")
     lib = ctypes.CDLL(p)
     for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            if override:  # an A/B build of an older commit: the entry point raises when it is used
+                continue
+            raise FqlpopError(f"{p} misses {name}: rebuild the HIP extension")
         fn.restype = res
         fn.argtypes = args
     if path is None:

@@ -77,12 +77,17 @@ def max_over_ranks(value: float, device: torch.device | None = None) -> float:
 # (identical) strategy state, so all ranks compute the same owners and moves
 # without exchanging them.
 
+EXTRA_FIELDS = ("lr", "discount", "tau")  # ExperimentConfig's fields after the reference's two
+
+
 def config_key(cfg):
-    """Total order on ExperimentConfig-like records (alpha, then seed; None first),
-    the order every rank iterates candidates in."""
+    """Total order on ExperimentConfig-like records (alpha, then seed, then lr, discount,
+    tau; None first), the order every rank iterates candidates in.  Configs without the
+    last three keep their relative order of before those fields existed."""
     def k(v):
         return (0, 0.0) if v is None else (1, float(v))
-    return (k(getattr(cfg, "alpha", None)), k(getattr(cfg, "seed", None)))
+    return (k(getattr(cfg, "alpha", None)), k(getattr(cfg, "seed", None))) + tuple(
+        k(getattr(cfg, f, None)) for f in EXTRA_FIELDS)
 
 
 def ordered(configs):
@@ -176,9 +181,17 @@ def collect_seed(base_seed: int, collect_index: int) -> int:
 def member_eval_seed(base_seed: int, round_index: int, cfg) -> int:
     """Seed of one candidate's own evaluation in round ``round_index`` (tasks without
     a batched world-model evaluation): a function of the run seed, the round and the
-    candidate's (alpha, seed), so it does not depend on which rank owns the member."""
-    (fa, a), (fs, s) = config_key(cfg)
-    a_bits = int(np.array([a], dtype=np.float64).view(np.uint64)[0])
+    candidate's (alpha, seed), so it does not depend on which rank owns the member.  Each
+    of lr, discount and tau that the candidate sets appends three words (its index, its
+    float64 bits); a candidate that sets none has the words of before those fields existed."""
+    def bits(v):
+        return int(np.array([v], dtype=np.float64).view(np.uint64)[0])
+    (fa, a), (fs, s) = config_key(cfg)[:2]
+    a_bits = bits(a)
     words = [int(base_seed) & 0xFFFFFFFF, int(round_index), fa, a_bits & 0xFFFFFFFF, a_bits >> 32, fs,
              int(s) & 0xFFFFFFFF]
+    for i, f in enumerate(EXTRA_FIELDS):
+        v = getattr(cfg, f, None)
+        if v is not None:
+            words += [2 + i, bits(float(v)) & 0xFFFFFFFF, bits(float(v)) >> 32]
     return int(np.random.default_rng(words).integers(0, 2**31 - 1))

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from fqlpop import _lib
-from fqlpop._lib import (INFO_STRIDE, STATE_ADAM_M, STATE_ADAM_V, STATE_PARAMS,
+from fqlpop._lib import (HP_KEYS, INFO_STRIDE, STATE_ADAM_M, STATE_ADAM_V, STATE_PARAMS,
                          TRAIN_INFO_KEYS, VAL_INFO_KEYS, check, fptr)
 
 
@@ -98,9 +98,13 @@ def split_plan(cfg: "PopulationConfig", n_members: int) -> dict:
 
 
 class Population:
-    """A population of FQL agents (one alpha and seed per member) on one GPU."""
+    """A population of FQL agents (one alpha and seed per member, and optionally its own
+    lr, discount and tau) on one GPU.
 
-    def __init__(self, cfg: PopulationConfig, alphas, seeds, device: int = 0):
+    ``hparams``: None, or per member None or a dict with any of "lr", "discount", "tau";
+    a missing key means the ``cfg`` value (``set_member_hparams``)."""
+
+    def __init__(self, cfg: PopulationConfig, alphas, seeds, device: int = 0, hparams=None):
         self.lib = _lib.load_library()
         self.cfg = cfg
         alphas = _f32(alphas).reshape(-1)
@@ -131,6 +135,18 @@ class Population:
         check(self.lib.fqlpop_state_size(self._h, ctypes.byref(n)))
         self.state_size = int(n.value)
         self.leaves = self._leaf_table()
+        if hparams is not None:
+            hparams = list(hparams)
+            if len(hparams) != self.n:
+                self.close()
+                raise ValueError(f"hparams needs one entry per member ({self.n}), got {len(hparams)}")
+            try:
+                for i, hp in enumerate(hparams):
+                    if hp:
+                        self.set_member_hparams(i, **hp)
+            except Exception:
+                self.close()
+                raise
 
     # ------------------------------------------------------------------ misc
     def close(self):
@@ -591,12 +607,32 @@ class Population:
         self.alphas[member] = alpha
         self.seeds[member] = seed
 
-    def clone_members(self, src, dst, alphas=None, seeds=None):
+    def set_member_hparams(self, member: int, lr=None, discount=None, tau=None):
+        """The member's learning rate, discount and target-EMA tau (fqlpop_set_member_hparams);
+        None keeps the current value.  Synchronises; holds from the next enqueued step on,
+        without recapturing the step graph.  Members that share (seed, alpha) and differ only
+        here draw the same minibatches and noises."""
+        cur = self.member_hparams(member)
+        new = {"lr": lr, "discount": discount, "tau": tau}
+        hp = np.array([cur[k] if new[k] is None else new[k] for k in HP_KEYS], dtype=np.float32)
+        check(self.lib.fqlpop_set_member_hparams(self._h, int(member), fptr(hp)))
+
+    def member_hparams(self, member: int) -> dict:
+        """{"lr", "discount", "tau"} of one member (the float32 values the kernels read), from
+        the engine's host mirror: no synchronisation."""
+        hp = np.zeros(len(HP_KEYS), dtype=np.float32)
+        check(self.lib.fqlpop_get_member_hparams(self._h, int(member), fptr(hp)))
+        return {k: float(hp[j]) for j, k in enumerate(HP_KEYS)}
+
+    def clone_members(self, src, dst, alphas=None, seeds=None, hparams=None):
         """Copy the complete training state of member ``src[i]`` into member ``dst[i]`` on
         the device (fqlpop_clone_members: one launch, stream-ordered between the steps, no
         host staging; it may return before the copy has run).  ``alphas`` / ``seeds`` None:
         every dst keeps its OWN current value -- not the source's, which would make the two
-        members draw identical batches forever."""
+        members draw identical batches forever.  The dst takes the SOURCE's lr, discount and
+        tau; ``hparams`` (None, one dict for every pair, or per pair None or a dict as
+        ``set_member_hparams`` takes) is applied to the dst after the clone, which then
+        synchronises."""
         src = np.ascontiguousarray(np.asarray(src, dtype=np.int32).reshape(-1))
         dst = np.ascontiguousarray(np.asarray(dst, dtype=np.int32).reshape(-1))
         if src.shape != dst.shape:
@@ -615,10 +651,18 @@ class Population:
                                             fptr(al), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         self.alphas[dst] = al
         self.seeds[dst] = sd
+        if hparams is not None:
+            per = [hparams] * len(dst) if isinstance(hparams, dict) else list(hparams)
+            if len(per) != len(dst):
+                raise ValueError("hparams needs one entry per pair")
+            for d, hp in zip(dst, per):
+                if hp:
+                    self.set_member_hparams(int(d), **hp)
 
-    def clone_member(self, src: int, dst: int, alpha=None, seed=None):
+    def clone_member(self, src: int, dst: int, alpha=None, seed=None, hparams=None):
         """``clone_members`` for one pair."""
-        self.clone_members([src], [dst], None if alpha is None else [alpha], None if seed is None else [seed])
+        self.clone_members([src], [dst], None if alpha is None else [alpha], None if seed is None else [seed],
+                           None if hparams is None else [hparams])
 
     def state_dict(self, member: int) -> dict:
         """Member state in flax ``to_state_dict`` shape: params (incl. target

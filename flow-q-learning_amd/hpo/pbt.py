@@ -1,4 +1,4 @@
-"""Population-based training of alpha: truncation exploit + perturb explore.
+"""Population-based training of alpha (and lr, discount, tau): truncation exploit + perturb explore.
 
 [no reference counterpart: the reference ships Identity and SuccessiveHalving only]
 
@@ -9,6 +9,18 @@ from ``perturb_factors`` (clipped to ``alpha_bounds``), a fresh seed and a copy 
 parent's score history.  The population keeps its size for the whole run, so the
 member-batched engine stays at the member count it is fastest at (successive halving
 empties it), and the run yields an alpha schedule (``lineage``), not just one alpha.
+
+``explore`` (default ``("alpha",)``: exactly the above) names the fields a child perturbs, a
+subset of alpha, lr, discount, tau, processed in that fixed order with one
+``rng.choice(perturb_factors)`` each: alpha, lr and tau are multiplied by the factor, discount
+moves through ``1 - discount`` (0.99 under 1.25 becomes 0.9875: the effective horizon scales
+by 1 / factor).  A field that is not explored is the parent's.  ``bounds`` maps a field to
+(lo, hi), either may be None; ``alpha_bounds`` is ``bounds["alpha"]``; discount and tau are
+kept in [0, 1], which the engine requires.  ``base`` gives the population defaults
+(AgentConfig's lr, discount, tau) that stand in where a parent leaves an explored field None.
+The member-batched engine keeps the three per member (``Population.set_member_hparams``), so
+a child's values hold from its clone on.  Lineage rows carry ``parent_<f>`` / ``child_<f>``
+for the explored fields beyond alpha.
 
 ``parent_of`` maps every child to its parent: the Trainer keys its cloning on it
 (``Population.clone_members`` copies the parent's training state into the freed slot).
@@ -27,12 +39,14 @@ from hpo.strategy import HpoStrategy
 from trainer.config import ExperimentConfig
 
 SEED_RANGE = 10000  # tune_alpha.py draws the initial seeds from range(10000) too
+FIELDS = ("alpha", "lr", "discount", "tau")  # the order explored fields are perturbed in
+DEFAULT_BOUNDS = {"discount": (0.0, 1.0), "tau": (0.0, 1.0)}  # the engine's ranges
 
 
 class PopulationBasedTraining(HpoStrategy):
     def __init__(self, population, total_evaluations: int, ready_interval: int = 1, truncation: float = 0.25,
                  perturb_factors=(0.8, 1.25), alpha_bounds=None, history_length: int = 1, seed: int = 0,
-                 state_dict: dict | None = None) -> None:
+                 state_dict: dict | None = None, explore=("alpha",), bounds=None, base=None) -> None:
         super().__init__(set(population), total_evaluations, state_dict)
         if ready_interval < 1 or history_length < 1:
             raise ValueError("ready_interval and history_length must be >= 1")
@@ -44,6 +58,24 @@ class PopulationBasedTraining(HpoStrategy):
         self.truncation = float(truncation)
         self.perturb_factors = tuple(float(f) for f in perturb_factors)
         self.alpha_bounds = None if alpha_bounds is None else (alpha_bounds[0], alpha_bounds[1])
+        unknown = [f for f in explore if f not in FIELDS]
+        if unknown:
+            raise ValueError(f"explore must be a subset of {FIELDS}, got {unknown}")
+        self.explore = tuple(f for f in FIELDS if f in explore)
+        self.bounds = dict(DEFAULT_BOUNDS)
+        for f, b in (bounds or {}).items():
+            if f not in FIELDS:
+                raise ValueError(f"bounds: unknown field {f!r}")
+            self.bounds[f] = (b[0], b[1])
+        if "alpha" in self.bounds:
+            if self.alpha_bounds is not None and self.alpha_bounds != self.bounds["alpha"]:
+                raise ValueError("alpha_bounds and bounds['alpha'] disagree: give one of them")
+            self.alpha_bounds = self.bounds["alpha"]
+        self.bounds["alpha"] = self.alpha_bounds
+        self.base = dict(base or {})
+        for f in self.explore:
+            if f != "alpha" and self.base.get(f) is None and any(getattr(c, f, None) is None for c in population):
+                raise ValueError(f"explore {f!r}: a candidate leaves it None and base gives no default")
         self.history_length = int(history_length)
         self.rng = random.Random(seed)
         self.candidate_scores = defaultdict(list)
@@ -84,15 +116,25 @@ class PopulationBasedTraining(HpoStrategy):
         recent = self.candidate_scores[candidate][-self.history_length:]
         return sum(recent) / len(recent) if recent else float("-inf")
 
-    def _clip(self, alpha: float) -> float:
-        if self.alpha_bounds is None:
+    def _clip(self, alpha: float, field: str = "alpha") -> float:
+        bounds = self.bounds.get(field)
+        if bounds is None:
             return alpha
-        lo, hi = self.alpha_bounds
+        lo, hi = bounds
         if lo is not None:
             alpha = max(float(lo), alpha)
         if hi is not None:
             alpha = min(float(hi), alpha)
         return alpha
+
+    def _value(self, cfg, field: str):
+        v = getattr(cfg, field, None)
+        return self.base.get(field) if v is None and field != "alpha" else v
+
+    def _perturb(self, field: str, value: float, factor: float) -> float:
+        if field == "discount":
+            return self._clip(1.0 - (1.0 - value) * factor, field)
+        return self._clip(value * factor, field)
 
     def _fresh_seed(self, used: set) -> int:
         if len(used) >= SEED_RANGE:
@@ -125,13 +167,20 @@ class PopulationBasedTraining(HpoStrategy):
         population = set(self.population)
         for loser in worst:
             parent = self.rng.choice(best)
-            factor = self.rng.choice(self.perturb_factors)
-            child = ExperimentConfig(alpha=self._clip(parent.alpha * factor), seed=self._fresh_seed(used))
+            fields = {f: getattr(parent, f, None) for f in FIELDS}  # not explored: the parent's
+            for f in self.explore:
+                factor = self.rng.choice(self.perturb_factors)
+                fields[f] = self._perturb(f, self._value(parent, f), factor)
+            child = ExperimentConfig(seed=self._fresh_seed(used), **fields)
             self.candidate_scores[child] = list(self.candidate_scores[parent])
             self.parent_of[child] = parent
-            self.lineage.append({"round": self.exploit_rounds, "child": child, "parent": parent,
-                                 "parent_alpha": parent.alpha, "child_alpha": child.alpha,
-                                 "parent_score": self._mean_recent(parent)})
+            row = {"round": self.exploit_rounds, "child": child, "parent": parent,
+                   "parent_alpha": parent.alpha, "child_alpha": child.alpha,
+                   "parent_score": self._mean_recent(parent)}
+            for f in self.explore:
+                if f != "alpha":
+                    row[f"parent_{f}"], row[f"child_{f}"] = self._value(parent, f), getattr(child, f)
+            self.lineage.append(row)
             population.discard(loser)
             population.add(child)
         self.population = population

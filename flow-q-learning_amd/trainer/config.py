@@ -34,9 +34,16 @@ class AgentConfig:
 @dataclass(frozen=True)
 class ExperimentConfig:
     """One population member: the tuned hyper-parameters (hashable: used as a
-    dict key by Trainer and the HPO strategies)."""
+    dict key by Trainer and the HPO strategies).  ``seed`` and ``alpha`` are the
+    reference's fields; ``lr``, ``discount`` and ``tau`` [no reference counterpart] are the
+    member's own values in the population engine (Population.set_member_hparams).  A
+    field left None means the TrainerConfig's AgentConfig value, and appears neither in the
+    experiment name nor in ``member_eval_seed``."""
     seed: int | None = None
     alpha: float | None = None
+    lr: float | None = None
+    discount: float | None = None
+    tau: float | None = None
 
 
 @dataclass

@@ -50,6 +50,11 @@ MODEL_ROLLOUT_ENSEMBLE_MSG = ("branches under the env-model ensemble (--model_ro
 LINEAGE_COLUMNS = ("round", "step", "child", "parent", "parent_alpha", "child_alpha", "parent_score")
 
 
+def member_hparams_for(acfg) -> dict:
+    """The per-member engine hyper-parameters of an AgentConfig (Population.set_member_hparams)."""
+    return {"lr": float(acfg.lr), "discount": float(acfg.discount), "tau": float(acfg.tau)}
+
+
 class Trainer:
     _clones = False  # (DistributedTrainer refuses cloning strategies)
 
@@ -102,15 +107,18 @@ class Trainer:
     # ----------------------------------------------------------- population
     def _make_population(self, configs, device):
         example = self.task.sample("train", 1)
-        alphas, seeds = [], []
+        alphas, seeds, hparams = [], [], []
         for cfg in configs:
             acfg, _ = agent_config_for(self.config, cfg)
             alphas.append(acfg.alpha)
             seeds.append(acfg.seed if cfg.seed is None else cfg.seed)
+            hparams.append(member_hparams_for(acfg))
+        # the shared fields (widths, batch size, ...) come from the first config; lr, discount
+        # and tau are per member, each from its own AgentConfig
         acfg, _ = agent_config_for(self.config, configs[0])
         pcfg = PopulationConfig.from_agent_config(asdict(acfg), example["observations"].shape[-1],
                                                   example["actions"].shape[-1])
-        pop = Population(pcfg, alphas, seeds, device=device)
+        pop = Population(pcfg, alphas, seeds, device=device, hparams=hparams)
         dd = self.task.device_datasets()
         if dd is not None:
             pop.set_dataset(dd["train"], "train")
@@ -132,6 +140,7 @@ class Trainer:
         slot = self._free_slots.pop(0)
         acfg, _ = agent_config_for(self.config, cfg)
         self.population.set_member(slot, acfg.alpha, acfg.seed if cfg.seed is None else cfg.seed, reinit=True)
+        self.population.set_member_hparams(slot, **member_hparams_for(acfg))  # (set_member keeps the slot's)
         self.member_of[cfg] = slot
         return slot
 
@@ -284,13 +293,15 @@ class Trainer:
             pairs.append((cfg, parent, self._free_slots.pop(0)))
         if not pairs:
             return
-        alphas, seeds = [], []
+        alphas, seeds, hparams = [], [], []
         for cfg, _, _ in pairs:
             acfg, _ = agent_config_for(self.config, cfg)
             alphas.append(acfg.alpha)
             seeds.append(acfg.seed if cfg.seed is None else cfg.seed)
+            hparams.append(member_hparams_for(acfg))
+        # the clone hands the child its parent's lr, discount and tau; its own follow
         self.population.clone_members([self.member_of[p] for _, p, _ in pairs], [s for _, _, s in pairs],
-                                      alphas=alphas, seeds=seeds)
+                                      alphas=alphas, seeds=seeds, hparams=hparams)
         self.population.sync()
         rows = {row["child"]: row for row in getattr(self.strategy, "lineage", [])}
         for cfg, parent, slot in pairs:
@@ -304,11 +315,19 @@ class Trainer:
                                  "child": exp.experiment_name, "parent": pexp.experiment_name,
                                  "parent_alpha": parent.alpha, "child_alpha": cfg.alpha,
                                  "parent_score": row.get("parent_score", "")})
+            for k in self._extra_lineage_columns():
+                self.lineage[-1][k] = row.get(k, "")
+
+    def _extra_lineage_columns(self) -> tuple:
+        """parent_<f> / child_<f> of the fields beyond alpha that the strategy explores."""
+        extra = [f for f in getattr(self.strategy, "explore", ()) if f != "alpha"]
+        return tuple(f"{side}_{f}" for f in extra for side in ("parent", "child"))
 
     def _write_lineage(self) -> None:
         path = Path(self.config.save_directory) / self.config.env_name / "pbt_lineage.csv"
         path.parent.mkdir(parents=True, exist_ok=True)
+        columns = LINEAGE_COLUMNS + self._extra_lineage_columns()
         with open(path, "w") as f:
-            f.write(",".join(LINEAGE_COLUMNS) + "\n")
+            f.write(",".join(columns) + "\n")
             for row in self.lineage:
-                f.write(",".join(str(row[k]) for k in LINEAGE_COLUMNS) + "\n")
+                f.write(",".join(str(row.get(k, "")) for k in columns) + "\n")

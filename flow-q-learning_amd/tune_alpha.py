@@ -9,6 +9,13 @@ the whole population (here: all members together on the GPU) and writes
 replaced by on-device clones of the best under a perturbed alpha, the population stays
 full; one GPU only; <save>/<env>/pbt_lineage.csv records every clone).
 
+--lrs / --discounts / --taus (each one or more values) extend the grid to alpha x seed x
+those: every combination is its own ExperimentConfig and trains as one member of the same
+population under its own learning rate, discount and target-EMA tau (the engine keeps the
+three per member).  Without them the grid, the seeds and --job_id are the reference's.
+--strategy pbt --pbt_explore alpha lr discount tau perturbs the named fields (default: alpha),
+within --pbt_{lr,discount,tau}_{min,max}.
+
 Data: --task synthetic (default; SURVEY.md 8d transitions + a toy evaluation
 env), --task npz (local OGBench .npz files under --data_directory) or --task
 simulated (candidates scored by world-model rollouts on the GPU).
@@ -108,6 +115,14 @@ def build_parser():
     parser.add_argument("--pbt_truncation", type=float, default=0.25)
     parser.add_argument("--pbt_alpha_min", type=float, default=None)
     parser.add_argument("--pbt_alpha_max", type=float, default=None)
+    parser.add_argument("--pbt_explore", nargs="+", choices=("alpha", "lr", "discount", "tau"), default=["alpha"])
+    for f in ("lr", "discount", "tau"):
+        parser.add_argument(f"--pbt_{f}_min", type=float, default=None)
+        parser.add_argument(f"--pbt_{f}_max", type=float, default=None)
+    # per-member lr / discount / tau grids (none given: the alpha x seed grid alone)
+    parser.add_argument("--lrs", type=float, nargs="+", default=None)
+    parser.add_argument("--discounts", type=float, nargs="+", default=None)
+    parser.add_argument("--taus", type=float, nargs="+", default=None)
     # --task simulated: score under the K env models saved by train_env_model.py --ensemble_size K
     # (0: the single model); --ensemble_score: the mean or the min of the per-model success rates,
     # or mixed episodes that draw a model afresh at every step (task/offline_task_simulated.py)
@@ -117,6 +132,15 @@ def build_parser():
     # train_env_model.py --bootstrap); 0: all K
     parser.add_argument("--env_model_elites", type=int, default=0)
     return parser
+
+
+def experiment_grid(combinations, lrs=None, discounts=None, taus=None):
+    """The ExperimentConfigs of a run: the (alpha, seed) combinations in their order, each
+    crossed with the given lr, discount and tau values (innermost); an axis left None stays
+    out of the grid and its field None."""
+    axes = [v if v else [None] for v in (lrs, discounts, taus)]
+    return [ExperimentConfig(seed=seed, alpha=alpha, lr=lr, discount=discount, tau=tau)
+            for (alpha, seed), lr, discount, tau in itertools.product(combinations, *axes)]
 
 
 def main(argv=None):
@@ -151,11 +175,11 @@ def main(argv=None):
     alpha_values = np.logspace(np.log10(3), np.log10(1000), num=args.number_of_alphas).tolist()
     seeds = random.sample(range(10000), args.number_of_seeds)
     combinations = list(itertools.product(alpha_values, seeds))
+    configs = experiment_grid(combinations, args.lrs, args.discounts, args.taus)
     task = make_task(args, config)
 
     if args.single_experiment:
-        alpha, seed = combinations[args.job_id]
-        experiment = Experiment(task, config, ExperimentConfig(seed=seed, alpha=alpha))
+        experiment = Experiment(task, config, configs[args.job_id])
         done = False
         while not done:
             done = experiment.train(config.eval_interval)
@@ -163,7 +187,6 @@ def main(argv=None):
         experiment.stop()
         return
 
-    configs = [ExperimentConfig(seed=seed, alpha=alpha) for alpha, seed in combinations]
     ckpt = config.save_directory / config.env_name / "checkpoint.pkl"
     state = {}
     if ckpt.exists():
@@ -175,10 +198,16 @@ def main(argv=None):
         bounds = None
         if args.pbt_alpha_min is not None or args.pbt_alpha_max is not None:
             bounds = (args.pbt_alpha_min, args.pbt_alpha_max)
+        hp_bounds = {f: (getattr(args, f"pbt_{f}_min"), getattr(args, f"pbt_{f}_max"))
+                     for f in ("lr", "discount", "tau")
+                     if getattr(args, f"pbt_{f}_min") is not None or getattr(args, f"pbt_{f}_max") is not None}
         strategy = PopulationBasedTraining(population=set(configs), total_evaluations=args.max_evaluations,
                                            ready_interval=args.pbt_ready_interval, truncation=args.pbt_truncation,
                                            alpha_bounds=bounds, history_length=args.history_length,
-                                           seed=config.seed, state_dict=state.get("strategy"))
+                                           seed=config.seed, state_dict=state.get("strategy"),
+                                           explore=tuple(args.pbt_explore), bounds=hp_bounds,
+                                           base={"lr": config.agent.lr, "discount": config.agent.discount,
+                                                 "tau": config.agent.tau})
     else:
         horizon = args.max_evaluations if args.halving_horizon is None else args.halving_horizon
         strategy = SuccessiveHalving(population=set(configs), total_evaluations=horizon,

@@ -62,9 +62,9 @@ typedef struct fqlpop_config {
     int flow_steps;        /* Euler steps (10) */
     int q_agg_min;         /* q_agg == "min" (else "mean") */
     int normalize_q_loss;  /* normalize_q_loss */
-    float discount;        /* 0.99 */
-    float tau;             /* 0.005 */
-    float lr;              /* Adam learning rate 3e-4 */
+    float discount;        /* 0.99   } the value every member starts with; per member:  */
+    float tau;             /* 0.005  } fqlpop_set_member_hparams                         */
+    float lr;              /* Adam learning rate 3e-4 (likewise)                         */
     int use_graph;         /* capture each step into a hipGraph (1) or launch eagerly (0) */
 } fqlpop_config;
 
@@ -198,12 +198,31 @@ int fqlpop_get_count(fqlpop_t* h, int member, int32_t* count);
 int fqlpop_set_count(fqlpop_t* h, int member, int32_t count);
 
 /* Per-member alpha and seed (ExperimentConfig.alpha/seed,
- * trainer/config.py:25-28); re-initialises params when reinit != 0. */
+ * trainer/config.py:25-28); re-initialises params when reinit != 0.  The member's hparams
+ * (below) stay as they are, with or without reinit. */
 int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int reinit);
+
+/* Per-member learning rate, discount and target-EMA tau: hp[FQLPOP_HP_COUNT], indexed by
+ * FQLPOP_HP_*.  fqlpop_create gives every member the fqlpop_config values.  They live in
+ * device memory and the step's kernels read their member's row, so a change needs no
+ * recapture: set synchronises as fqlpop_set_member does and holds from the next enqueued
+ * step on, the replay of a captured graph included; fqlpop_total_loss uses the member's
+ * discount too.  set returns FQLPOP_E_ARG before any GPU call, and changes nothing, for a
+ * member out of range, an lr that is negative or not finite, or a discount or tau that is
+ * NaN or outside [0, 1].  get answers from the host mirror without synchronising.
+ * The sampler key of a member is made of its seed and alpha alone: members that share both
+ * and differ only in hparams draw the same minibatches and noises (a controlled comparison).
+ * The env-model trainers have schedules of their own.  [no reference counterpart: the
+ * reference gives every experiment one AgentConfig] */
+#define FQLPOP_HP_COUNT 3
+enum { FQLPOP_HP_LR = 0, FQLPOP_HP_DISCOUNT = 1, FQLPOP_HP_TAU = 2 };
+int fqlpop_set_member_hparams(fqlpop_t* h, int member, const float* hp /*[FQLPOP_HP_COUNT]*/);
+int fqlpop_get_member_hparams(fqlpop_t* h, int member, float* hp);
 
 /* Copies the complete training state of member src[i] into member dst[i], i < n_pairs, and
  * gives dst[i] alpha alphas[i] and seed seeds[i]: both parameter buffers and their W^T
- * copies, the target critic, Adam m and v and the update count, in one device launch on the
+ * copies, the target critic, Adam m and v, the update count and src[i]'s hparams (lr,
+ * discount, tau; the host mirror follows), in one device launch on the
  * stream the steps run on (and, with fqlpop_synth_create's rings, the ring and its counters
  * in a second one).  Ordered after the steps enqueued before it and before later
  * ones; no host staging and no synchronisation, so it may return before the copy has run
