@@ -1021,6 +1021,17 @@ DEV int opaque_tid() {
     return v;
 }
 
+// em_sweep_kernel's static LDS: the __shared__ arrays it declares below (the diagnostic build's
+// ph too), which the CU's LDS holds beside the dynamic part (fqlpop_emtrain_create: sw_fits)
+#ifdef FQ_DIAG
+constexpr int SW_PH_LDS = (int)sizeof(unsigned long long[EM_PH_N]);
+#else
+constexpr int SW_PH_LDS = 0;
+#endif
+constexpr int SW_STATIC_LDS = (int)(sizeof(float[NLOG][R]) + sizeof(float[R]) + sizeof(long long[R]) +
+                                    2 * sizeof(float[R]) + sizeof(float[2][R])) + SW_PH_LDS;
+constexpr int CU_LDS_BYTES = 160 * 1024;
+
 // record of one (block, step) in a.seq: xhat [K0][R] | rstd [R] | acts[0..n-1] | the step's own
 // output gradient [D][R] | (sweep path) g_i [dims[i + 1]][R], i = 0..n-1 (each layer's output
 // gradient after the ReLU mask: the dW operands)
@@ -1030,11 +1041,14 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     __shared__ float lab[R];
     __shared__ long long rowbase[R];
     __shared__ float mu_s[R], rs_s[R], cs[2][R];
+    static_assert(sizeof(lsum) + sizeof(lab) + sizeof(rowbase) + sizeof(mu_s) + sizeof(rs_s) + sizeof(cs) + SW_PH_LDS ==
+                      SW_STATIC_LDS, "SW_STATIC_LDS sums em_sweep_kernel's __shared__ arrays");
     ModelView mv;
     if (!ens_enter(a, mv)) return;
     const int tid = threadIdx.x, blk = mv.blk;
 #ifdef FQ_DIAG  // phase times of block 0 (s_memrealtime, 100 MHz), summed over the steps
     __shared__ unsigned long long ph[EM_PH_N];
+    static_assert(sizeof(ph) == SW_PH_LDS, "SW_PH_LDS is ph");
     unsigned long long ph_prev = 0;
     const bool ph_on = a.probe != nullptr && blockIdx.x == 0;
     if (ph_on && tid < EM_PH_N) ph[tid] = 0;
@@ -1123,7 +1137,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     sw_load(fw_op(0), fr);
     // the next step's input rows (actions; observations at t = 0 only; next observations; rewards),
     // one value per thread, loaded a step ahead
-    const int nin = (A + D + 1) * R;
+    const int nin = (A + D + 1) * R;  // <= SW_NT: sw_fits admits no shape that needs a second value per thread
     auto in_load = [&](int t, int tid) -> float {
         if (tid >= nin || t >= T) return 0.f;
         const int r = tid % R, f = tid / R;
@@ -1721,8 +1735,10 @@ static void em_layouts(const fqlpop_emtrain_config* c, Net* net, long long* P, N
 }
 
 // the sweep path takes every Dense op (both directions, the frozen termination predictor's
-// too) as one unit per wave, and a step's record in 16 loads per thread
-static bool sw_fits(const Net& n, const Net& tpn, bool tp, int D) {
+// too) as one unit per wave, a step's record in SW_RQ loads per thread, and a step's inputs
+// (actions, next observations, rewards: in_load) as one value per thread
+static bool sw_fits(const Net& n, const Net& tpn, bool tp, int D, int A) {
+    if ((long long)R * (A + D + 1) > SW_NT) return false;
     for (int i = 0; i < n.n; ++i)
         if (!sw_op_fits(n.dims[i], n.dims[i + 1]) || !sw_op_fits(n.dims[i + 1], n.dims[i])) return false;
     if (tp)
@@ -1780,9 +1796,10 @@ static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* para
         ARGCHK(fl * 4 <= 150 * 1024, "env-model layer widths exceed the LDS budget of the fused step");
         h->lds_bytes = (int)(fl * 4);
         h->blocks = cfg->batch_size / R;
-        if (ms && fq::engine_option_em_seq_sweep() && sw_fits(h->net, h->tpn, h->tpn.n > 0, cfg->obs_dim)) {
+        if (ms && fq::engine_option_em_seq_sweep() && sw_fits(h->net, h->tpn, h->tpn.n > 0, cfg->obs_dim, cfg->action_dim)) {
             const long long sl = fl + SW_SCR + 4 * h->net.dims[0];
-            if (sl * 4 <= 160 * 1024) {
+            // dynamic + em_sweep_kernel's static LDS within the CU's; otherwise the fallback
+            if (sl * 4 + SW_STATIC_LDS <= CU_LDS_BYTES) {
                 h->sweep = true;
                 h->sweep_lds = (int)(sl * 4);
                 // dW GEMM blocks: 16-step chunks at least, at most 4 chunks per sequence block

@@ -5,6 +5,7 @@ tests/test_emtrain_cpu.py (not a test module)."""
 from __future__ import annotations
 
 import contextlib
+import functools
 
 import numpy as np
 
@@ -23,6 +24,15 @@ SHAPES = {
     "C": (69, 20, (144, 272), (272, 144)),      # KS = 32 path; 9 tiles for 8 waves; no sweep plan
     "D": (42, 8, (96, 48), (48,)),              # 96: a ragged 64-tile of the dW GEMM; K0 = 50
     "E": (28, 5, (64,), (64,)),
+    # the edges of the sweep's admission rule (em_plan; csrc/emtrain.hip: sw_fits, em_create)
+    "F": (55, 8, (32,), (16,)),                 # a step's inputs (A + D + 1) 16 = 1024: one per thread, rewards last
+    "G": (56, 8, (32,), (16,)),                 # 1040 inputs: the rewards would be the values dropped
+    "H": (69, 21, (128, 128), (128,)),          # 1456 inputs: humanoid-sized, non-default widths
+    "I": (39, 5, (128, 256, 128), (64,)),       # a step's record 640 rows = SW_RQ SW_NT / 16 exactly
+    "J": (40, 4, (128, 256, 128), (64,)),       # record 641
+    "K": (17, 8, (128, 256, 128), (128, 256, 96, 128, 256)),   # tw > 0: dynamic sweep LDS 163 216 bytes,
+                                                # within the CU's only without the kernel's static LDS
+    "L": (39, 5, (128, 256, 128), (128, 256, 128)),            # I under the default frozen predictor: 150 272 bytes
 }
 SINGLE_CASES = [("A", 16), ("B", 48), ("C", 32)]          # (shape, batch size)
 # (shape, T, batch size, em_seq_sweep, plan: sweep, tchunks)
@@ -31,11 +41,35 @@ MULTISTEP_CASES = [(s, T_, B, opt, bool(opt), tc if opt else 1)
                    for opt in (1, 0)]
 MULTISTEP_FALLBACK = ("C", 4, 16, None, False, 1)         # the default option, no sweep plan
 ENSEMBLE_CASE = ("B", 48, 3)                              # shape, batch size, K
+# (shape, T, batch size, em_seq_sweep, plan: sweep, tchunks, termination weights); option None is
+# the default (sweep where the plan admits it): the rows past an edge must fall back by themselves
+MULTISTEP_EDGE_CASES = (
+    [(s, T_, 16, opt, bool(opt), 1, tws) for s, T_, tws in (("F", 3, (0.0, 1.0)), ("I", 2, (0.0, 1.0)),
+                                                             ("L", 2, (1.0,)), ("A", 1, (0.0, 1.0)))
+     for opt in (1, 0)] +
+    [(s, T_, 16, None, False, 1, tws) for s, T_, tws in (("G", 3, (0.0, 1.0)), ("H", 2, (0.0, 1.0)),
+                                                          ("J", 2, (0.0, 1.0)), ("K", 2, (1.0,)))])
+_W3, _DEEP = (128, 256, 128), (128, 256, 96, 128, 256)
+# (obs, act, hidden, tp_hidden, tw, sweep): the edge rows, their neighbours one unit either side of
+# each limit, and the static-LDS window (dynamic sweep LDS 162 369 .. 163 840 bytes) from just
+# below (obs 15) through its middle (16, 17, 18) to just above (19)
+PLAN_PROBES = (
+    [(D, 8, (32,), (16,), tw, D <= 55) for D in (54, 55, 56) for tw in (0.0, 1.0)] +
+    [(55, 9, (32,), (16,), 0.0, False), (69, 21, (128, 128), (128,), 1.0, False),
+     (38, 5, _W3, (64,), 0.0, True), (39, 5, _W3, (64,), 0.0, True), (39, 5, _W3, _W3, 1.0, True),
+     (40, 4, _W3, (64,), 0.0, False), (39, 6, _W3, (64,), 0.0, False), (17, 8, _W3, _DEEP, 0.0, True)] +
+    [(D, 8, _W3, _DEEP, 1.0, D <= 15) for D in (15, 16, 17, 18, 19)])
+ENSEMBLE_SWEEP_CASE = ("F", 3, 16, 2)                     # shape, T, batch size, K: a second model's slot
 
 # fqlpop_emtrain_create's constants (csrc/emtrain.hip)
 _R, _SW_NW, _SW_FM, _SW_NT, _SW_RQ = 16, 16, 32, 1024, 10
 _SW_SCR = _SW_NW * 16 * _R
 LDS_BUDGET, SWEEP_LDS_BUDGET = 150 * 1024, 160 * 1024
+CU_LDS_BYTES = 160 * 1024      # a CU's LDS: a block's dynamic and static parts together
+_NLOG = 16
+# em_sweep_kernel's __shared__ arrays (SW_STATIC_LDS): lsum [NLOG][R], lab [R], rowbase [R] (8 bytes
+# each), mu_s, rs_s [R], cs [2][R]; em_seq_grad_kernel declares the same
+SW_STATIC_LDS = 4 * _NLOG * _R + 4 * _R + 8 * _R + 2 * 4 * _R + 4 * 2 * _R
 
 
 def spec_of(shape: str) -> em.EnvModelSpec:
@@ -51,31 +85,61 @@ def sw_op_plan(Kc: int, No: int):
     return ntile, S, (nks + S - 1) // S, nks
 
 
+@functools.lru_cache(maxsize=None)
 def _sw_op_fits(Kc, No):
     ntile, S, cks, _ = sw_op_plan(Kc, No)
     return ntile * S <= _SW_NW and cks <= _SW_FM
 
 
-def em_plan(shape: str, kind: str, tw: float, T_: int = 1, B: int = 16, sweep_option: bool = True) -> dict:
+_FITS_N = 320
+_fits_table = []
+
+
+def _op_fits(Kc, No):
+    """_sw_op_fits of both directions of an op; either width may be an array (the enumeration of
+    tests/test_emtrain_cpu.py), then through a table of _sw_op_fits filled on first use."""
+    if np.ndim(Kc) == 0 and np.ndim(No) == 0:
+        return _sw_op_fits(Kc, No) and _sw_op_fits(No, Kc)
+    if not _fits_table:
+        _fits_table.append(np.array([[k > 0 and n > 0 and _sw_op_fits(k, n) for n in range(_FITS_N)]
+                                     for k in range(_FITS_N)]))
+    return _fits_table[0][Kc, No] & _fits_table[0][No, Kc]     # (a width >= _FITS_N: an IndexError)
+
+
+def em_plan_dims(D, A: int, hid, tph, kind: str, tw: float, T_: int = 1, B: int = 16,
+                 sweep_option: bool = True) -> dict:
     """What fqlpop_emtrain_create decides for ``kind`` in ("state", "termination", "multistep"):
-    the fused step's LDS bytes, whether the multistep step takes the sweep path, its LDS bytes,
-    the T chunks of the dW GEMM and the blocks per model."""
-    spec = spec_of(shape)
-    D = spec.obs_dim
-    dims = spec.tp_dims() if kind == "termination" else spec.sp_dims()
-    tdims = spec.tp_dims() if (kind != "termination" and tw > 0) else []
+    the fused step's LDS bytes, whether the multistep step takes the sweep path, its (dynamic) LDS
+    bytes, the T chunks of the dW GEMM and the blocks per model; and the sizes the sweep's rule
+    bounds: a step's inputs ``nin``, its record ``record`` (floats) and the dynamic LDS bytes the
+    sweep would ask for, ``sweep_need``.  ``D`` may be an array of observation widths: then
+    every entry that depends on it is an array."""
+    sp_dims, tp_dims = [D + A, *hid, D], [D, *tph, 1]
+    dims = tp_dims if kind == "termination" else sp_dims
+    tdims = tp_dims if (kind != "termination" and tw > 0) else []
     ms = kind == "multistep"
-    maxd = max(dims + tdims)
+    maxd = functools.reduce(np.maximum, dims + tdims)
     fl = _R * (2 * dims[0] + sum(dims) + 3 * maxd + D + sum(tdims) + (D * (1 if tdims else 2) if ms else 0))
-    plan = {"lds": 4 * fl, "sweep": False, "sweep_lds": 0, "tchunks": 1, "blocks": B // _R}
+    sl = fl + _SW_SCR + 4 * dims[0]
+    nin, record = _R * (A + D + 1), _R * (dims[0] + 1 + sum(dims[:-1]) + D)
+    sweep = np.zeros(np.shape(D), bool)
     if ms and sweep_option:
+        # sw_fits: every op one unit per wave, a step's inputs one value per thread, its record
+        # SW_RQ per thread; em_create: dynamic + em_sweep_kernel's static LDS within the CU's
         ops = list(zip(dims[:-1], dims[1:])) + list(zip(tdims[:-1], tdims[1:]))
-        fits = all(_sw_op_fits(k, n) and _sw_op_fits(n, k) for k, n in ops)
-        fits = fits and _R * (dims[0] + 1 + sum(dims[:-1]) + D) <= _SW_RQ * _SW_NT
-        sl = fl + _SW_SCR + 4 * dims[0]
-        if fits and 4 * sl <= SWEEP_LDS_BUDGET:
-            plan.update(sweep=True, sweep_lds=4 * sl, tchunks=max(1, min(4, T_ // 16)))
+        fits = functools.reduce(np.logical_and, [_op_fits(k, n) for k, n in ops])
+        sweep = fits & (nin <= _SW_NT) & (record <= _SW_RQ * _SW_NT) & (4 * sl + SW_STATIC_LDS <= CU_LDS_BYTES)
+    plan = {"lds": 4 * fl, "sweep": sweep, "sweep_lds": np.where(sweep, 4 * sl, 0),
+            "tchunks": np.where(sweep, max(1, min(4, T_ // 16)), 1), "blocks": B // _R,
+            "nin": nin, "record": record, "sweep_need": 4 * sl if ms else 0}
+    if np.ndim(D) == 0:
+        plan = {k: v.item() if isinstance(v, (np.ndarray, np.generic)) else v for k, v in plan.items()}
     return plan
+
+
+def em_plan(shape: str, kind: str, tw: float, T_: int = 1, B: int = 16, sweep_option: bool = True) -> dict:
+    """em_plan_dims of a named shape."""
+    return em_plan_dims(*SHAPES[shape], kind, tw, T_, B, sweep_option)
 
 
 def tchunk_lengths(T_: int, tchunks: int):

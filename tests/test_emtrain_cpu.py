@@ -1,6 +1,7 @@
 """CPU checks of the env-model trainer oracle (oracle/envmodel_train_oracle.py):
 hand-written gradients vs torch autograd in float64, known answers of the focal
 loss, the cosine schedule and the Adam step."""
+import itertools
 import math
 import os
 import sys
@@ -266,6 +267,7 @@ import _emtrain_cases as C  # noqa: E402
 from _helpers import EM_GRAD_REL, EmOptimiserChecker, em_leaf_table, em_logs_ratio  # noqa: E402
 
 _MS = C.MULTISTEP_CASES + [C.MULTISTEP_FALLBACK]
+_EDGE = C.MULTISTEP_EDGE_CASES
 
 
 def test_case_table_fits_the_lds_budget_and_reaches_its_edges():
@@ -292,6 +294,28 @@ def test_case_table_fits_the_lds_budget_and_reaches_its_edges():
     assert C.tchunk_lengths(67, 4) == [16, 17, 17, 17]
     # A: one block, one k-step of the first layer
     assert C.SINGLE_CASES[0] == ("A", 16) and sum(C.SHAPES["A"][:2]) == 4
+    # the edge rows: every case creatable, on the path its row names, within the CU's LDS
+    for shape, T_, B, option, sweep, tchunks, tws in _EDGE:
+        for tw in tws:
+            plan = C.em_plan(shape, "multistep", tw, T_, B, option != 0)
+            assert plan["lds"] <= C.LDS_BUDGET and plan["sweep_lds"] + C.SW_STATIC_LDS <= C.CU_LDS_BYTES, (shape, tw)
+            assert (plan["sweep"], plan["tchunks"], plan["blocks"]) == (sweep, tchunks, B // 16), (shape, T_, tw, plan)
+    edge = {s: C.em_plan(s, "multistep", 1.0, 2, 16) for s in "FGHIJKL"}
+    # F, G, H: a step's inputs at SW_NT = 1024 values exactly (rewards in threads 1008..1023), 16 and 432 past it
+    assert [edge[s]["nin"] for s in "FGH"] == [1024, 1040, 1456]
+    assert (55 + 8) * 16 == 1008 and [edge[s]["sweep"] for s in "FGH"] == [True, False, False]
+    # I, L, J: a step's record at SW_RQ SW_NT = 10240 floats (640 rows of 16) exactly, and one row past it
+    assert [edge[s]["record"] for s in "ILJ"] == [640 * 16, 640 * 16, 641 * 16]
+    assert [edge[s]["sweep"] for s in "ILJ"] == [True, True, False] and edge["L"]["sweep_lds"] == 150272
+    assert all(edge[s]["nin"] <= 1024 for s in "IJKL")
+    # K: the dynamic part alone fits the CU's LDS, with em_sweep_kernel's static arrays it does not;
+    # nothing else refuses it (without the frozen predictor it sweeps)
+    assert edge["K"]["sweep_need"] == 163216 <= C.CU_LDS_BYTES < 163216 + C.SW_STATIC_LDS == 164688
+    assert not edge["K"]["sweep"] and edge["K"]["lds"] == 146432 <= C.LDS_BUDGET
+    assert C.em_plan("K", "multistep", 0.0, 2, 16)["sweep"] and edge["K"]["record"] <= 10240
+    for D, A, hid, tph, tw, sweep in C.PLAN_PROBES:
+        plan = C.em_plan_dims(D, A, hid, tph, "multistep", tw, 2, 16)
+        assert plan["sweep"] == sweep and plan["lds"] <= C.LDS_BUDGET, (D, A, hid, tph, tw, plan)
 
 
 def _case_step(kind, shape, tw, B, T_, seed):
@@ -316,7 +340,8 @@ def _case_step(kind, shape, tw, B, T_, seed):
 
 _COND = [("state", s, tw, B, 1) for s, B in C.SINGLE_CASES for tw in (0.0, 1.0)] + \
         [("termination", s, 0.0, B, 1) for s, B in C.SINGLE_CASES] + \
-        [("multistep", c[0], tw, c[2], c[1]) for c in _MS if c[3] != 0 for tw in (0.0, 1.0)]
+        [("multistep", c[0], tw, c[2], c[1]) for c in _MS if c[3] != 0 for tw in (0.0, 1.0)] + \
+        [("multistep", c[0], tw, c[2], c[1]) for c in _EDGE if c[3] != 0 for tw in c[6]]
 
 
 @pytest.mark.parametrize("kind,shape,tw,B,T_", _COND)
@@ -332,6 +357,28 @@ def test_cases_are_well_conditioned(kind, shape, tw, B, T_):
     for m, k in names:
         d, scale = float(np.abs(g1[m][k] - g0[m][k]).max()), float(np.abs(g0[m][k]).max())
         assert d <= 0.01 * EM_GRAD_REL * scale, (m, k, d / scale)
+
+
+@pytest.mark.parametrize("seed", [6, 9])
+def test_edge_cases_find_their_batches_within_the_cap(seed):
+    """batch_with_margin's 64 draws suffice at every edge case, for both checked steps of the GPU
+    test's streams (6: test_multistep_at_the_edges_of_the_sweep_plan, 9: the ensemble case), at the
+    random-bias parameters the GPU warm-up starts from."""
+    cases = [c for c in _EDGE if c[3] != 0] if seed == 6 else [(*C.ENSEMBLE_SWEEP_CASE[:3], None, True, 1, (1.0,))]
+    for shape, T_, B, _, _, _, tws in cases:
+        spec = C.spec_of(shape)
+        sp, tp = C.random_bias_params(shape, 11)
+        for tw in tws:
+            rng, n = np.random.default_rng(seed), [0]
+
+            def draw():
+                n[0] += 1
+                return C.seq_batch(rng, B, T_, spec.obs_dim, spec.action_dim)
+
+            for _ in range(2):
+                C.batch_with_margin(draw, lambda b: C.oracle_step("multistep", C.f64(sp), b, tw, C.f64(tp)))
+            print(shape, tw, "draws", n[0])
+            assert n[0] <= 8, (shape, tw, n[0])      # far from the cap: no case leans on it
 
 
 class _OracleDevice:
@@ -357,6 +404,14 @@ class _OracleDevice:
             tree["Dense_1"]["bias"] = np.zeros_like(tree["Dense_1"]["bias"])
         if "ln_bias" in self.mut:
             tree["LayerNorm_0"]["bias"] = np.zeros_like(tree["LayerNorm_0"]["bias"])
+        if "stage_64" in self.mut:
+            # em_sweep_kernel's input stage without the rule (A + D + 1) 16 <= SW_NT: one value per
+            # thread is 64 rows; the next-observation rows past them stay the zeros of the LDS clear
+            # and the reward row never reaches lab (uninitialised in the kernel: a constant here)
+            A = batch["actions"].shape[-1]
+            batch = dict(batch, next_observations=batch["next_observations"].copy(),
+                         rewards=np.full_like(batch["rewards"], -1.0))
+            batch["next_observations"][..., max(0, 64 - A):] = 0.0
         logs, grads, _ = C.oracle_step(self.kind, tree, batch, self.tw, tp, keep)
         g = C.flat_of(self.names, grads)
         p, m, v = (a.astype(np.float64) for a in self.state)
@@ -377,7 +432,7 @@ class _OracleDevice:
 _MUT_SHAPE, _MUT_B = "B", 48
 
 
-def _trained_like(kind, shape, B, count, zero_bias=False):
+def _trained_like(kind, shape, B, count, zero_bias=False, T_=1):
     """(flat, m, v, frozen predictor) on the CPU: random biases (or the constructor's zeros),
     moments as three oracle steps leave them, rescaled to ``count`` updates."""
     spec = C.spec_of(shape)
@@ -390,20 +445,22 @@ def _trained_like(kind, shape, B, count, zero_bias=False):
     rng = np.random.default_rng(3)
     p = tree
     for i in range(3):
-        _, grads, _ = C.oracle_step(kind, p, C.row_batch(rng, B, spec.obs_dim, spec.action_dim), 1.0, C.f64(tp),
-                                    np.ones((B, spec.obs_dim)))
+        b = C.seq_batch(rng, B, T_, spec.obs_dim, spec.action_dim) if kind == "multistep" else \
+            C.row_batch(rng, B, spec.obs_dim, spec.action_dim)
+        _, grads, _ = C.oracle_step(kind, p, b, 1.0, C.f64(tp), np.ones((B, spec.obs_dim)))
         p, m, v = T.adam_update(p, grads, m, v, i, C.LR)
     flat = C.flat_of(names, tree)     # the parameters stay the random-bias ones
     return (flat, C.flat_of(names, m) / (1 - 0.9 ** 3) * (1 - 0.9 ** count),
             C.flat_of(names, v) / (1 - 0.999 ** 3) * (1 - 0.999 ** count), tp)
 
 
-def _play(mutations, count=1000, steps=2000, zero_bias=False, n_steps=2):
+def _play(mutations, count=1000, steps=2000, zero_bias=False, n_steps=2, kind="state", shape=_MUT_SHAPE, B=_MUT_B,
+          T_=1):
     """Two checked steps of the (mutated) oracle device from a trained-like state through the
     GPU test's checks: the largest error / bound of each."""
-    kind, shape, B = "state", _MUT_SHAPE, _MUT_B
     spec = C.spec_of(shape)
-    flat, m, v, tp = _trained_like(kind, shape, B, max(count, 1), zero_bias)
+    rel = C.LOG_REL_MS if kind == "multistep" else C.LOG_REL
+    flat, m, v, tp = _trained_like(kind, shape, B, max(count, 1), zero_bias, T_)
     if count == 0:
         m, v = np.zeros_like(m), np.zeros_like(v)
     dev = _OracleDevice(kind, shape, 1.0, steps, flat, m, v, count, tp, mutations)
@@ -413,11 +470,12 @@ def _play(mutations, count=1000, steps=2000, zero_bias=False, n_steps=2):
     for _ in range(n_steps):
         tree = C.tree_of(dev.names, dev.shapes, ck.before()[0])
         b, want_logs, grads = C.batch_with_margin(
-            lambda: C.row_batch(rng, B, spec.obs_dim, spec.action_dim),
+            (lambda: C.seq_batch(rng, B, T_, spec.obs_dim, spec.action_dim)) if kind == "multistep" else
+            (lambda: C.row_batch(rng, B, spec.obs_dim, spec.action_dim)),
             lambda bb: C.oracle_step(kind, tree, bb, 1.0, C.f64(tp)))
         logs = dev.train_step(b)
         ratios, _ = ck.measure(C.flat_of(dev.names, grads), C.LR, steps)
-        ratios["logs"] = em_logs_ratio(logs, want_logs, C.LOG_REL, C.LOG_ABS)
+        ratios["logs"] = em_logs_ratio(logs, want_logs, rel, C.LOG_ABS)
         for k, r in ratios.items():
             acc[k] = max(acc.get(k, 0.0), r)
     return acc, dev
@@ -438,6 +496,20 @@ def test_checks_catch_mutations_from_a_trained_state(mutation, caught_by):
     acc, _ = _play((mutation,))
     print(mutation, acc)
     assert acc[caught_by] >= 10.0, acc
+
+
+@pytest.mark.parametrize("shape,T_", [("G", 3), ("H", 2)])
+def test_checks_catch_an_input_stage_of_64_rows(shape, T_):
+    """What the sweep computed at the shapes its rule now refuses: at G only the rewards are
+    dropped (actions and next observations are rows 0..63 exactly), at H also 26 rows of the next
+    observation.  Either exceeds the logs' and the gradients' bounds by >= 10x at the GPU test's T
+    and batch size, so test_multistep_at_the_edges_of_the_sweep_plan sees the sweep run there."""
+    kw = dict(count=200, steps=400, kind="multistep", shape=shape, B=16, T_=T_)
+    acc, _ = _play((), **kw)
+    assert max(acc.values()) <= 0.5, acc
+    acc, _ = _play(("stage_64",), **kw)
+    print(shape, acc)
+    assert acc["logs"] >= 10.0 and acc["m"] >= 10.0, acc
 
 
 def test_checks_catch_a_missing_clamp():
@@ -469,3 +541,115 @@ def test_frozen_predictor_biases_are_invisible_from_the_constructor_state(mutati
     assert max(acc.values()) <= 0.5, acc
     for which in range(3):
         np.testing.assert_array_equal(good.flat(which), bad.flat(which))
+
+
+# ---------------------------------------------------------------------------
+# Admission implies capacity: every shape em_plan sends to the sweep is within each limit of
+# em_sweep_kernel, restated here from the kernel (csrc/emtrain.hip), one predicate per limit and
+# apart from em_plan; the rule of the commit before this check is kept as _parent_sw_admits.
+# ---------------------------------------------------------------------------
+_GRID_OBS = np.arange(1, 131)
+_GRID_ACT = (1, 2, 5, 8, 21)
+_GRID_W = (8, 20, 32, 50, 64, 96, 128, 144, 192, 256, 272)
+_GRID_TP = ((16,), (64,), (128, 256, 128), (272, 144), C.SHAPES["K"][3])
+_R, _NT, _NW, _FM, _RQ, _SCR = 16, 1024, 16, 32, 10, 16 * 16 * 16      # R, SW_NT, SW_NW, SW_FM, SW_RQ, SW_SCR
+_units_cache = {}
+
+
+def _units(Kc, No):
+    """sw_plan (the kernel's own split of an op into tiles x S units of cks k-steps) against the
+    kernel's two limits on it: (units and fragments fit, the split's reduction fits); a width is an
+    int or the pair (a, b) for a obs + b over _GRID_OBS."""
+    key = (Kc, No)
+    if key not in _units_cache:
+        Kc, No = (x[0] * _GRID_OBS + x[1] if isinstance(x, tuple) else np.full(_GRID_OBS.shape, x) for x in key)
+        ntile, nks = (No + 15) // 16, (Kc + 3) // 4
+        S = np.ones_like(ntile)
+        for _ in range(4):      # S doubles from 1 to at most SW_NW = 16
+            S = np.where((S < _NW) & (ntile * S * 2 <= _NW) & (S * 2 <= nks), 2 * S, S)
+        # sw_compute: one unit per wave (SW_NW waves); sw_load / sw_chain: fr[SW_FM] fragments per chunk;
+        # sw_compute's k-split reduction: q = tid + i SW_NT, i < 4 ("No <= 128 here ... q < 4 SW_NT")
+        _units_cache[key] = ((ntile * S <= _NW) & (-(-nks // S) <= _FM), (S == 1) | (No * _R <= 4 * _NT))
+    return _units_cache[key]
+
+
+def _sweep_ops(A, hid, tph, tw):
+    """(Kc, No) of every op of em_sweep_kernel's programs: fw_op (n layers, the frozen predictor's m
+    layers and its m dX ops) and the backward sweep's dX op of every layer."""
+    dims = [(1, A), *hid, (1, 0)]
+    tdims = [(1, 0), *tph, 1] if tw > 0 else []
+    fw = list(zip(dims[:-1], dims[1:])) + list(zip(tdims[:-1], tdims[1:]))
+    return fw + [(n, k) for k, n in fw]
+
+
+def _kernel_limits(A, hid, tph, tw):
+    """name -> bool [obs]: each limit of em_sweep_kernel, over _GRID_OBS."""
+    D = _GRID_OBS
+    ops = [_units(k, n) for k, n in _sweep_ops(A, hid, tph, tw)]
+    K0, n_act, tsum = D + A, D + A + sum(hid), (D + sum(tph) + 1 if tw > 0 else D)
+    maxd = np.maximum(K0, max(hid + (tph if tw > 0 else ())))
+    # the kernel's LDS carve-up: x0, xhat [K0][R] | acts[0..n] | gA, gB, gC [maxd][R] | nobs [D][R] | tp
+    # acts (or pred [D][R]) | carry [D][R] | scr [SW_SCR] | lnacc, lnp [2][K0] each
+    dyn = 4 * (_R * (2 * K0 + (n_act + D) + 3 * maxd + D + tsum + D) + _SCR + 4 * K0)
+    return {
+        # in_load / `if (tid < nin)`: one staged value per thread of the SW_NT
+        "stage": (A + D + 1) * _R <= _NT,
+        "units": np.logical_and.reduce([u for u, _ in ops]),
+        "split": np.logical_and.reduce([sp for _, sp in ops]),
+        # the backward sweep's rec[SW_RQ]: st[tid + j SW_NT], j < SW_RQ, covers xhat | rstd | acts | g
+        "record": _R * (K0 + 1 + n_act + D) <= _RQ * _NT,
+        # dynamic + the kernel's __shared__ arrays within a CU's LDS
+        "lds": dyn + C.SW_STATIC_LDS <= C.CU_LDS_BYTES,
+    }, dyn
+
+
+def _parent_sw_admits(lims, dyn):
+    """sw_fits and em_create's test before this check: op units, the record, and
+    ``sl * 4 <= 160 * 1024`` on the dynamic LDS alone."""
+    return lims["units"] & lims["record"] & (dyn <= 160 * 1024)
+
+
+def _grid():
+    for A in _GRID_ACT:
+        for n in (1, 2, 3):
+            for hid in itertools.product(_GRID_W, repeat=n):
+                yield A, hid, (), 0.0
+                for tph in _GRID_TP:
+                    yield A, hid, tph, 1.0
+
+
+def test_sweep_admission_implies_the_kernels_capacity():
+    admitted, parent_bad, top = 0, {}, {"nin": 0, "record": 0, "lds": 0}
+    for A, hid, tph, tw in _grid():
+        plan = C.em_plan_dims(_GRID_OBS, A, hid, tph or (16,), "multistep", tw, 4, 16)
+        ok = plan["lds"] <= C.LDS_BUDGET          # em_create accepts the shape at all
+        # the fallback: the fused step's LDS beside em_seq_grad_kernel's static arrays (the same ones)
+        assert (plan["lds"][ok] + C.SW_STATIC_LDS <= C.CU_LDS_BYTES).all()
+        adm = plan["sweep"] & ok
+        lims, dyn = _kernel_limits(A, hid, tph, tw)
+        assert (dyn == plan["sweep_need"]).all(), (A, hid, tph, tw)
+        for name, within in lims.items():
+            assert within[adm].all(), (name, A, hid, tph, tw, _GRID_OBS[adm & ~within])
+        admitted += int(adm.sum())
+        for k, v in (("nin", plan["nin"]), ("record", plan["record"]), ("lds", dyn + C.SW_STATIC_LDS)):
+            top[k] = max(top[k], int(v[adm].max()) if adm.any() else 0)
+        padm = _parent_sw_admits(lims, dyn) & ok
+        for name, within in lims.items():
+            parent_bad[name] = parent_bad.get(name, 0) + int((padm & ~within).sum())
+    print("admitted", admitted, "largest admitted", top, "parent admits beyond a limit", parent_bad)
+    # not vacuous: the grid reaches the stage's and the record's limit exactly, and the LDS window
+    assert admitted > 10000 and top["nin"] == _NT and top["record"] == _RQ * _NT
+    assert C.CU_LDS_BYTES - C.SW_STATIC_LDS < top["lds"] <= C.CU_LDS_BYTES
+    # red before green: the parent's rule admits shapes past the stage and past the LDS
+    assert parent_bad["stage"] > 0 and parent_bad["lds"] > 0 and not (parent_bad["units"] or parent_bad["record"])
+
+
+@pytest.mark.parametrize("shape,tw,limit", [("G", 0.0, "stage"), ("G", 1.0, "stage"), ("H", 1.0, "stage"),
+                                            ("K", 1.0, "lds")])
+def test_parent_rule_admitted_shapes_the_kernel_cannot_run(shape, tw, limit):
+    D, A, hid, tph = C.SHAPES[shape]
+    i = D - 1
+    lims, dyn = _kernel_limits(A, hid, tph, tw)
+    assert _parent_sw_admits(lims, dyn)[i] and not lims[limit][i]
+    assert all(within[i] for name, within in lims.items() if name != limit)
+    assert not C.em_plan(shape, "multistep", tw, 2, 16)["sweep"]

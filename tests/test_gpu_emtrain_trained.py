@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import _emtrain_cases as C
+import envmodel as em
 import initobs_np as V
 from _helpers import EmOptimiserChecker, em_leaf_table, em_logs_ratio, engine_options
 from envmodel import initial_observation as io
@@ -110,6 +111,10 @@ def test_multistep_from_trained_state(shape, T_, B, option, sweep, tchunks, tw):
     """em_sweep_kernel + em_seq_dw_kernel (em_seq_sweep = 1), the round-5 em_seq_grad_kernel
     (= 0) and the automatic fallback (shape C, default option), each asserted through ``plan``:
     empty and uneven k-split chunks, odd T, odd T-chunk lengths, a ragged 64-tile."""
+    _multistep_case(shape, T_, B, option, sweep, tchunks, tw)
+
+
+def _multistep_case(shape, T_, B, option, sweep, tchunks, tw):
     ctx = engine_options(em_seq_sweep=option) if option is not None else contextlib.nullcontext()
     with ctx:
         tr, tp64 = _trainer("multistep", shape, tw, B, 2 * W_MULTI, T_)
@@ -118,6 +123,35 @@ def test_multistep_from_trained_state(shape, T_, B, option, sweep, tchunks, tw):
     acc = _checked_steps(tr, "multistep", shape, tw, tp64, B, T_, 2 * W_MULTI, (0.25, 0.25),
                          np.random.default_rng(6))
     _report(f"multistep-tw{tw:g}-{shape}-T{T_}-B{B}-sweep{int(sweep)}", acc)
+    tr.close()
+
+
+@pytest.mark.parametrize("shape,T_,B,option,sweep,tchunks,tw",
+                         [(*c[:6], tw) for c in C.MULTISTEP_EDGE_CASES for tw in c[6]], ids=lambda v: str(v))
+def test_multistep_at_the_edges_of_the_sweep_plan(shape, T_, B, option, sweep, tchunks, tw):
+    """The shapes at and one past every limit of the sweep's admission rule (sw_fits, em_create),
+    through test_multistep_from_trained_state's checks: a step's inputs at one value per thread
+    with the rewards in the last 16 threads (F) and past that (G, H); its record at SW_RQ floats
+    per thread (I, L: under the default frozen predictor) and past that (J); the dynamic LDS that
+    fits only without the kernel's static arrays (K); T = 1, no step ahead to load and no carried
+    gradient (A).  The rows past an edge run the default option and must fall back by themselves."""
+    assert sweep == (C.em_plan(shape, "multistep", tw, T_, B)["sweep"] and option != 0)
+    _multistep_case(shape, T_, B, option, sweep, tchunks, tw)
+
+
+@pytest.mark.parametrize("D,A,hid,tph,tw,sweep", C.PLAN_PROBES, ids=lambda v: str(v).replace(" ", ""))
+def test_plan_matches_its_cpu_restatement(D, A, hid, tph, tw, sweep):
+    """fqlpop_emtrain_create's choice against em_plan either side of every limit (trainers created
+    and closed, no step): tests/test_emtrain_cpu.py proves on em_plan that no admitted shape
+    exceeds a limit of the sweep kernel."""
+    spec = em.EnvModelSpec(D, A, hid, tph)
+    cfg = EnvModelTrainerConfig(steps=10, model="multistep", sequence_length=2, termination_weight=tw,
+                                batch_size=16, init_learning_rate=C.LR)
+    tr = StatePredictorTrainer(spec, em.init_state_predictor(spec, 0), None, None, cfg,
+                               tp_params=em.init_termination_predictor(spec, 1) if tw > 0 else None)
+    want = C.em_plan_dims(D, A, hid, tph, "multistep", tw, 2, 16)
+    assert want["sweep"] == sweep
+    assert tr.plan == {k: want[k] for k in ("sweep", "tchunks", "blocks")}
     tr.close()
 
 
@@ -168,6 +202,28 @@ def test_ensemble_models_from_trained_states(xcd):
     acc = _checked_steps(tr, "state", shape, 1.0, C.f64(tp), B, 1, 2 * W_SINGLE, (0.25, 0.25),
                          np.random.default_rng(9), others=K)
     _report(f"ensemble-{shape}-K{K}-xcd{xcd}", acc)
+    tr.close()
+
+
+def test_ensemble_sweep_at_the_full_staging_width():
+    """ens_enter shares em_sweep_kernel: both models of a K = 2 multistep ensemble at shape F,
+    where every one of the 1024 threads stages one input value."""
+    shape, T_, B, K = C.ENSEMBLE_SWEEP_CASE
+    spec = C.spec_of(shape)
+    D, A = spec.obs_dim, spec.action_dim
+    trees = [C.random_bias_params(shape, 20 + k) for k in range(K)]
+    tp = trees[0][1]
+    cfg = EnvModelTrainerConfig(steps=2 * W_MULTI, model="multistep", sequence_length=T_, termination_weight=1.0,
+                                batch_size=B, init_learning_rate=C.LR)
+    tr = StatePredictorEnsembleTrainer(spec, [t[0] for t in trees], _Loader(_trajectory_dataset(2, D, A, seed=4)),
+                                       None, cfg, seeds=[7, 8], tp_params=tp)
+    assert tr.plan == {"sweep": True, "tchunks": 1, "blocks": B // 16}
+    tr.steps(W_MULTI)
+    for which in (0, 1, 2):
+        assert not np.array_equal(tr.flat(0, which), tr.flat(1, which))
+    acc = _checked_steps(tr, "multistep", shape, 1.0, C.f64(tp), B, T_, 2 * W_MULTI, (0.25, 0.25),
+                         np.random.default_rng(9), others=K)
+    _report(f"ensemble-multistep-{shape}-T{T_}-K{K}", acc)
     tr.close()
 
 
