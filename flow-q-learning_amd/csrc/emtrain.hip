@@ -33,6 +33,7 @@
 
 #include "../../include/fqlpop.h"
 #include "emboot.h"
+#include "emlayout.h"
 #include "hostmem.h"
 #include "kernels.h"
 
@@ -41,17 +42,7 @@
 namespace fq {
 namespace em {
 
-constexpr int R = 16;      // minibatch rows per block
-constexpr int NT = 512;    // threads per block
-constexpr int MAXL = 8;    // Dense layers per net
-constexpr int NLOG = 16;   // per-block log sums
-
-struct Net {
-    int n;                              // Dense layers (hidden + output)
-    int dims[MAXL + 1];                 // dims[0] = input, dims[n] = output
-    long long w[MAXL], b[MAXL];         // flat offsets (flax leaf order)
-    long long ln_scale, ln_bias;        // state predictor LayerNorm_0 (-1: none)
-};
+// (R, NT, the sweep's constants, struct Net and every LDS / record layout: emlayout.h)
 
 // The model axis of an ensemble launch (fqlpop_emtrain_create_ensemble): K models that share
 // the dataset, the frozen termination predictor, the config and the update count, each with
@@ -362,6 +353,22 @@ DEV void sq_err_rows(const float* out, const float* x0, const float* nobs, int D
     if (g == 0) lsum0[r] += s;
 }
 
+// The state predictor's loss on out [D][R]: pred = out + obs (x0 rows k < D are the
+// observations), kept when keep_pred (the frozen termination predictor's input, the next step's
+// observation); gA = d MSE / d pred scaled by gscale; squared errors into lsum0; a barrier.
+template <int NTHREADS>
+DEV void pred_loss(const float* out, const float* x0, const float* nobs, float* pred, bool keep_pred, float* gA, int D,
+                   float gscale, float* lsum0, int tid) {
+    for (int q = tid; q < D * R; q += NTHREADS) {
+        const float p = out[q] + x0[q];
+        const float d = p - nobs[q];
+        if (keep_pred) pred[q] = p;
+        gA[q] = gscale * d;
+    }
+    sq_err_rows<NTHREADS>(out, x0, nobs, D, lsum0);
+    __syncthreads();
+}
+
 // A block's model: the per-model pointers and seed of StepArgs moved to the block's model, and
 // the block's index within it.  Derived once at kernel entry; the model index and every offset
 // are wave-uniform (blockIdx and kernel arguments only; readfirstlane pins the quotients of
@@ -433,6 +440,29 @@ DEV long long em_unit(const StepArgs& a, const ModelView& m, int gr, uint32_t sa
     return m.tab[v % (uint64_t)n];
 }
 
+// First dataset row of batch position gr's sequence: injected [B][T] rows, or a MultistepLoader
+// window of T steps inside a Philox-drawn episode
+DEV long long em_window(const StepArgs& a, const ModelView& mv, int gr) {
+    if (a.injected) return (long long)gr * a.T;
+    uint32_t c2;
+    const long long ep = em_unit(a, mv, gr, SALT_EP, a.n_rows / a.ep_len, &c2);
+    const long long st = (long long)(c2 % (uint32_t)(a.ep_len - a.T));
+    return ep * a.ep_len + st;
+}
+
+// flax LayerNorm statistics of row r of x0 [K0][R] (eps 1e-6, E[x^2] - mu^2 clipped)
+DEV void ln_stats(const float* x0, int K0, int r, float* mu_s, float* rs_s) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = 0; k < K0; ++k) {
+        const float v = x0[k * R + r];
+        s1 += v;
+        s2 += v * v;
+    }
+    const float mu = s1 / K0;
+    mu_s[r] = mu;
+    rs_s[r] = 1.0f / sqrtf(fmaxf(s2 / K0 - mu * mu, 0.f) + 1e-6f);
+}
+
 __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float lsum[NLOG][R];
@@ -444,23 +474,17 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     const Net& N = a.net;
     const int D = a.D, A = a.A;
     const int K0 = N.dims[0];
-    // LDS: x0 [K0][R] | xhat [K0][R] | acts[i] [dims[i]][R] i = 0..n (acts[n] = output) |
-    //      gA, gB, gC [maxd][R] | nobs [D][R] | tp acts [dims][R]
-    int maxd = 0;
-    for (int i = 0; i <= N.n; ++i) maxd = max(maxd, N.dims[i]);
-    for (int i = 0; i <= a.tpn.n; ++i) maxd = max(maxd, a.tpn.dims[i]);
-    float* x0 = lds;
-    float* xhat = x0 + K0 * R;
+    const EmLds L = em_lds(N, a.tpn, D, false, false);
+    float* x0 = lds + L.x0;
+    float* xhat = lds + L.xhat;
     float* acts[MAXL + 1];
-    acts[0] = xhat + K0 * R;
-    for (int i = 1; i <= N.n; ++i) acts[i] = acts[i - 1] + N.dims[i - 1] * R;
-    float* gA = acts[N.n] + N.dims[N.n] * R;
-    float* gB = gA + maxd * R;
-    float* gC = gB + maxd * R;
-    float* nobs = gC + maxd * R;
     float* tacts[MAXL + 1];
-    tacts[0] = nobs + D * R;
-    for (int i = 1; i <= a.tpn.n; ++i) tacts[i] = tacts[i - 1] + a.tpn.dims[i - 1] * R;
+    for (int i = 0; i <= N.n; ++i) acts[i] = lds + em_acts(L, N, i);
+    for (int i = 0; i <= a.tpn.n; ++i) tacts[i] = lds + em_tacts(L, a.tpn, i);
+    float* gA = lds + L.gA;
+    float* gB = lds + L.gB;
+    float* gC = lds + L.gC;
+    float* nobs = lds + L.nobs;
 
     // ---- rows: injected batch rows, or Philox-drawn dataset rows ([EXT] Dataset.sample)
     if (tid < R) {
@@ -504,19 +528,9 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
     // ---- forward
     const float* P = mv.params;
     if (N.ln_scale >= 0) {
-        // flax LayerNorm over the K0 input features of each row (eps 1e-6, E[x^2] - mu^2 clipped)
+        // flax LayerNorm over the K0 input features of each row
         __shared__ float mu_s[R], rs_s[R];
-        if (tid < R) {
-            float s1 = 0.f, s2 = 0.f;
-            for (int k = 0; k < K0; ++k) {
-                const float v = x0[k * R + tid];
-                s1 += v;
-                s2 += v * v;
-            }
-            const float mu = s1 / K0;
-            mu_s[tid] = mu;
-            rs_s[tid] = 1.0f / sqrtf(fmaxf(s2 / K0 - mu * mu, 0.f) + 1e-6f);
-        }
+        if (tid < R) ln_stats(x0, K0, tid, mu_s, rs_s);
         __syncthreads();
         for (int t = tid; t < K0 * R; t += NT) {
             const int k = t / R, r = t % R;
@@ -538,15 +552,8 @@ __global__ __launch_bounds__(NT) void em_grad_kernel(const StepArgs a) {
         // pred = out + obs; MSE(pred, next) over B x D; grads / (1 + tw)
         const float norm = 1.0f + a.tw;
         const float gscale = 2.0f / ((float)a.B * D) / norm;
-        float* pred = lds_ptr(tacts[0]);  // pred [D][R]: the frozen termination predictor's input
-        for (int t = tid; t < D * R; t += NT) {
-            const float p = out[t] + x0[t];  // x0 rows k < D are the observations
-            const float d = p - nobs[t];
-            pred[t] = p;
-            gA[t] = gscale * d;
-        }
-        sq_err_rows<NT>(out, x0, nobs, D, lsum[0]);
-        __syncthreads();
+        // (without a frozen termination predictor a single step has no pred buffer: em_lds)
+        pred_loss<NT>(out, x0, nobs, lds_ptr(tacts[0]), a.tpn.n > 0, gA, D, gscale, lsum[0], tid);
         if (a.tw > 0.f) tp_score(a, tacts, gA, gB, gC, lab, lsum, invB, norm);
     } else {
         // focal loss (alpha, gamma) on the logit
@@ -625,42 +632,30 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
     __shared__ float lab[R];
     __shared__ long long rowbase[R];
     __shared__ float mu_s[R], rs_s[R], cs[2][R];
+    static_assert(sizeof(lsum) + sizeof(lab) + sizeof(rowbase) + sizeof(mu_s) + sizeof(rs_s) + sizeof(cs) + SW_PH_LDS ==
+                      SW_STATIC_LDS, "em_seq_grad_kernel's __shared__ arrays are em_sweep_kernel's (SW_STATIC_LDS)");
     ModelView mv;
     if (!ens_enter(a, mv)) return;
     const int tid = threadIdx.x, blk = mv.blk;
     const Net& N = a.net;
     const int D = a.D, A = a.A, T = a.T;
     const int K0 = N.dims[0];
-    int maxd = 0;
-    for (int i = 0; i <= N.n; ++i) maxd = max(maxd, N.dims[i]);
-    for (int i = 0; i <= a.tpn.n; ++i) maxd = max(maxd, a.tpn.dims[i]);
-    // LDS as em_grad_kernel, + carry [D][R] (the gradient w.r.t. the carried observation)
-    float* x0 = lds;
-    float* xhat = x0 + K0 * R;
+    const EmLds L = em_lds(N, a.tpn, D, true, false);  // carry: the gradient w.r.t. the carried observation
+    const EmRec rc = em_rec(N, D, false);
+    float* x0 = lds + L.x0;
+    float* xhat = lds + L.xhat;
     float* acts[MAXL + 1];
-    acts[0] = xhat + K0 * R;
-    for (int i = 1; i <= N.n; ++i) acts[i] = acts[i - 1] + N.dims[i - 1] * R;
-    float* gA = acts[N.n] + N.dims[N.n] * R;
-    float* gB = gA + maxd * R;
-    float* gC = gB + maxd * R;
-    float* nobs = gC + maxd * R;
     float* tacts[MAXL + 1];
-    tacts[0] = nobs + D * R;
-    for (int i = 1; i <= a.tpn.n; ++i) tacts[i] = tacts[i - 1] + a.tpn.dims[i - 1] * R;
-    float* carry = tacts[a.tpn.n > 0 ? a.tpn.n : 0] + (a.tpn.n > 0 ? a.tpn.dims[a.tpn.n] * R : D * R);
+    for (int i = 0; i <= N.n; ++i) acts[i] = lds + em_acts(L, N, i);
+    for (int i = 0; i <= a.tpn.n; ++i) tacts[i] = lds + em_tacts(L, a.tpn, i);
+    float* gA = lds + L.gA;
+    float* gB = lds + L.gB;
+    float* gC = lds + L.gC;
+    float* nobs = lds + L.nobs;
+    float* carry = lds + L.carry;
 
     // ---- sequences: injected [B][T] rows, or MultistepLoader windows drawn by Philox
-    if (tid < R) {
-        const int gr = blk * R + tid;
-        long long base = (long long)gr * T;
-        if (!a.injected) {
-            uint32_t c2;
-            const long long ep = em_unit(a, mv, gr, SALT_EP, a.n_rows / a.ep_len, &c2);
-            const long long st = (long long)(c2 % (uint32_t)(a.ep_len - T));
-            base = ep * a.ep_len + st;
-        }
-        rowbase[tid] = base;
-    }
+    if (tid < R) rowbase[tid] = em_window(a, mv, blk * R + tid);
     for (int q = tid; q < NLOG * R; q += NT) lsum[q / R][q % R] = 0.f;
     __syncthreads();
 
@@ -668,10 +663,8 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
     const float norm = 1.0f + a.tw;
     const float inv_n = 1.0f / ((float)a.B * (float)T);
     const float gscale = 2.0f / ((float)a.B * (float)T * D) / norm;
-    float* const sq = mv.seq + (long long)blk * T * a.seq_stride;  // this block's store
-    // store layout per step: xhat [K0][R] | rstd [R] | acts[0..n-1] | direct output grad [D][R]
-    int act_floats = 0;
-    for (int i = 0; i < N.n; ++i) act_floats += N.dims[i] * R;
+    float* const sq = mv.seq + (long long)blk * T * a.seq_stride;  // this block's store (records: em_rec)
+    const int act_floats = rc.own - rc.acts0;
 
     // ---- forward through the sequence
     for (int t = 0; t < T; ++t) {
@@ -687,17 +680,7 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
         }
         if (tid < R) lab[tid] = mv.rew[rowbase[tid] + t] == 0.f ? 1.f : 0.f;
         __syncthreads();
-        if (tid < R) {
-            float s1 = 0.f, s2 = 0.f;
-            for (int k = 0; k < K0; ++k) {
-                const float v = x0[k * R + tid];
-                s1 += v;
-                s2 += v * v;
-            }
-            const float mu = s1 / K0;
-            mu_s[tid] = mu;
-            rs_s[tid] = 1.0f / sqrtf(fmaxf(s2 / K0 - mu * mu, 0.f) + 1e-6f);
-        }
+        if (tid < R) ln_stats(x0, K0, tid, mu_s, rs_s);
         __syncthreads();
         for (int q = tid; q < K0 * R; q += NT) {
             const int k = q / R, r = q % R;
@@ -710,22 +693,15 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
             dense_fwd<EM_SEQ_KS>(P + N.w[i], P + N.b[i], acts[i], N.dims[i], N.dims[i + 1], acts[i + 1], i < N.n - 1);
         const float* out = lds_ptr(acts[N.n]);
         float* pred = lds_ptr(tacts[0]);
-        for (int q = tid; q < D * R; q += NT) {
-            const float p = out[q] + x0[q];
-            const float d = p - nobs[q];
-            pred[q] = p;
-            gA[q] = gscale * d;
-        }
-        sq_err_rows<NT>(out, x0, nobs, D, lsum[0]);
-        __syncthreads();
+        pred_loss<NT>(out, x0, nobs, pred, true, gA, D, gscale, lsum[0], tid);
         if (a.tw > 0.f) tp_score<EM_SEQ_KS>(a, tacts, gA, gB, gC, lab, lsum, inv_n, norm);
         if (a.train) {
             float* st = sq + (long long)t * a.seq_stride;
-            for (int q = tid; q < K0 * R; q += NT) st[q] = xhat[q];
-            if (tid < R) st[K0 * R + tid] = rs_s[tid];
-            float* sa = st + K0 * R + R;
+            for (int q = tid; q < K0 * R; q += NT) st[rc.xhat + q] = xhat[q];
+            if (tid < R) st[rc.rstd + tid] = rs_s[tid];
+            float* sa = st + rc.acts0;
             for (int q = tid; q < act_floats; q += NT) sa[q] = lds_ptr(acts[0])[q];  // acts[0..n-1] are contiguous
-            float* sg = sa + act_floats;
+            float* sg = st + rc.own;
             for (int q = tid; q < D * R; q += NT) sg[q] = gA[q];
         }
         for (int q = tid; q < D * R; q += NT) x0[q] = pred[q];  // the next step's observation
@@ -747,7 +723,7 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
             // the step's record (xhat | rstd | acts[0..n-1]) in batches of 8 loads per thread,
             // all in flight before their LDS stores (one HBM round trip per element otherwise)
             constexpr int BQ = 8;
-            const int n1 = K0 * R, n2 = n1 + R, n3 = n2 + act_floats;
+            const int n1 = rc.rstd, n2 = rc.acts0, n3 = rc.own;
             float* const a0 = lds_ptr(acts[0]);
             for (int q0 = tid; q0 < n3; q0 += BQ * NT) {
                 float v[BQ];
@@ -762,7 +738,7 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
                 }
             }
         }
-        const float* sg = st + K0 * R + R + act_floats;
+        const float* sg = st + rc.own;
         // total gradient w.r.t. this step's prediction: its own loss terms + the next step's
         for (int q = tid; q < D * R; q += NT) {
             const float gv = sg[q] + (acc ? carry[q] : 0.f);
@@ -828,34 +804,18 @@ __global__ __launch_bounds__(NT) void em_seq_grad_kernel(const StepArgs a) {
 //   * em_seq_dw_kernel: dW_i = sum over the (t, row) pairs of acts_i g_i^T and db_i, one GEMM
 //     per (block, T chunk, 64 x 64 tile) over the stored records, into the per-chunk partials
 //     that em_adam_kernel folds in a fixed order.
-// Taken when every op fits one unit per wave (fqlpop_emtrain_create: sw_fits); otherwise, and
-// under engine option em_seq_sweep = 0, em_seq_grad_kernel runs.
-constexpr int SW_NT = 1024, SW_NW = SW_NT / 64, SW_FM = 32, SW_SCR = SW_NW * 16 * R;
-constexpr int SW_RQ = 10;    // a step's record, loaded a step ahead: <= SW_RQ floats per thread
+// Taken when the plan admits the shape (emlayout.h: sw_fits); otherwise, and under engine option
+// em_seq_sweep = 0, em_seq_grad_kernel runs.
 // diagnostic phase slots (FQ_DIAG, FQLPOP_EM_PROBE): 0 inputs, 26 LayerNorm statistics, 1
 // normalise, 2-5 forward ops, 6-13 termination-predictor ops, 27 record stores, 14 next
 // observation; backward: 28 record to LDS, 29 next record's loads, 15 barrier, 16 carry,
 // 17-20 dX ops, 30 LayerNorm backward sums, 25 carry update
-constexpr int EM_PH_N = 32;
 
 struct SwOp {
     const float* A;  // k-major [Kc][No] (No contiguous): W for a forward op, W^T for a dX op
     int Kc, No;      // contracted rows, outputs
 };
-// units of an op: ntile output tiles x S k-chunks of cks k-steps (4 rows each), at most one per wave
-DEV void sw_plan(int Kc, int No, int& ntile, int& S, int& cks) {
-    ntile = (No + 15) >> 4;
-    const int nks = (Kc + 3) >> 2;
-    S = 1;
-    while (S < SW_NW && ntile * S * 2 <= SW_NW && S * 2 <= nks) S *= 2;
-    cks = (nks + S - 1) / S;
-}
-bool sw_op_fits(int Kc, int No) {
-    const int ntile = (No + 15) >> 4, nks = (Kc + 3) >> 2;
-    int S = 1;
-    while (S < SW_NW && ntile * S * 2 <= SW_NW && S * 2 <= nks) S *= 2;
-    return ntile * S <= SW_NW && (nks + S - 1) / S <= SW_FM;
-}
+// (the units of an op: sw_plan, emlayout.h)
 // the wave's A fragments of op o: fr[j] = A[4 (ch cks + j) + lk][16 tile + li] (unguarded buffer
 // loads: rows >= Kc read 0, a lane's column >= No feeds only its own discarded output row)
 // wave-uniform values through readfirstlane: an op descriptor picked by run-time branches is
@@ -1021,20 +981,10 @@ DEV int opaque_tid() {
     return v;
 }
 
-// em_sweep_kernel's static LDS: the __shared__ arrays it declares below (the diagnostic build's
-// ph too), which the CU's LDS holds beside the dynamic part (fqlpop_emtrain_create: sw_fits)
-#ifdef FQ_DIAG
-constexpr int SW_PH_LDS = (int)sizeof(unsigned long long[EM_PH_N]);
-#else
-constexpr int SW_PH_LDS = 0;
-#endif
-constexpr int SW_STATIC_LDS = (int)(sizeof(float[NLOG][R]) + sizeof(float[R]) + sizeof(long long[R]) +
-                                    2 * sizeof(float[R]) + sizeof(float[2][R])) + SW_PH_LDS;
-constexpr int CU_LDS_BYTES = 160 * 1024;
-
-// record of one (block, step) in a.seq: xhat [K0][R] | rstd [R] | acts[0..n-1] | the step's own
-// output gradient [D][R] | (sweep path) g_i [dims[i + 1]][R], i = 0..n-1 (each layer's output
-// gradient after the ReLU mask: the dW operands)
+// LDS: em_lds, with SW_STATIC_LDS pinned to the __shared__ arrays below; records: em_rec.  Two
+// forms are kept for speed (profiles/emlayout/sweep_variants.txt): layer buffers step an LDS
+// pointer through em_layer (an offset added to the base at every use: + 1.2 %), and the backward
+// walks g(n-1) .. g(0) with a running pointer from rec.g0 (em_rec_g per op: + 1.5 %).
 __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float lsum[NLOG][R];
@@ -1064,50 +1014,29 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
 #endif
     const Net& N = a.net;
     const Net& TP = a.tpn;
-    const int D = a.D, A = a.A, T = a.T, n = N.n, m = a.tw > 0.f ? TP.n : 0;
+    const int D = a.D, A = a.A, T = a.T, n = N.n, m = TP.n;  // (m == 0 when tw == 0: em_lds)
     const int K0 = N.dims[0];
-    int maxd = 0;
-    for (int i = 0; i <= n; ++i) maxd = max(maxd, N.dims[i]);
-    for (int i = 0; i <= m; ++i) maxd = max(maxd, TP.dims[i]);
-    // LDS: x0, xhat [K0][R] | acts[0..n] | gA, gB, gC [maxd][R] | nobs [D][R] | tp acts (or pred
-    // [D][R]) | carry [D][R] | scr [SW_SCR] | ln grad sums [2][K0]
-    float* x0 = lds;
-    float* xhat = x0 + K0 * R;
-    // (layer buffers by computed offset: a runtime-indexed array of LDS pointers went to scratch)
-    float* const acts0 = xhat + K0 * R;
-    auto acts = [&](int i) {
-        float* p = acts0;
-        for (int j = 0; j < i; ++j) p += N.dims[j] * R;
-        return lds_ptr(p);
-    };
-    float* gA = acts(n) + N.dims[n] * R;
-    float* gB = gA + maxd * R;
-    float* gC = gB + maxd * R;
-    float* nobs = gC + maxd * R;
-    float* const tacts0 = nobs + D * R;
-    auto tacts = [&](int i) {
-        float* p = tacts0;
-        for (int j = 0; j < i; ++j) p += TP.dims[j] * R;
-        return lds_ptr(p);
-    };
-    float* carry = tacts(m) + (m > 0 ? TP.dims[m] * R : D * R);
-    float* scr = carry + D * R;
-    float* lnacc = scr + SW_SCR;   // [2][K0] LayerNorm grad sums over t
-    float* lnp = lnacc + 2 * K0;   // [2][K0] LayerNorm scale, bias (no global load inside the sweeps)
+    const EmLds L = em_lds(N, TP, D, true, true);
+    const EmRec rc = em_rec(N, D, true);
+    float* x0 = lds + L.x0;
+    float* xhat = lds + L.xhat;
+    // (layer buffers by summed widths: a runtime-indexed array of LDS pointers went to scratch)
+    float* const acts0 = lds + L.acts0;
+    float* const tacts0 = lds + L.tacts0;
+    auto acts = [&](int i) { return lds_ptr(em_layer(acts0, N, i)); };
+    auto tacts = [&](int i) { return lds_ptr(em_layer(tacts0, TP, i)); };
+    float* gA = lds + L.gA;
+    float* gB = lds + L.gB;
+    float* gC = lds + L.gC;
+    float* nobs = lds + L.nobs;
+    float* carry = lds + L.carry;
+    float* scr = lds + L.scr;
+    float* lnacc = lds + L.lnacc;  // [2][K0] LayerNorm grad sums over t
+    float* lnp = lds + L.lnp;      // [2][K0] LayerNorm scale, bias (no global load inside the sweeps)
 
-    if (tid < R) {
-        const int gr = blk * R + tid;
-        long long base = (long long)gr * T;
-        if (!a.injected) {  // MultistepLoader windows, as em_seq_grad_kernel
-            uint32_t c2;
-            const long long ep = em_unit(a, mv, gr, SALT_EP, a.n_rows / a.ep_len, &c2);
-            const long long st = (long long)(c2 % (uint32_t)(a.ep_len - T));
-            base = ep * a.ep_len + st;
-        }
-        rowbase[tid] = base;
-    }
+    if (tid < R) rowbase[tid] = em_window(a, mv, blk * R + tid);
     // every LDS float finite before the first op: a chain reads x past its operand (times zeros)
-    for (int q = tid; q < (int)(lnp - lds); q += SW_NT) lds[q] = 0.f;
+    for (int q = tid; q < L.lnp; q += SW_NT) lds[q] = 0.f;
     for (int q = tid; q < NLOG * R; q += SW_NT) lsum[q / R][q % R] = 0.f;
     for (int q = tid; q < 2 * K0; q += SW_NT) {
         lnacc[q] = 0.f;
@@ -1120,9 +1049,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     const float inv_n = 1.0f / ((float)a.B * (float)T);
     const float gscale = 2.0f / ((float)a.B * (float)T * D) / norm;
     float* const sq = mv.seq + (long long)blk * T * a.seq_stride;
-    int act_floats = 0;
-    for (int i = 0; i < n; ++i) act_floats += N.dims[i] * R;
-    const int off_g0 = K0 * R + R + act_floats + D * R;  // g_i from here (g_{n-1} first)
+    const int act_floats = rc.own - rc.acts0;
 
     // ---- the forward sweep's op program: n layers, then (tw > 0) the frozen termination
     // predictor's m layers and its m dX ops
@@ -1161,17 +1088,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         inx = in_load(t + 1, tid);
         __syncthreads();
         stamp(0);
-        if (tid < R) {
-            float s1 = 0.f, s2 = 0.f;
-            for (int k = 0; k < K0; ++k) {
-                const float v = x0[k * R + tid];
-                s1 += v;
-                s2 += v * v;
-            }
-            const float mu = s1 / K0;
-            mu_s[tid] = mu;
-            rs_s[tid] = 1.0f / sqrtf(fmaxf(s2 / K0 - mu * mu, 0.f) + 1e-6f);
-        }
+        if (tid < R) ln_stats(x0, K0, tid, mu_s, rs_s);
         __syncthreads();
         stamp(26);
         for (int q = tid; q < K0 * R; q += SW_NT) {
@@ -1190,16 +1107,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
                 sw_compute(o, on, fr, P + N.b[j], acts(j), acts(j + 1), j < n - 1 ? 1 : 0, nullptr, scr);
                 if (j == n - 1) {
                     // pred = out + obs; MSE; d loss / d pred (gA); the termination predictor's input
-                    const float* out = acts(n);
-                    float* pred = tacts(0);
-                    for (int q = tid; q < D * R; q += SW_NT) {
-                        const float p = out[q] + x0[q];
-                        const float d = p - nobs[q];
-                        pred[q] = p;
-                        gA[q] = gscale * d;
-                    }
-                    sq_err_rows<SW_NT>(out, x0, nobs, D, lsum[0]);
-                    __syncthreads();
+                    pred_loss<SW_NT>(acts(n), x0, nobs, tacts(0), true, gA, D, gscale, lsum[0], tid);
                 }
             } else if (j < n + m) {
                 const int i = j - n;
@@ -1234,11 +1142,11 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         }
         if (a.train) {
             float* st = sq + (long long)t * a.seq_stride;
-            for (int q = tid; q < K0 * R; q += SW_NT) st[q] = xhat[q];
-            if (tid < R) st[K0 * R + tid] = rs_s[tid];
-            float* sa = st + K0 * R + R;
+            for (int q = tid; q < K0 * R; q += SW_NT) st[rc.xhat + q] = xhat[q];
+            if (tid < R) st[rc.rstd + tid] = rs_s[tid];
+            float* sa = st + rc.acts0;
             for (int q = tid; q < act_floats; q += SW_NT) sa[q] = acts0[q];  // acts[0..n-1] contiguous
-            float* sg = sa + act_floats;
+            float* sg = st + rc.own;
             for (int q = tid; q < D * R; q += SW_NT) sg[q] = gA[q];
         }
         stamp(27);
@@ -1267,7 +1175,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
     // the step's record (xhat | rstd | acts[1..n-1] for the masks | own output gradient), a step
     // ahead in registers (RQ per thread), then into LDS at the step's start
     constexpr int RQ = SW_RQ;
-    const int n_rec = K0 * R + R + act_floats + D * R;
+    const int n_rec = rc.g0;
     float rec[RQ];
     auto rec_load = [&](int t, int tid) {
         const float* st = sq + (long long)max(t, 0) * a.seq_stride;
@@ -1280,7 +1188,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         float* st = sq + (long long)t * a.seq_stride;
         {
             float* const a0 = acts0;
-            const int n1 = K0 * R, n2 = n1 + R, n3 = n2 + act_floats;
+            const int n1 = rc.rstd, n2 = rc.acts0, n3 = rc.own;
 #pragma unroll
             for (int j = 0; j < RQ; ++j) {
                 const int q = tid + j * SW_NT;
@@ -1304,7 +1212,7 @@ __global__ __launch_bounds__(SW_NT) void em_sweep_kernel(const StepArgs a) {
         stamp(16);
         float* g = gA;
         float* gn = gB;
-        float* sgi = st + off_g0;
+        float* sgi = st + rc.g0;  // g(n-1) first, then each layer below it: em_rec_g
         for (int j = 0; j < n; ++j) {
             const int i = n - 1 - j;
             for (int q = tid; q < N.dims[i + 1] * R; q += SW_NT) sgi[q] = lds_ptr(g)[q];  // g_i for dW
@@ -1370,7 +1278,7 @@ struct SeqDwArgs {
     float* part;
     long long P;
     Net net;
-    int T, tchunks, K0, D;
+    int T, tchunks, D;
     int first[MAXL + 1];  // prefix of per-layer tile counts
     long long ens_seq, ens_part;  // floats between two models' record stores / partial sets
 };
@@ -1388,12 +1296,8 @@ __global__ __launch_bounds__(256) void em_seq_dw_kernel(const SeqDwArgs a) {
     const int tf = (Nn + 63) / 64, lt = tl - a.first[i];
     const int k0 = 64 * (lt / tf), f0 = 64 * (lt % tf);
     // offsets of acts_i and g_i inside a record
-    int oa = a.K0 * R + R, og = 0;
-    for (int j = 0; j < i; ++j) oa += a.net.dims[j] * R;
-    int act_floats = 0;
-    for (int j = 0; j < a.net.n; ++j) act_floats += a.net.dims[j] * R;
-    og = a.K0 * R + R + act_floats + a.D * R;
-    for (int j = a.net.n - 1; j > i; --j) og += a.net.dims[j + 1] * R;  // g_{n-1} first
+    const EmRec rc = em_rec(a.net, a.D, true);
+    const int oa = em_rec_acts(rc, a.net, i), og = em_rec_g(rc, a.net, i);
     const int t0 = a.T * c / a.tchunks, t1 = a.T * (c + 1) / a.tchunks;
     const float* sq = mseq + (long long)b * a.T * a.seq_stride;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
@@ -1635,32 +1539,6 @@ using namespace fq;
 using namespace fq::em;
 
 namespace {
-// flax leaf order (path-sorted): Dense_i/bias, Dense_i/kernel ..., LayerNorm_0/bias, LayerNorm_0/scale
-Net layout(int in, int nh, const int* hid, int out, bool ln, long long* total) {
-    Net n{};
-    n.n = nh + 1;
-    ARGCHK(n.n <= MAXL, "too many layers");
-    n.dims[0] = in;
-    for (int i = 0; i < nh; ++i) n.dims[i + 1] = hid[i];
-    n.dims[nh + 1] = out;
-    long long o = 0;
-    for (int i = 0; i < n.n; ++i) {
-        n.b[i] = o;
-        o += n.dims[i + 1];
-        n.w[i] = o;
-        o += (long long)n.dims[i] * n.dims[i + 1];
-    }
-    n.ln_scale = n.ln_bias = -1;
-    if (ln) {
-        n.ln_bias = o;
-        o += in;
-        n.ln_scale = o;
-        o += in;
-    }
-    *total = o;
-    return n;
-}
-
 // Flat params with every Dense kernel [in][out] replaced by its transpose [out][in]
 std::vector<float> transposed(const Net& n, const float* p, long long P) {
     std::vector<float> t(p, p + P);
@@ -1710,45 +1588,6 @@ struct fqlpop_emtrain {
     Stream<> s;
 };
 
-static void em_layouts(const fqlpop_emtrain_config* c, Net* net, long long* P, Net* tpn, long long* PT) {
-    ARGCHK(c->obs_dim > 0 && c->action_dim >= 0, "bad obs/action dims");
-    ARGCHK(c->num_hidden >= 0 && c->num_hidden < MAXL, "bad num_hidden");
-    for (int i = 0; i < c->num_hidden; ++i) ARGCHK(c->hidden_dims[i] > 0 && c->hidden_dims[i] <= 1024, "bad hidden dim");
-    if (c->kind == FQLPOP_EM_STATE_PREDICTOR || c->kind == FQLPOP_EM_MULTISTEP) {
-        *net = layout(c->obs_dim + c->action_dim, c->num_hidden, c->hidden_dims, c->obs_dim, true, P);
-        *PT = 0;
-        if (c->termination_weight > 0.f) {
-            ARGCHK(c->tp_num_hidden >= 0 && c->tp_num_hidden < MAXL, "bad tp_num_hidden");
-            *tpn = layout(c->obs_dim, c->tp_num_hidden, c->tp_hidden_dims, 1, false, PT);
-        } else {
-            *tpn = Net{};
-            tpn->ln_scale = tpn->ln_bias = -1;
-        }
-    } else {
-        ARGCHK(c->kind == FQLPOP_EM_TERMINATION,
-              "kind must be FQLPOP_EM_STATE_PREDICTOR, FQLPOP_EM_TERMINATION or FQLPOP_EM_MULTISTEP");
-        *net = layout(c->obs_dim, c->num_hidden, c->hidden_dims, 1, false, P);
-        *tpn = Net{};
-        tpn->ln_scale = tpn->ln_bias = -1;
-        *PT = 0;
-    }
-}
-
-// the sweep path takes every Dense op (both directions, the frozen termination predictor's
-// too) as one unit per wave, a step's record in SW_RQ loads per thread, and a step's inputs
-// (actions, next observations, rewards: in_load) as one value per thread
-static bool sw_fits(const Net& n, const Net& tpn, bool tp, int D, int A) {
-    if ((long long)R * (A + D + 1) > SW_NT) return false;
-    for (int i = 0; i < n.n; ++i)
-        if (!sw_op_fits(n.dims[i], n.dims[i + 1]) || !sw_op_fits(n.dims[i + 1], n.dims[i])) return false;
-    if (tp)
-        for (int i = 0; i < tpn.n; ++i)
-            if (!sw_op_fits(tpn.dims[i], tpn.dims[i + 1]) || !sw_op_fits(tpn.dims[i + 1], tpn.dims[i])) return false;
-    long long act = 0;
-    for (int i = 0; i < n.n; ++i) act += n.dims[i];
-    return (long long)R * (n.dims[0] + 1 + act + D) <= (long long)SW_RQ * SW_NT;
-}
-
 extern "C" {
 
 int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_params) {
@@ -1756,7 +1595,8 @@ int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_para
         ARGCHK(cfg && n_params, "null argument");
         Net a, b;
         long long P, PT;
-        em_layouts(cfg, &a, &P, &b, &PT);
+        const char* why = em_nets(cfg, &a, &P, &b, &PT);
+        ARGCHK(!why, why);
         *n_params = P;
     });
 }
@@ -1768,8 +1608,7 @@ int fqlpop_emtrain_param_count(const fqlpop_emtrain_config* cfg, int64_t* n_para
 static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* params, int64_t n_params,
                       const uint64_t* seeds, int xcd, int device, fqlpop_emtrain_t** out) {
     {
-        ARGCHK(cfg->batch_size > 0 && cfg->batch_size % R == 0, "batch_size must be a positive multiple of 16");
-        ARGCHK(cfg->steps > 0, "steps must be > 0");
+        const EmPlan plan = em_plan(cfg, fq::engine_option_em_seq_sweep(), n_params, K);
         auto h = std::make_unique<fqlpop_emtrain>();
         h->cfg = *cfg;
         h->device = device;
@@ -1777,35 +1616,13 @@ static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* para
         h->xcd = xcd;
         for (int k = 0; k < K; ++k) h->seeds[k] = seeds[k];
         h->cfg.seed = seeds[0];
-        em_layouts(cfg, &h->net, &h->P, &h->tpn, &h->PT);
-        ARGCHK(n_params == h->P * K, "params size mismatch");
-        // LDS: x0, xhat [K0][R], acts [sum dims][R], gA, gB [maxd][R], nobs [D][R], tp acts
-        int maxd = 0, sum = 0, tsum = 0;
-        for (int i = 0; i <= h->net.n; ++i) { maxd = std::max(maxd, h->net.dims[i]); sum += h->net.dims[i]; }
-        for (int i = 0; i <= h->tpn.n && h->tpn.n > 0; ++i) { maxd = std::max(maxd, h->tpn.dims[i]); tsum += h->tpn.dims[i]; }
+        h->net = plan.net; h->tpn = plan.tpn; h->P = plan.P; h->PT = plan.PT;
+        h->T = plan.T;
+        h->lds_bytes = plan.lds_bytes;
+        h->blocks = plan.blocks;
+        h->sweep = plan.sweep; h->sweep_lds = plan.sweep_lds; h->tchunks = plan.tchunks;
+        h->seq_stride = plan.seq_stride;
         const bool ms = cfg->kind == FQLPOP_EM_MULTISTEP;
-        if (ms) {
-            ARGCHK(cfg->sequence_length >= 1, "sequence_length must be >= 1");
-            ARGCHK(cfg->episode_length > cfg->sequence_length, "episode_length must exceed sequence_length");
-            h->T = cfg->sequence_length;
-        }
-        // multistep: + the carried-gradient buffer, + the prediction buffer when no frozen
-        // termination predictor owns one
-        const long long fl = (long long)R * (2 * h->net.dims[0] + sum + 3 * maxd + cfg->obs_dim + tsum +
-                                             (ms ? cfg->obs_dim * (h->tpn.n > 0 ? 1 : 2) : 0));
-        ARGCHK(fl * 4 <= 150 * 1024, "env-model layer widths exceed the LDS budget of the fused step");
-        h->lds_bytes = (int)(fl * 4);
-        h->blocks = cfg->batch_size / R;
-        if (ms && fq::engine_option_em_seq_sweep() && sw_fits(h->net, h->tpn, h->tpn.n > 0, cfg->obs_dim, cfg->action_dim)) {
-            const long long sl = fl + SW_SCR + 4 * h->net.dims[0];
-            // dynamic + em_sweep_kernel's static LDS within the CU's; otherwise the fallback
-            if (sl * 4 + SW_STATIC_LDS <= CU_LDS_BYTES) {
-                h->sweep = true;
-                h->sweep_lds = (int)(sl * 4);
-                // dW GEMM blocks: 16-step chunks at least, at most 4 chunks per sequence block
-                h->tchunks = std::max(1, std::min(4, h->T / 16));
-            }
-        }
         const long long P = h->P;
         const long long B = cfg->batch_size * (long long)h->T, D = cfg->obs_dim, A = cfg->action_dim;
         // per-model strides (a model's parameter block starts on a 256-byte boundary)
@@ -1816,15 +1633,7 @@ static void em_create(const fqlpop_emtrain_config* cfg, int K, const float* para
         h->s_act = B * A;
         h->s_rew = B;
         h->s_keep = B * D;
-        if (ms) {
-            long long act = 0;
-            for (int i = 0; i < h->net.n; ++i) act += h->net.dims[i];
-            long long gfl = 0;  // sweep: each layer's output gradient g_i (the dW operands)
-            if (h->sweep)
-                for (int i = 0; i < h->net.n; ++i) gfl += h->net.dims[i + 1];
-            h->seq_stride = (long long)R * (h->net.dims[0] + 1 + act + D + gfl);
-            h->s_seq = h->seq_stride * h->T * h->blocks;
-        }
+        h->s_seq = h->seq_stride * h->T * h->blocks;
         HIPCHK(hipSetDevice(device));
         h->s = Stream<>::create();
         const long long PK = h->s_par * K;
@@ -2040,7 +1849,7 @@ static void em_launch_step(fqlpop_emtrain* h, const StepArgs& a) {
         if (a.train) {
             SeqDwArgs d{};
             d.seq = h->seq; d.seq_stride = h->seq_stride; d.part = h->part; d.P = h->P; d.net = h->net;
-            d.T = h->T; d.tchunks = h->tchunks; d.K0 = h->net.dims[0]; d.D = h->cfg.obs_dim;
+            d.T = h->T; d.tchunks = h->tchunks; d.D = h->cfg.obs_dim;
             d.ens_seq = h->s_seq; d.ens_part = h->s_part;
             int tot = 0;
             for (int i = 0; i < h->net.n; ++i) {
@@ -2400,14 +2209,10 @@ int fqlpop_emtrain_eval_oob(fqlpop_emtrain_t* h, int n_batches, uint64_t draw, f
 namespace fq {
 namespace em {
 
-constexpr int VMAXH = 6;   // hidden layers per side
 constexpr int VLOG = 2;    // per-block log sums: squared error, kl terms
 constexpr int VAE_STATIC_LDS = VLOG * R * 4 + R * 8;  // lsum + rowid of em_vae_grad_kernel
 
-struct VaeDense {
-    int K, N, seg;          // in, out, Adam segment
-    long long w, b;         // flat offsets
-};
+// (VMAXH, VaeDense and the two kernels' LDS layouts: emlayout.h)
 struct VaeArgs {
     int train;
     int nh, D, L, B, maxd;
@@ -2453,33 +2258,25 @@ __global__ __launch_bounds__(NT) void em_vae_grad_kernel(const VaeArgs a) {
     __shared__ long long rowid[R];
     const int tid = threadIdx.x, blk = blockIdx.x;
     const int nh = a.nh, D = a.D, L = a.L;
-    // LDS: x [D][R] | encoder hidden e_1..e_nh | mu, logvar, eps, z [L][R] | decoder hidden
-    //      d_1..d_nh | xhat [D][R] | gmu, glv [L][R] | gA, gB [maxd][R]
+    const VaeLds ly = vae_lds(a.enc, a.dec, nh, D, L, a.maxd);
     float* eact[VMAXH + 1];
     float* dact[VMAXH + 1];
-    float* p = lds;
-    eact[0] = p;
-    p += D * R;
-    for (int i = 0; i < nh; ++i) {
-        eact[i + 1] = p;
-        p += a.enc[i].N * R;
-    }
-    float* mu = p;
-    float* lv = mu + L * R;
-    float* eps = lv + L * R;
-    float* z = eps + L * R;
-    p = z + L * R;
+    float* x = lds + ly.x;
+    float* mu = lds + ly.mu;
+    float* lv = lds + ly.lv;
+    float* eps = lds + ly.eps;
+    float* z = lds + ly.z;
+    eact[0] = x;
     dact[0] = z;
-    for (int i = 0; i < nh; ++i) {
-        dact[i + 1] = p;
-        p += a.dec[i].N * R;
+    for (int i = 1; i <= nh; ++i) {
+        eact[i] = lds + vae_hidden(ly.e1, a.enc, i);
+        dact[i] = lds + vae_hidden(ly.d1, a.dec, i);
     }
-    float* xhat = p;
-    float* gmu = xhat + D * R;
-    float* glv = gmu + L * R;
-    float* gA = glv + L * R;
-    float* gB = gA + a.maxd * R;
-    float* x = lds;
+    float* xhat = lds + ly.xhat;
+    float* gmu = lds + ly.gmu;
+    float* glv = lds + ly.glv;
+    float* gA = lds + ly.gA;
+    float* gB = lds + ly.gB;
 
     // ---- rows (injected, or Philox-drawn rows of the initial-observation set) and eps
     if (tid < R) {
@@ -2585,21 +2382,16 @@ __global__ __launch_bounds__(NT) void em_vae_decode_kernel(const VaeDecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nh = a.nh, D = a.D, L = a.L;
     const long long row0 = (long long)blockIdx.x * R;
-    // LDS: z [L][R] | d_1..d_nh | out [D][R]
+    const VaeDecLds ly = vae_dec_lds(a.dec, nh, L);
     float* dact[VMAXH + 2];
-    float* p = lds;
-    dact[0] = p;
-    p += L * R;
-    for (int i = 0; i <= nh; ++i) {
-        dact[i + 1] = p;
-        p += a.dec[i].N * R;
-    }
+    dact[0] = lds + ly.z;
+    for (int i = 1; i <= nh + 1; ++i) dact[i] = lds + vae_hidden(ly.d1, a.dec, i);
     for (int t = tid; t < R * L; t += NT) {
         const int r = t / L, k = t % L;
         const long long row = row0 + r;
         float v = 0.f;
         if (row < a.n) v = a.z ? a.z[row * L + k] : nrand(a.seed, (uint32_t)row, (uint32_t)k, 0u, 0x5A3u);
-        lds[k * R + r] = v;
+        lds[ly.z + k * R + r] = v;
     }
     __syncthreads();
     for (int i = 0; i <= nh; ++i)
@@ -2780,16 +2572,14 @@ int fqlpop_initobs_create(const fqlpop_initobs_config* cfg, const float* params,
         ARGCHK(n_params == h->P, "params size mismatch");
         const VaeArgs& a = h->proto;
         const int nh = a.nh, D = a.D, L = a.L;
-        // dynamic + static LDS of em_vae_grad_kernel (its layout comment), before any GPU call
-        long long sumh = 0;
-        for (int i = 0; i < nh; ++i) sumh += cfg->hidden_dims[i];
-        const long long fl = (long long)R * (2 * D + 2 * sumh + 6 * L + 2 * a.maxd);
+        // dynamic + static LDS of em_vae_grad_kernel, before any GPU call
+        const long long fl = vae_lds(a.enc, a.dec, nh, D, L, a.maxd).total;
         if (fl * 4 + VAE_STATIC_LDS > 160 * 1024)
             throw Err{FQLPOP_E_UNSUPPORTED,
                         "initial-observation VAE: layer widths need " + std::to_string(fl * 4 + VAE_STATIC_LDS) +
                             " bytes of LDS, the fused step has 163840"};
         h->lds_bytes = (int)(fl * 4);
-        h->dec_lds = (int)(4LL * R * (L + sumh + D));
+        h->dec_lds = 4 * vae_dec_lds(a.dec, nh, L).total;
         h->blocks = cfg->batch_size / R;
         {
             const VaeDense* ch[VMAXH + 1];

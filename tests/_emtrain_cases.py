@@ -24,7 +24,7 @@ SHAPES = {
     "C": (69, 20, (144, 272), (272, 144)),      # KS = 32 path; 9 tiles for 8 waves; no sweep plan
     "D": (42, 8, (96, 48), (48,)),              # 96: a ragged 64-tile of the dW GEMM; K0 = 50
     "E": (28, 5, (64,), (64,)),
-    # the edges of the sweep's admission rule (em_plan; csrc/emtrain.hip: sw_fits, em_create)
+    # the edges of the sweep's admission rule (em_plan; csrc/emlayout.h: sw_fits, em_plan)
     "F": (55, 8, (32,), (16,)),                 # a step's inputs (A + D + 1) 16 = 1024: one per thread, rewards last
     "G": (56, 8, (32,), (16,)),                 # 1040 inputs: the rewards would be the values dropped
     "H": (69, 21, (128, 128), (128,)),          # 1456 inputs: humanoid-sized, non-default widths
@@ -61,14 +61,14 @@ PLAN_PROBES = (
     [(D, 8, _W3, _DEEP, 1.0, D <= 15) for D in (15, 16, 17, 18, 19)])
 ENSEMBLE_SWEEP_CASE = ("F", 3, 16, 2)                     # shape, T, batch size, K: a second model's slot
 
-# fqlpop_emtrain_create's constants (csrc/emtrain.hip)
+# fqlpop_emtrain_create's constants (csrc/emlayout.h)
 _R, _SW_NW, _SW_FM, _SW_NT, _SW_RQ = 16, 16, 32, 1024, 10
 _SW_SCR = _SW_NW * 16 * _R
 LDS_BUDGET, SWEEP_LDS_BUDGET = 150 * 1024, 160 * 1024
 CU_LDS_BYTES = 160 * 1024      # a CU's LDS: a block's dynamic and static parts together
 _NLOG = 16
 # em_sweep_kernel's __shared__ arrays (SW_STATIC_LDS): lsum [NLOG][R], lab [R], rowbase [R] (8 bytes
-# each), mu_s, rs_s [R], cs [2][R]; em_seq_grad_kernel declares the same
+# each), mu_s, rs_s [R], cs [2][R]
 SW_STATIC_LDS = 4 * _NLOG * _R + 4 * _R + 8 * _R + 2 * 4 * _R + 4 * 2 * _R
 
 
@@ -131,6 +131,8 @@ def em_plan_dims(D, A: int, hid, tph, kind: str, tw: float, T_: int = 1, B: int 
         sweep = fits & (nin <= _SW_NT) & (record <= _SW_RQ * _SW_NT) & (4 * sl + SW_STATIC_LDS <= CU_LDS_BYTES)
     plan = {"lds": 4 * fl, "sweep": sweep, "sweep_lds": np.where(sweep, 4 * sl, 0),
             "tchunks": np.where(sweep, max(1, min(4, T_ // 16)), 1), "blocks": B // _R,
+            # a record: what the backward loads, and on the sweep path every layer's output gradient
+            "seq_stride": np.where(sweep, record + _R * sum(dims[1:]), record) if ms else 0,
             "nin": nin, "record": record, "sweep_need": 4 * sl if ms else 0}
     if np.ndim(D) == 0:
         plan = {k: v.item() if isinstance(v, (np.ndarray, np.generic)) else v for k, v in plan.items()}

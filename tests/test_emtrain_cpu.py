@@ -1,6 +1,7 @@
 """CPU checks of the env-model trainer oracle (oracle/envmodel_train_oracle.py):
 hand-written gradients vs torch autograd in float64, known answers of the focal
 loss, the cosine schedule and the Adam step."""
+import functools
 import itertools
 import math
 import os
@@ -618,10 +619,13 @@ def _grid():
                     yield A, hid, tph, 1.0
 
 
+_GRID_T, _GRID_B = 4, 16
+
+
 def test_sweep_admission_implies_the_kernels_capacity():
     admitted, parent_bad, top = 0, {}, {"nin": 0, "record": 0, "lds": 0}
     for A, hid, tph, tw in _grid():
-        plan = C.em_plan_dims(_GRID_OBS, A, hid, tph or (16,), "multistep", tw, 4, 16)
+        plan = C.em_plan_dims(_GRID_OBS, A, hid, tph or (16,), "multistep", tw, _GRID_T, _GRID_B)
         ok = plan["lds"] <= C.LDS_BUDGET          # em_create accepts the shape at all
         # the fallback: the fused step's LDS beside em_seq_grad_kernel's static arrays (the same ones)
         assert (plan["lds"][ok] + C.SW_STATIC_LDS <= C.CU_LDS_BYTES).all()
@@ -653,3 +657,95 @@ def test_parent_rule_admitted_shapes_the_kernel_cannot_run(shape, tw, limit):
     assert _parent_sw_admits(lims, dyn)[i] and not lims[limit][i]
     assert all(within[i] for name, within in lims.items() if name != limit)
     assert not C.em_plan(shape, "multistep", tw, 2, 16)["sweep"]
+
+
+# ---------------------------------------------------------------------------
+# The C++ plan itself (csrc/emlayout.h: em_plan, which fqlpop_emtrain_create copies) against
+# em_plan_dims: tests/cpp/emlayout_test.cpp, a stand-alone child process under AddressSanitizer and
+# UBSan, walks the grid above, SHAPES and PLAN_PROBES, checks the kernels' layouts at every shape
+# and writes one record per shape.  The fields are integers: equal, no tolerance.  Every field at
+# the named shapes, of every kind; over the grid (5.7 million multistep shapes) whether the shape
+# is refused, the fused step's LDS and the path.
+# ---------------------------------------------------------------------------
+_PLAN_FIELDS = ("lds", "sweep", "sweep_lds", "tchunks", "blocks", "seq_stride", "nin", "record", "sweep_need")
+
+
+_KINDS = {"state": 0, "termination": 1, "multistep": 2}      # FQLPOP_EM_*
+
+
+def _named_plan_cases():
+    """(label, kind, D, A, hid, tph, tw, T, B, option) of SHAPES A-L, multistep with and without the
+    frozen predictor and the sweep option and the two single-step kinds, and of PLAN_PROBES."""
+    for name, (D, A, hid, tph) in C.SHAPES.items():
+        for tw in (0.0, 1.0):
+            for T_, B, option in ((2, 16, 1), (67, 48, 1), (2, 16, 0)):
+                yield name, "multistep", D, A, hid, tph, tw, T_, B, option
+            yield name, "state", D, A, hid, tph, tw, 1, 32, 1
+        yield name, "termination", D, A, hid, tph, 0.0, 1, 32, 1
+    for D, A, hid, tph, tw, _ in C.PLAN_PROBES:
+        yield f"probe {D} {A} {hid} {tph}", "multistep", D, A, hid, tph, tw, 2, 16, 1
+
+
+def _shape_lines():
+    def ints(v):
+        return f"{len(v)} " + " ".join(str(int(x)) for x in v)
+
+    for _, kind, D, A, hid, tph, tw, T_, B, option in _named_plan_cases():
+        net = tph if kind == "termination" else hid      # the trained net's hidden widths
+        yield f"shape {_KINDS[kind]} {D} {A} {ints(net)} {ints(tph if tw > 0 else ())} {tw} {T_} {B} {option}"
+    yield (f"grid {_GRID_T} {_GRID_B} {ints(_GRID_OBS)} {ints(_GRID_ACT)} {ints(_GRID_W)} {len(_GRID_TP)} " +
+           " ".join(ints(tp) for tp in _GRID_TP))
+
+
+def _run_emlayout_test(tmp_path, src=os.path.join(ROOT, "tests", "cpp", "emlayout_test.cpp")):
+    """emlayout_test's records [shapes][refused, *_PLAN_FIELDS] and its report."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no system C++ compiler (c++, g++ or clang++) on PATH")
+    exe, shapes, plans = (str(tmp_path / f) for f in ("emlayout_test", "shapes.txt", "plans.bin"))
+    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=undefined", src, "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stdout + cc.stderr
+    with open(shapes, "w") as f:
+        f.write("\n".join(_shape_lines()) + "\n")
+    run = subprocess.run([exe, shapes, plans], capture_output=True, text=True)
+    return np.fromfile(plans, np.int32).reshape(-1, 1 + len(_PLAN_FIELDS)), run
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_lds_sweep():
+    """em_plan_dims' (lds, sweep) over _grid(), obs fastest: two arrays of one entry per shape."""
+    plans = [C.em_plan_dims(_GRID_OBS, A, hid, tph or (16,), "multistep", tw, _GRID_T, _GRID_B)
+             for A, hid, tph, tw in _grid()]
+    return np.concatenate([p["lds"] for p in plans]), np.concatenate([p["sweep"] for p in plans])
+
+
+def _plan_mismatches(got):
+    """The shapes at which emlayout_test's records differ from em_plan_dims: labels of the named
+    ones, row numbers of the grid's."""
+    named = list(_named_plan_cases())
+    bad = []
+    for row, (name, kind, D, A, hid, tph, tw, T_, B, option) in zip(got, named):
+        plan = C.em_plan_dims(D, A, hid, tph, kind, tw, T_, B, bool(option))
+        want = [0] + [int(plan[k]) for k in _PLAN_FIELDS] if plan["lds"] <= C.LDS_BUDGET else [1] + [0] * len(_PLAN_FIELDS)
+        if row.tolist() != want:
+            bad.append((f"{name} {kind} tw {tw} T {T_} B {B} option {option}", row.tolist(), want))
+    lds, sweep = _grid_lds_sweep()
+    grid = got[len(named):]
+    assert grid.shape[0] == lds.size
+    refused = lds > C.LDS_BUDGET
+    want = np.stack([refused, np.where(refused, 0, lds), sweep & ~refused], 1)
+    bad += [(f"grid row {i}", grid[i].tolist(), want[i].tolist()) for i in np.flatnonzero((grid[:, :3] != want).any(1))]
+    return bad
+
+
+def test_cpp_plan_equals_em_plan_dims_over_the_grid(tmp_path):
+    got, run = _run_emlayout_test(tmp_path)
+    print(run.stdout)
+    assert run.returncode == 0 and " 0 failed checks" in run.stdout, run.stdout + run.stderr
+    bad = _plan_mismatches(got)
+    assert not bad, (len(bad), bad[:12])
+    # not vacuous: shapes on either path, and shapes the fused step's budget refuses
+    assert got[:, 2].sum() > 10000 and (got[:, 2] == 0).sum() > 10000 and got[:, 0].sum() > 10000
