@@ -424,6 +424,8 @@ struct LossArgs {
     const float* alpha;           // per slot
     int B, A, E, da_n;
     int q_min, normq;
+    int metric;                   // the critic loss reduces amet against act into the mse info slot (0: a
+                                  // train step that leaves it to metric_mse_kernel)
     const float* hparams;         // [slots][HP_COUNT]: the critic loss reads its member's discount
     int nz;
     const int* slots;
@@ -431,6 +433,16 @@ struct LossArgs {
 void launch_loss_critic(const LossArgs& a, hipStream_t s);
 void launch_loss_bc(const LossArgs& a, hipStream_t s);
 void launch_loss_actor(const LossArgs& a, hipStream_t s);
+// The mse info slot alone, as loss_critic_kernel reduces it (the same thread -> element
+// mapping and summation order: bit-identical): info[9] = mean((amet - act)^2) over n = A B.
+struct MetricArgs {
+    TRef amet, act;               // [A][B]
+    TRef info;                    // [16]
+    int n;
+    int nz;
+    const int* slots;
+};
+void launch_metric_mse(const MetricArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------- optimiser ----
 void launch_adam(const AdamArgs& a, hipStream_t s);

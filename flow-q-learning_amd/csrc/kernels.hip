@@ -1424,7 +1424,8 @@ void launch_ln_gelu_fwd(const LnArgs& a, hipStream_t s) {
 //   HEAD_EULER    x += v/steps in o2 rows; last step: o0 = clip(x) (a_flow)
 //   HEAD_OS       M = 3B: [0,B) a' = clip(v) -> o1 (target-critic input rows)
 //                 [B,2B) a_pi = v -> o0, clip(a_pi) -> o2 cols B.. (critic input)
-//                 [2B,3B) clip(v) -> o3 (mse metric actions)
+//                 [2B,3B) clip(v) -> o3 (mse metric actions); a launch over the metric
+//                 columns alone counts them from 0 and passes B = 0 (all columns -> o3)
 //   HEAD_ACT      o0 = clip(v)                              (sample_actions)
 template <int MODE>
 DEV void head_write(const HeadArgs& a, int slot, int y, int j, int m, float v) {
@@ -3578,6 +3579,16 @@ void launch_sample(const SampleArgs& a, hipStream_t s, const SynthRing* ring) {
 }
 
 // =============================================================== losses ====
+// A thread's partial sum of the mse metric sum_i (am[i] - ac[i])^2 (256-thread blocks)
+DEV float metric_partial(const float* am, const float* ac, int n) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float d = am[i] - ac[i];
+        s += d * d;
+    }
+    return s;
+}
+
 // [EXT] critic_loss: y = r + gamma*mask*agg_k Qt_k(s',a'); L = mean (Q-y)^2
 // over [E,B]; also the Q-term of actor_loss (q = mean_k Q_k(s, clip(a_pi))),
 // its gradient seeds, and the mse metric.  One block per member.
@@ -3619,14 +3630,9 @@ __global__ __launch_bounds__(256) void loss_critic_kernel(const LossArgs a) {
         qpi_s += qp;
         qpi_abs += fabsf(qp);
     }
-    // mse metric of sample_actions(s) against the dataset actions
-    const float* am = at(a.amet, slot);
-    const float* ac = at(a.act, slot);
-    float smse = 0.f;
-    for (int i = threadIdx.x; i < A * B; i += 256) {
-        const float d = am[i] - ac[i];
-        smse += d * d;
-    }
+    // mse metric of sample_actions(s) against the dataset actions (a.metric 0: left to
+    // metric_mse_kernel, the slot is not written)
+    float smse = a.metric ? metric_partial(at(a.amet, slot), at(a.act, slot), A * B) : 0.f;
     float rv[11] = {sq, qs, qmx, qmn, qpi_s, qpi_abs, smse, sdq[0], sdq[1], sdq[2], sdq[3]};
     block_reduce_n<11>(rv, {0, 0, 1, 2, 0, 0, 0, 0, 0, 0, 0}, red);
     sq = rv[0];
@@ -3651,8 +3657,18 @@ __global__ __launch_bounds__(256) void loss_critic_kernel(const LossArgs a) {
         info[3] = qmn;
         info[7] = -lam * qmean_pi;
         info[8] = qmean_pi;
-        info[9] = smse / (float)(A * B);
+        if (a.metric) info[9] = smse / (float)(A * B);
     }
+}
+
+// The mse info slot on its own (MetricArgs): loss_critic_kernel's partial sums, the same wave
+// and cross-wave order as its slot of block_reduce_n, the same division.  One block per member.
+__global__ __launch_bounds__(256) void metric_mse_kernel(const MetricArgs a) {
+    const int slot = a.slots[blockIdx.x];
+    __shared__ float red[8];
+    float rv[1] = {metric_partial(at(a.amet, slot), at(a.act, slot), a.n)};
+    block_reduce_n<1>(rv, {0}, red);
+    if (threadIdx.x == 0) at(a.info, slot)[9] = rv[0] / (float)a.n;
 }
 
 // [EXT] BC flow-matching loss: mean over [B,A] of (v_theta(s,x_t,t) - (a - x0))^2.
@@ -3740,6 +3756,9 @@ __global__ __launch_bounds__(256) void loss_actor_kernel(const LossArgs a) {
 
 void launch_loss_critic(const LossArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(loss_critic_kernel, dim3(a.nz), dim3(256), 0, s, a);
+}
+void launch_metric_mse(const MetricArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(metric_mse_kernel, dim3(a.nz), dim3(256), 0, s, a);
 }
 void launch_loss_bc(const LossArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(loss_bc_kernel, dim3(a.nz), dim3(256), 0, s, a);

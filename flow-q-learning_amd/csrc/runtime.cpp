@@ -72,6 +72,9 @@ struct EngineOptions {
     int em_ens_xcd = 0;    // env-model ensemble training: 1 = deal the K models' blocks so that the block
                            // ids sharing an XCD hold at most ceil(K / 8) models (emtrain.hip,
                            // ens_block_map); 0 = model-major.  Same results either way.
+    int lazy_metric = 1;   // the metrics-only third of the one-step actor forward (the mse info value) is
+                           // evaluated when the train info is read, not in every step (materialise_metric;
+                           // bit-identical); 0 = in the step.  With the streamed forward only (stream_fwd).
 };
 // (Schedule experiments that measured slower were removed in round 4 and stay in git history
 // and DESIGN.md section 5: a 4th stream, stream priorities, the critic optimiser on the main
@@ -109,6 +112,7 @@ const EngineOptionRef kEngineOptions[] = {
     {"split_blocks", &EngineOptions::split_blocks, 64, 1024},
     {"em_seq_sweep", &EngineOptions::em_seq_sweep, 0, 1},
     {"em_ens_xcd", &EngineOptions::em_ens_xcd, 0, 1},
+    {"lazy_metric", &EngineOptions::lazy_metric, 0, 1},
 };
 
 // ---------------------------------------------------------------- host Philox
@@ -297,6 +301,15 @@ struct fqlpop : StepStreams<> {
     Buf q, qt, dq, vpred, dv, act_t, x0_t, rew_t, mask_t, apiraw, aflow, amet, da, dout_os;
     Buf info, vinfo;
     Buf inj_batch, inj_noise;
+    // engine option lazy_metric: the last train step left its mse info value to be evaluated
+    // on demand (materialise_metric): the parameter buffer that step read and its active slots
+    bool lazy_metric = false;
+    struct {
+        bool pending = false;
+        int buf = 0;
+        std::vector<int> slots;
+    } metric;
+    long long metric_evals = 0;  // materialisations that launched (fqlpop_metric_evaluations)
 
     Event<> ev_sample, ev_bcfwd, ev_bcloss, ev_flow, ev_bdone;
     Event<> ev_t0, ev_t1;  // fqlpop_time_dominant_kernel
@@ -1056,17 +1069,22 @@ void adam_net(const Ctx& c, hipStream_t s, int ni) {
 
 // Columns of a streamed forward: [st_lo, st_hi) keep their activations (U, G, MU / RS) for
 // the backward pass, the layer outputs G only up to g_hi (default st_hi).  An empty range
-// stores nothing (the target critic).
+// stores nothing (the target critic).  The launch runs the M columns of the input from column
+// c0 (default: all ld); the kernel counts columns from c0, so only a launch from column 0 stores.
 struct FwdCols {
     int st_lo, st_hi;
     int g_hi = -1;
+    int c0 = 0, M = -1;
 };
 
-// One whole-network forward launch (stream_fwd_kernel) of `n` over all ld columns of its input.
+// One whole-network forward launch (stream_fwd_kernel) of `n` over the columns `k` of its input.
 void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int mode, const HeadArgs& head) {
     fqlpop* h = c.h;
     const NetLayout& N = *n.lay;
     const bool store = k.st_hi > k.st_lo, stats = store && !n.MU.empty();
+    const int M = k.M < 0 ? n.ld - k.c0 : k.M;
+    ARGCHK(k.c0 % 16 == 0 && M > 0 && M % 16 == 0 && k.c0 + M <= n.ld && (!store || (k.c0 == 0 && k.st_hi <= M)),
+           "streamed forward: bad column range");
     StreamArgs a{};
     a.params = *n.arena + N.off;
     a.P = n.arena_ss;
@@ -1084,9 +1102,9 @@ void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int
             if (stats && N.ln) { a.MU[l] = n.MU[l].p; a.RS[l] = n.RS[l].p; }
         }
     }
-    a.x0 = n.X->p;
+    a.x0 = n.X->p + k.c0;
     a.x0_ss = n.X->ss;
-    a.ld_x = n.ld; a.K0 = N.in_dim; a.L = N.L; a.M = n.ld;
+    a.ld_x = n.ld; a.K0 = N.in_dim; a.L = N.L; a.M = M;
     if (store) { a.s_ss = n.U[0].ss; a.s_sy = n.sy; }
     if (stats) { a.st_ss = n.MU[0].ss; a.st_sy = n.st_sy; }
     a.ld_s = n.ld; a.st_lo = k.st_lo; a.st_hi = k.st_hi;
@@ -1099,7 +1117,7 @@ void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int
     if (F > 1) {
         SplitFwdArgs sa{};
         sa.s = a;
-        sa.sync = split_prep(h, n.fwd_site, (long long)(n.ld / 16) * N.E * c.nz, s);
+        sa.sync = split_prep(h, n.fwd_site, (long long)(M / 16) * N.E * c.nz, s);
         launch_split_fwd(mode, N.ln, false, F, sa, s);
     } else {
         launch_stream_fwd(mode, N.ln, a, s);
@@ -1302,6 +1320,7 @@ void split_euler_phase_report(const unsigned long long* ph, long long nb, int L,
 }
 
 void flip_params(fqlpop* h);
+bool split_error_pending(const fqlpop* h);
 
 // Enqueue one population update (train) or one total_loss pass (!train).
 //
@@ -1355,7 +1374,10 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     sa.rew_t = h->rew_t.ref();
     sa.mask_t = h->mask_t.ref();
     sa.nz = c.nz; sa.slots = h->slots;
-    // one-step actor forward on [s'; s; s] (z_next; z_d; z_metric), on sM
+    // one-step actor forward on [s'; s; s] (z_next; z_d; z_metric), on sM.  The z_metric third
+    // feeds the mse info value alone: a train step with lazy_metric leaves those columns (which
+    // the sampler still writes) to materialise_metric and runs [s'; s] only.
+    const bool lazy = train && h->lazy_metric;
     auto os_forward = [&]() {
         HeadArgs ha = head_args(c, h->n_os);
         ha.o0 = h->apiraw.ref(); ha.ld0 = B;
@@ -1364,7 +1386,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         ha.o3 = h->amet.ref(); ha.ld3 = B;
         if (h->stream_fwd) {
             // only the z_d rows [B, 2B) are back-propagated (distill + Q loss)
-            stream_fwd(c, sM, h->n_os, FwdCols{B, 2 * B}, HEAD_OS, ha);
+            stream_fwd(c, sM, h->n_os, FwdCols{B, 2 * B, -1, 0, lazy ? B2 : 3 * B}, HEAD_OS, ha);
         } else {
             fwd_hidden(c, sM, h->n_os);
             launch_head_fwd(HEAD_OS, ha, sM);
@@ -1398,6 +1420,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     la.g_bcb4 = pref(h, h->grads, h->bc, h->bc.b[L]);
     la.g_osb4 = pref(h, h->grads, h->os, h->os.b[L]);
     la.info = (train ? h->info : h->vinfo).ref();
+    la.metric = lazy ? 0 : 1;
     la.alpha = h->alpha;
     la.B = B; la.A = A; la.E = h->E;
     la.q_min = h->cfg.q_agg_min; la.normq = h->cfg.normalize_q_loss;
@@ -1581,6 +1604,19 @@ Graphs& graph_for(fqlpop* h, bool train, bool inj_batch, bool inj_noise, bool re
 // launch that the graphs bake in calls this; graph_for captures again on demand.
 void drop_graphs(fqlpop* h) { h->graphs.clear(); }
 
+// With lazy_metric the one-step forward's split site runs 2B-column train launches and
+// B-column metric launches between the 3B-column validation launches, so the exchange words
+// of the site's last third of clusters would keep one validation launch's tags until the
+// next, and the 24-bit generation in a tag repeats after 2^24 launches: cleared before every
+// validation launch (tag 0 matches no hand-off), as update_slots does for a changed count.
+void clear_metric_tail(fqlpop* h) {
+    fqlpop::SplitSite& st = h->split_site[SITE_OSF];
+    if (!h->lazy_metric || !st.xch || split_plan(h, h->nz).F[SITE_OSF] <= 1) return;
+    const long long third = (long long)(h->B / 16) * h->nz, words = split_cluster_bytes() / 8;
+    unsigned long long* x = st.xch;
+    HIPCHK(hipMemsetAsync(x + 2 * third * words, 0, split_cluster_bytes() * third, h->sM));
+}
+
 void run(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     if (h->nz == 0) return;
     if (h->stream_bwd && h->wt_dirty) {  // params set on the host side since the last step
@@ -1588,14 +1624,75 @@ void run(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         transpose_nets(h, h->sM, 7, true, h->params, h->paramsT_nx);
         h->wt_dirty = false;
     }
+    if (!train) clear_metric_tail(h);
     if (!h->cfg.use_graph) {
         enqueue(h, train, inj_batch, inj_noise);
-        if (train) flip_params(h);
-        return;
+    } else {
+        Graphs& gr = graph_for(h, train, inj_batch, inj_noise, false);
+        HIPCHK(hipGraphLaunch(gr.exec, h->sM));
     }
-    Graphs& gr = graph_for(h, train, inj_batch, inj_noise, false);
-    HIPCHK(hipGraphLaunch(gr.exec, h->sM));
-    if (train) flip_params(h);
+    if (!train) return;
+    flip_params(h);
+    if (h->lazy_metric) {
+        // this step's mse is pending (it replaces an earlier step's: the step's sampler and
+        // optimiser overwrote that one's inputs, and its info that one's): the step read the
+        // buffer that is now params_nx
+        h->metric.pending = true;
+        h->metric.buf = h->cur ^ 1;
+        h->metric.slots = h->h_slots;
+    }
+}
+
+// The mse info value of the last train step, if it is still pending (engine option
+// lazy_metric): sample_actions(s, z_metric) against the batch actions, evaluated from what
+// the step left on the device.  The metric columns [2B, 3B) of os_in and act_t stay as the
+// step's sampler wrote them until the next sampler runs; the parameters the step read stay
+// in the other half of the double buffer (params_nx since the flip) until the next optimiser
+// writes it; the active slots are those of the step.  So this is the same forward kernel on
+// the same inputs and the same reduction as the eager step's (lazy_metric 0): bit-identical.
+// Eager launches on sM, after the step; not captured.  A no-op when nothing is pending.
+// Callers: fqlpop_read_info(which 0), and BEFORE its first write every entry point that
+// overwrites an input of the evaluation or moves its result:
+//   either parameter buffer    state_copy (fqlpop_set_state: which 0 writes params and mirrors
+//                              them; m / v are materialised too, one rule for every write),
+//                              fqlpop_set_member with reinit (init_member), fqlpop_set_active
+//                              (mirror_params of the idle members), fqlpop_clone_members;
+//   the active slots           fqlpop_set_active (update_slots);
+//   os_in / act_t              fqlpop_step_injected and fqlpop_total_loss (their sampler);
+//   info rows                  fqlpop_clone_members, fqlpop_set_member with reinit.
+// fqlpop_step does not: its step replaces the record.  The rollouts, collects, sample_actions,
+// set_dataset, set_count, set_member without reinit and the hparams write none of these.
+void materialise_metric(fqlpop* h) {
+    if (!h->metric.pending) return;
+    h->metric.pending = false;
+    HIPCHK(hipStreamSynchronize(h->sM));  // (every stream of the step has joined sM)
+    // a failed split launch left the step's results invalid (its members poison, and
+    // fqlpop_read_info refuses): the metric goes with them, and no split launch follows on
+    // counters the failed one may have left set
+    if (split_error_pending(h)) return;
+    if (h->metric.slots != h->h_slots)
+        throw Err{FQLPOP_E_STATE, "the active set changed under a pending metric evaluation"};
+    if (h->nz == 0) return;
+    const Ctx c = step_ctx(h);
+    const int B = h->B;
+    float* pre = h->params_buf[h->metric.buf];  // the parameters the step read
+    Net os = h->n_os;
+    os.arena = &pre;
+    HeadArgs ha = head_args(c, os);
+    // HEAD_OS sends column m >= 2 head.B to o3; the launch counts its columns from the metric
+    // third, so with head.B = 0 every one of them is a metric column of o3 = amet
+    ha.B = 0;
+    ha.o3 = h->amet.ref(); ha.ld3 = B;
+    stream_fwd(c, h->sM, os, FwdCols{0, 0, -1, 2 * B, B}, HEAD_OS, ha);
+    MetricArgs ma{};
+    ma.amet = h->amet.ref();
+    ma.act = h->act_t.ref();
+    ma.info = h->info.ref();
+    ma.n = h->A * B;
+    ma.nz = c.nz; ma.slots = h->slots;
+    launch_metric_mse(ma, h->sM);
+    HIPCHK(hipGetLastError());
+    ++h->metric_evals;
 }
 
 // The graph of one step for the current (mode, active count, probe set, parameter buffer),
@@ -1819,17 +1916,21 @@ int fqlpop_diagnostic_build(void) {
 #endif
 }
 
-double fqlpop_flops_per_member_step(const fqlpop_config* c) {
-    // F(i,o) = 2B(iH + (L-1)H^2 + Ho) per forward; dX without
-    // the first layer = 2B((L-1)H^2 + Ho).
+// F(i,o) = 2B(iH + (L-1)H^2 + Ho) per forward; dX without
+// the first layer = 2B((L-1)H^2 + Ho).  metric: with the one-step forward's z_metric third.
+static double update_flops(const fqlpop_config* c, bool metric) {
     const double B = c->batch_size, H = c->hidden_dim, L = c->num_hidden, D = c->obs_dim, A = c->action_dim;
     const double E = c->num_qs, S = c->flow_steps;
     auto F = [&](double i, double o) { return 2.0 * B * (i * H + (L - 1) * H * H + H * o); };
     auto dX = [&](double o) { return 2.0 * B * ((L - 1) * H * H + H * o); };
     const double Fc = F(D + A, 1), Fbc = F(D + A + 1, A), Fos = F(D + A, A);
-    return Fos + E * Fc + E * Fc + E * Fc + E * dX(1) + Fbc + Fbc + dX(A) + S * Fbc + Fos + Fos + dX(A) +
-           E * Fc + E * Fc + Fos;
+    return (metric ? Fos : 0.0) + E * Fc + E * Fc + E * Fc + E * dX(1) + Fbc + Fbc + dX(A) + S * Fbc + Fos + Fos +
+           dX(A) + E * Fc + E * Fc + Fos;
 }
+
+double fqlpop_flops_per_member_step(const fqlpop_config* c) { return update_flops(c, true); }
+
+double fqlpop_train_step_flops(fqlpop_t* h) { return h ? update_flops(&h->cfg, !h->lazy_metric) : 0.0; }
 
 int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, const uint64_t* seeds_in,
                   int device, fqlpop_t** out) {
@@ -1880,6 +1981,7 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         h->euler_fused = euler_flow_supported(H, L, D, A, B) && !h->bc.ln && eo.euler_fused;
         h->stream_fwd = stream_fwd_supported(H, L, D + A + 1, A, B) && eo.stream_fwd;
         h->stream_bwd = stream_bwd_supported(H, L, A, B, B) && eo.stream_bwd;
+        h->lazy_metric = h->stream_fwd && eo.lazy_metric;  // (the per-layer forward runs all 3B columns)
         // Adam / EMA / W^T / grad stats fused into the grouped dW epilogue
         h->fused_adam = h->stream_bwd && H % 128 == 0 && L <= GEMM_GROUP_MAX && h->critic.off == 0 && eo.fused_adam;
         if (h->euler_fused) {  // dominant kernel: one persistent Euler launch per step
@@ -2130,6 +2232,8 @@ int fqlpop_set_dataset(fqlpop_t* h, int which, const float* obs, const float* ac
 int fqlpop_set_active(fqlpop_t* h, const uint8_t* mask) {
     return guard([&] {
         ARGCHK(h && mask, "null argument");
+        HIPCHK(hipSetDevice(h->device));
+        materialise_metric(h);
         for (int i = 0; i < h->n; ++i) h->active[i] = mask[i] ? 1 : 0;
         update_slots(h);
         // a member that does not step keeps its parameters in both buffers
@@ -2183,6 +2287,7 @@ int fqlpop_step_injected(fqlpop_t* h, const float* batch, const float* noise) {
         if (split_error_pending(h)) sync_all_streams(h);
         check_split_error(h, -1, true);
         if (h->nz == 0) return;
+        materialise_metric(h);
         stage_injected(h, batch, noise);
         run(h, true, true, noise != nullptr);
         HIPCHK(hipStreamSynchronize(h->sM));  // host buffers are borrowed only for the call
@@ -2196,6 +2301,7 @@ int fqlpop_total_loss(fqlpop_t* h, const float* batch, const float* noise) {
         HIPCHK(hipSetDevice(h->device));
         if (h->nz == 0) return;
         if (!batch && h->ds[0].rows == 0 && h->ds[1].rows == 0) throw Err{FQLPOP_E_STATE, "no dataset set"};
+        materialise_metric(h);
         stage_injected(h, batch, noise);
         run(h, false, batch != nullptr, noise != nullptr);
         if (batch) HIPCHK(hipStreamSynchronize(h->sM));
@@ -2208,9 +2314,21 @@ int fqlpop_read_info(fqlpop_t* h, int which, float* out) {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipStreamSynchronize(h->sM));
         check_split_error(h);
+        if (which == 0) {
+            materialise_metric(h);
+            HIPCHK(hipStreamSynchronize(h->sM));
+            check_split_error(h);  // (the metric's forward may be a split launch)
+        }
         const Buf& info = which ? h->vinfo : h->info;
         HIPCHK(hipMemcpy(out, info.p, sizeof(float) * info.ss * h->n,
                          hipMemcpyDeviceToHost));
+    });
+}
+
+int fqlpop_metric_evaluations(fqlpop_t* h, int64_t* n) {
+    return guard([&] {
+        ARGCHK(h && n, "null argument");
+        *n = h->metric_evals;
     });
 }
 
@@ -2296,6 +2414,7 @@ static void state_copy(fqlpop* h, int member, int which, float* flat, const floa
     float* arena = which == 0 ? h->params : which == 1 ? h->adam_m : h->adam_v;
     std::vector<float> blk((size_t)h->P), tblk((size_t)h->PT, 0.f);
     HIPCHK(hipSetDevice(h->device));
+    if (!get) materialise_metric(h);
     HIPCHK(hipDeviceSynchronize());
     // never export (checkpoint, member copy) state a failed launch wrote; a write restores it
     if (get) check_split_error(h, member);
@@ -2381,6 +2500,7 @@ int fqlpop_set_member(fqlpop_t* h, int member, float alpha, uint64_t seed, int r
         HIPCHK(hipMemcpy(h->seeds + member, &seed, sizeof(uint64_t), hipMemcpyHostToDevice));
         upload_skey(h, member);
         if (reinit) {
+            materialise_metric(h);
             (void)absorb_split_error(h);
             init_member(h, member, seed);
             if (h->synth.ctr)  // a fresh member has collected nothing
@@ -2447,6 +2567,7 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
             is_dst[dst[i]] = 1;
         }
         HIPCHK(hipSetDevice(h->device));
+        materialise_metric(h);
         // never copy state a failed split launch wrote (no copy, no sync when the word is clear)
         if (split_error_pending(h)) sync_all_streams(h);
         (void)absorb_split_error(h);

@@ -8,7 +8,8 @@
   --kernel-iters 1` (round_profile.sh), every launch of the concurrent step; launches per step
   = round(calls / (S + W)) (the one isolated replay of the dominant kernel is rounded away);
 * serial: the `avg us` column of pmc_table.py's table over a `bench.py --serial` run
-  (round_pmc.sh), every launch uncontended on one stream.
+  (round_pmc.sh), every launch uncontended on one stream; or, given as a .csv, the
+  kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of it.
 stretch = in-step average / serial average of the same launch."""
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ def read_instep(path: str):
 
 
 def read_serial(path: str):
+    if path.endswith(".csv"):  # a kernel_stats.csv of the --serial run instead of the PMC table
+        return read_instep(path)
     out = {}
     with open(path) as f:
         for line in f:

@@ -140,6 +140,8 @@ _SIGS = {
                                                    ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double)]),
     "fqlpop_flops_per_member_step": (ctypes.c_double, [ctypes.POINTER(Config)]),
+    "fqlpop_train_step_flops": (ctypes.c_double, [_P]),
+    "fqlpop_metric_evaluations": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_set_probe": (ctypes.c_int, [_P, ctypes.c_int]),
     "fqlpop_dominant_kernel_info": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int,
                                                    ctypes.POINTER(ctypes.c_double),

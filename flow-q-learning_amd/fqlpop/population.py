@@ -162,7 +162,20 @@ class Population:
 
     @property
     def flops_per_member_step(self) -> float:
-        return float(self.lib.fqlpop_flops_per_member_step(ctypes.byref(self._c)))
+        """What one train step of this population runs per member (fqlpop_train_step_flops):
+        without the metrics-only third of the one-step forward under engine option
+        ``lazy_metric``, which runs when the train info is read."""
+        fn = getattr(self.lib, "fqlpop_train_step_flops", None)
+        if fn is None:  # an A/B build of an older commit (FQLPOP_LIB): every step ran all of it
+            return float(self.lib.fqlpop_flops_per_member_step(ctypes.byref(self._c)))
+        return float(fn(self._h))
+
+    @property
+    def metric_evaluations(self) -> int:
+        """Deferred mse evaluations launched so far (fqlpop_metric_evaluations)."""
+        n = ctypes.c_int64()
+        check(self.lib.fqlpop_metric_evaluations(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def sync(self):
         check(self.lib.fqlpop_sync(self._h))

@@ -97,6 +97,12 @@ const char* fqlpop_last_error(void);
  *   blocks of an ensemble training launch.  0: model-major.  1: the block ids that share an
  *   XCD (id mod 8) hold at most ceil(K / 8) models, so an XCD's L2 holds those models'
  *   weights only (fqlpop_emtrain_ensemble_block_map).  Bit-identical results.
+ *   lazy_metric (0/1, default 1): a train step leaves the mse info value (the one-step
+ *   forward's z_metric columns, a third of that launch, read by no loss or gradient) to be
+ *   evaluated when it is read: by fqlpop_read_info(h, 0, .), and before any call that would
+ *   overwrite what the evaluation reads (fqlpop_set_state, _set_member with reinit,
+ *   _set_active, _clone_members, _step_injected, _total_loss).  Bit-identical to 0, which
+ *   evaluates it in every step.  Takes effect with the streamed forward (stream_fwd).
  * The defaults are the measured-fastest configuration.  Unknown names or values
  * out of range: FQLPOP_E_ARG.  (Round 3's schedule experiments that measured slower --
  * streams, prio, cdw_sb, dw_stagger, xstep, bc_late, fuse_dq, early_join -- were
@@ -171,7 +177,8 @@ int fqlpop_total_loss(fqlpop_t* h, const float* batch, const float* noise);
 
 /* Copies info[n_members][FQLPOP_INFO_STRIDE] of the last train step (which=0)
  * or last total_loss (which=1) to the host; synchronises.  Replaces the
- * update_info / val_info dicts (trainer/experiment.py:109,115). */
+ * update_info / val_info dicts (trainer/experiment.py:109,115).  which=0 first evaluates
+ * the last train step's mse if it is still pending (engine option lazy_metric). */
 int fqlpop_read_info(fqlpop_t* h, int which, float* out);
 
 /* Replaces agent.sample_actions(observations=obs, seed=..)
@@ -737,6 +744,13 @@ int fqlpop_initobs_sample(fqlpop_initobs_t* h, int64_t n, uint64_t seed, const f
 /* Algorithmic GEMM FLOPs of one member-update at the handle's config
  * (SURVEY.md 8d formula). */
 double fqlpop_flops_per_member_step(const fqlpop_config* cfg);
+/* GEMM FLOPs one train step of this population runs per member: the count above, less the
+ * one-step forward's z_metric columns when the handle defers them (engine option
+ * lazy_metric); those run when the train info is read.  0 for a null handle. */
+double fqlpop_train_step_flops(fqlpop_t* h);
+/* Deferred mse evaluations (engine option lazy_metric) the handle has launched so far: a
+ * fqlpop_read_info with nothing pending launches nothing.  [test hook] */
+int fqlpop_metric_evaluations(fqlpop_t* h, int64_t* n);
 
 #ifdef __cplusplus
 }
