@@ -410,6 +410,22 @@ struct SynthCloneArgs {
     int src[16], dst[16];         // CLONE_MAX_PAIRS
 };
 void launch_synth_clone(const SynthCloneArgs& a, hipStream_t s);
+// fqlpop_synth_write / fqlpop_synth_append: n rows of device-visible fields into one slot's ring.
+//   launch_synth_put         row i to position (base + i) mod cap, base = 0 (write) or the
+//                            slot's head (append), read from the device counters; writes no
+//                            counter.  n == 0: no launch.
+//   launch_synth_put_commit  write: rows = n, head = appended mod cap, appended = appended;
+//                            append: the collect's rule, head, rows, appended advanced by n.
+struct SynthPutArgs {
+    SynthRing ring;
+    int D, A, slot;
+    int write;                    // 1: fqlpop_synth_write, 0: fqlpop_synth_append
+    long long n;                  // 0 .. cap
+    long long appended;           // write only
+    const float *obs, *act, *rew, *mask, *nobs;   // [n][D], [n][A], [n], [n], [n][D]
+};
+void launch_synth_put(const SynthPutArgs& a, hipStream_t s);
+void launch_synth_put_commit(const SynthPutArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- loss ----
 struct LossArgs {

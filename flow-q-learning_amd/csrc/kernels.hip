@@ -4402,6 +4402,55 @@ void launch_synth_clone(const SynthCloneArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(synth_clone_kernel, dim3((unsigned)chunks, (unsigned)a.n_pairs), dim3(256), 0, s, a);
 }
 
+// Block (chunk, field): float i of a field of width w belongs to row i / w and goes to position
+// (base + i / w) mod cap, that is to float (base * w + i) mod (cap * w) of the slot's field:
+// two contiguous runs, no division (n <= cap and base < cap, so one subtraction wraps).
+// Reads head (append), which synth_put_commit_kernel advances afterwards.
+__global__ __launch_bounds__(256) void synth_put_kernel(const SynthPutArgs a) {
+    const int f = blockIdx.y;
+    const long long w = (f == 0 || f == 4) ? a.D : (f == 1 ? a.A : 1);
+    const float* __restrict__ src = f == 0 ? a.obs : f == 1 ? a.act : f == 2 ? a.rew : f == 3 ? a.mask : a.nobs;
+    float* ring = f == 0 ? a.ring.obs : f == 1 ? a.ring.act : f == 2 ? a.ring.rew : f == 3 ? a.ring.mask : a.ring.nobs;
+    const long long cap = a.ring.cap;
+    float* __restrict__ dst = ring + (long long)a.slot * cap * w;
+    const long long base = a.write ? 0 : a.ring.ctr[(long long)a.slot * SYNTH_CTR + 1];
+    const long long total = a.n * w, span = cap * w;
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+        long long j = base * w + i;
+        if (j >= span) j -= span;
+        dst[j] = src[i];
+    }
+}
+
+void launch_synth_put(const SynthPutArgs& a, hipStream_t s) {
+    if (a.n <= 0) return;
+    long long chunks = (a.n * a.D + 255) / 256;
+    if (chunks > 1024) chunks = 1024;
+    hipLaunchKernelGGL(synth_put_kernel, dim3((unsigned)chunks, 5), dim3(256), 0, s, a);
+}
+
+// The only writer of the slot's counters in a write or an append.
+__global__ void synth_put_commit_kernel(const SynthPutArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    long long* c = a.ring.ctr + (long long)a.slot * SYNTH_CTR;
+    const long long cap = a.ring.cap;
+    if (a.write) {
+        c[0] = a.n;
+        c[1] = a.appended % cap;
+        c[2] = a.appended;
+    } else {
+        const long long rows = c[0] + a.n;
+        c[0] = rows < cap ? rows : cap;
+        c[1] = (c[1] + a.n) % cap;
+        c[2] += a.n;
+    }
+}
+
+void launch_synth_put_commit(const SynthPutArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(synth_put_commit_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
 // ====================================================== ensemble rollout ==
 // (RolloutEnsArgs, kernels.h)  rollout_kernel's block under several resident env models.
 // The actor part is rollout_kernel's, statement for statement (a change to either goes

@@ -1,7 +1,7 @@
 // What the setters of the population handle (struct fqlpop, runtime.cpp) replace, each as one
 // struct of owners and sizes whose default-constructed value is the handle's documented empty
-// state, and the step's streams.  Owners only, as emboot.h: tests/cpp/popmem_test.cpp runs
-// them on the host over a counting heap.  The kernel-argument structs of kernels.h that two of
+// state, and the step's streams.  Owners only, as emboot.h: tests/cpp/popmem_test.cpp (and
+// rowstage_test.cpp for PopRowStage) runs them on the host over a counting heap.  The kernel-argument structs of kernels.h that two of
 // them keep (the env-model leaf layout) are template parameters, so that the test needs no HIP.
 #pragma once
 
@@ -121,6 +121,33 @@ struct PopStartStage {
         s.cap = cap;
         return s;
     }
+};
+
+// The host rows of the ring writes in flight (fqlpop_synth_write, fqlpop_synth_append): N mapped
+// host buffers used in turn, each one call's rows field after field (obs, act, rew, mask,
+// next_obs), grown on demand by replace_released.  Empty: no rows, none in use.
+template <int N, class BE = DefaultBackend>
+struct PopRowStage {
+    HostBuf<float, BE> host[N];
+    bool used[N] = {};  // buffer i has a reader to wait for (the handle's event i)
+    long long rows = 0;
+    int D = 0, A = 0;
+
+    static PopRowStage make(long long rows, int D, int A, unsigned flags) {
+        PopRowStage s;
+        for (auto& hb : s.host) hb = HostBuf<float, BE>((size_t)rows * width(D, A), flags, "ring row stage");
+        s.rows = rows;
+        s.D = D;
+        s.A = A;
+        return s;
+    }
+    static long long width(int D, int A) { return 2LL * D + A + 2; }  // floats per row
+    // where field f (0 obs, 1 act, 2 rew, 3 mask, 4 next_obs) of an n-row call starts, in floats
+    long long field(int f, long long n) const {
+        const long long before[5] = {0, D, D + A, D + A + 1, D + A + 2};
+        return before[f] * n;
+    }
+    long long field_width(int f) const { return f == 0 || f == 4 ? D : f == 1 ? A : 1; }
 };
 
 // The streams of a population step: the main one and three side streams, which are streams of

@@ -362,6 +362,11 @@ struct fqlpop : StepStreams<> {
     PopStartStage<kSynthStage> synth_start;
     Event<> synth_start_ev[kSynthStage];  // buffer i's last reader (made with the first stage)
     int synth_start_next = 0;
+    // the host rows of fqlpop_synth_write / fqlpop_synth_append in flight, likewise
+    static constexpr int kSynthRowStage = 2;
+    PopRowStage<kSynthRowStage> synth_rows;
+    Event<> synth_rows_ev[kSynthRowStage];  // buffer i's last reader (made with the first stage)
+    int synth_rows_next = 0;
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
@@ -3120,6 +3125,70 @@ int fqlpop_synth_read(fqlpop_t* h, int member, float* obs, float* act, float* re
         down(mask, h->synth.mask, 1);
         down(next_obs, h->synth.nobs, h->D);
     });
+}
+
+namespace {
+// fqlpop_synth_write (write: positions 0 .. n - 1, counters from n and appended) and
+// fqlpop_synth_append (positions from the device's head on).  The rows are copied to a mapped
+// host buffer, which the placement kernel reads in stream order; the caller's arrays are free
+// when this returns.
+void synth_put_run(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew, const float* mask,
+                   const float* next_obs, int64_t n, bool write, int64_t appended) {
+    need_rings(h);
+    check_member(h, member);
+    const long long cap = h->synth.cap;
+    ARGCHK(n >= 0 && n <= cap, "n must be in 0..capacity");
+    ARGCHK(n == 0 || (obs && act && rew && mask && next_obs), "null argument");
+    if (write)
+        ARGCHK(appended >= n && n == std::min<long long>(cap, appended),
+               "a ring holds rows = min(capacity, appended): n must equal it");
+    if (!write && n == 0) return;
+    HIPCHK(hipSetDevice(h->device));
+    SynthPutArgs p{};
+    p.ring = h->synth; p.D = h->D; p.A = h->A; p.slot = member;
+    p.write = write ? 1 : 0; p.n = n; p.appended = write ? appended : 0;
+    int stage = -1;
+    if (n > 0) {
+        auto& st = h->synth_rows;
+        if (n > st.rows) {
+            HIPCHK(hipStreamSynchronize(h->sM));
+            for (auto& ev : h->synth_rows_ev)
+                if (!ev) ev = Event<>(hipEventDisableTiming);
+            replace_released(st, [&] {
+                return PopRowStage<fqlpop::kSynthRowStage>::make(n, h->D, h->A, hipHostMallocMapped);
+            });
+        }
+        stage = h->synth_rows_next;
+        h->synth_rows_next = (stage + 1) % fqlpop::kSynthRowStage;
+        // the buffer's last reader (the placement of kSynthRowStage calls ago) has run
+        if (st.used[stage]) HIPCHK(hipEventSynchronize(h->synth_rows_ev[stage]));
+        float* hp = st.host[stage];
+        const float* src[5] = {obs, act, rew, mask, next_obs};
+        for (int f = 0; f < 5; ++f)
+            std::memcpy(hp + st.field(f, n), src[f], sizeof(float) * (size_t)(n * st.field_width(f)));
+        float* dp = nullptr;
+        HIPCHK(hipHostGetDevicePointer((void**)&dp, hp, 0));
+        p.obs = dp + st.field(0, n); p.act = dp + st.field(1, n); p.rew = dp + st.field(2, n);
+        p.mask = dp + st.field(3, n); p.nobs = dp + st.field(4, n);
+    }
+    launch_synth_put(p, h->sM);
+    if (stage >= 0) {
+        HIPCHK(hipEventRecord(h->synth_rows_ev[stage], h->sM));
+        h->synth_rows.used[stage] = true;
+    }
+    launch_synth_put_commit(p, h->sM);
+    HIPCHK(hipGetLastError());
+}
+}  // namespace
+
+int fqlpop_synth_write(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
+                       const float* mask, const float* next_obs, int64_t n, int64_t appended) {
+    return guard([&] { synth_put_run(h, member, obs, act, rew, mask, next_obs, n, true, appended); });
+}
+
+int fqlpop_synth_append(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
+                        const float* mask, const float* next_obs, int64_t n) {
+    return guard([&] { synth_put_run(h, member, obs, act, rew, mask, next_obs, n, false, 0); });
 }
 
 int fqlpop_synth_clear(fqlpop_t* h, int member) {

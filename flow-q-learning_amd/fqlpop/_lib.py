@@ -177,6 +177,8 @@ _SIGS = {
                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_synth_read": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64]),
     "fqlpop_synth_clear": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fqlpop_synth_write": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64, ctypes.c_int64]),
+    "fqlpop_synth_append": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64]),
     "fqlpop_emtrain_param_count": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_create": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

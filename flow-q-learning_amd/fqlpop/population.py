@@ -130,6 +130,7 @@ class Population:
             if prev_hwq is not None:
                 _lib.set_engine_option("hw_queues", prev_hwq)
         self._h = h
+        self.synth_capacity = None  # rows per ring once synth_create has run
         self.active = np.ones(self.n, dtype=bool)
         n = ctypes.c_int64()
         check(self.lib.fqlpop_state_size(self._h, ctypes.byref(n)))
@@ -568,6 +569,72 @@ class Population:
     def synth_clear(self, member: int = -1):
         """Empty one member's ring, or (-1) all; stream-ordered."""
         check(self.lib.fqlpop_synth_clear(self._h, int(member)))
+
+    def _synth_rows(self, data) -> tuple[dict, int]:
+        """``data`` (a ``synth_read`` dict) as float32 C-contiguous arrays and its row count;
+        ValueError for a missing field, a dtype other than float32 or a wrong shape."""
+        D, A = self.cfg.obs_dim, self.cfg.action_dim
+        tails = {"observations": (D,), "actions": (A,), "rewards": (), "masks": (), "next_observations": (D,)}
+        if not isinstance(data, dict) or any(k not in data for k in tails):
+            raise ValueError(f"ring rows need the fields {tuple(tails)}")
+        out, n = {}, None
+        for k, tail in tails.items():
+            a = np.asarray(data[k])
+            if a.dtype != np.float32:
+                raise ValueError(f"ring rows: {k} must be float32, got {a.dtype}")
+            n = a.shape[0] if n is None and a.ndim >= 1 else n
+            if a.shape != (n,) + tail:
+                raise ValueError(f"ring rows: {k} must have shape {(n,) + tail}, got {a.shape}")
+            out[k] = np.ascontiguousarray(a)
+        return out, int(n)
+
+    def synth_write(self, member: int, data: dict, appended: int | None = None):
+        """Ring positions 0 .. n - 1 of one member become ``data`` (the dict ``synth_read``
+        returns) and its counters rows = n, head = appended mod capacity, appended
+        (fqlpop_synth_write; ``appended`` defaults to the row count).  Stream-ordered with
+        ``step``, ``collect`` and ``clone_members``; returns without waiting."""
+        rows, n = self._synth_rows(data)
+        check(self.lib.fqlpop_synth_write(self._h, int(member), fptr(rows["observations"]), fptr(rows["actions"]),
+                                          fptr(rows["rewards"]), fptr(rows["masks"]),
+                                          fptr(rows["next_observations"]), n, n if appended is None else int(appended)))
+
+    def synth_append(self, member: int, data: dict):
+        """Appends the rows of ``data`` (a dict as ``synth_read`` returns, e.g. transitions
+        observed in an environment) to one member's ring as a collect appends its branches
+        (fqlpop_synth_append): from the ring's head on, wrapping.  Stream-ordered as
+        ``synth_write``: behind a ``collect`` it lands behind that collect's rows."""
+        rows, n = self._synth_rows(data)
+        check(self.lib.fqlpop_synth_append(self._h, int(member), fptr(rows["observations"]), fptr(rows["actions"]),
+                                           fptr(rows["rewards"]), fptr(rows["masks"]),
+                                           fptr(rows["next_observations"]), n))
+
+    def synth_state(self, member: int) -> dict:
+        """One member's ring for a checkpoint: the ``synth_read`` dict of its valid rows plus
+        "appended" and "capacity" (``load_synth_state`` puts it back); synchronises."""
+        info = self.synth_info(member)
+        state = self.synth_read(member, info["rows"])
+        state["appended"] = info["appended"]
+        state["capacity"] = int(self.synth_capacity)
+        return state
+
+    def load_synth_state(self, member: int, state: dict):
+        """Restores ``synth_state``'s dict into one member's ring: rows, positions and
+        counters, so that collects and draws continue bit for bit.  ValueError for a state
+        of another capacity (positions and wrap would differ)."""
+        if not isinstance(state, dict) or "appended" not in state or "capacity" not in state:
+            raise ValueError('a ring state needs "appended" and "capacity" (Population.synth_state)')
+        capacity = getattr(self, "synth_capacity", None)
+        if capacity is None:
+            raise ValueError("this population has no rings (synth_create)")
+        if int(state["capacity"]) != int(capacity):
+            raise ValueError(f"the ring state was saved at capacity {int(state['capacity'])}, this population's rings "
+                             f"have capacity {int(capacity)}: positions and wrap would differ")
+        rows, n = self._synth_rows(state)
+        appended = int(state["appended"])
+        if n != min(int(capacity), appended):
+            raise ValueError(f"the ring state holds {n} rows, but appended = {appended} at capacity {int(capacity)} "
+                             f"means {min(int(capacity), appended)}")
+        self.synth_write(member, rows, appended)
 
     # ----------------------------------------------------------------- state
     def get_flat(self, member: int, which: int = STATE_PARAMS) -> np.ndarray:

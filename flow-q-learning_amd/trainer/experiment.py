@@ -64,6 +64,11 @@ class Experiment:
             self.agent.from_state_dict(state_dict["agent"])
             self.experiment_name = state_dict["experiment_name"]
             self.current_step = state_dict["current_step"]
+            # the member's ring of synthetic transitions (training on world-model branches).
+            # No key: a checkpoint from before rings were saved, the ring stays empty; a key
+            # without rings: a run resumed with rollouts switched off
+            if "synth_ring" in state_dict and self._has_rings():
+                self.agent.population.load_synth_state(self.agent.member, state_dict["synth_ring"])
 
         self.logger = Logger(trainer_config.save_directory, trainer_config.env_name, self.experiment_name,
                              agent_config, use_wandb=trainer_config.use_wandb,
@@ -75,9 +80,15 @@ class Experiment:
         self.env_name = trainer_config.env_name
 
     # ------------------------------------------------------------------ io
+    def _has_rings(self) -> bool:
+        return getattr(self.agent.population, "synth_capacity", None) is not None
+
     def state_dict(self) -> dict:
-        return {"experiment_name": self.experiment_name, "logger": self.logger.state_dict(),
-                "agent": self.agent.to_state_dict(), "current_step": self.current_step}
+        sd = {"experiment_name": self.experiment_name, "logger": self.logger.state_dict(),
+              "agent": self.agent.to_state_dict(), "current_step": self.current_step}
+        if self._has_rings():  # beside "agent", whose dict stays the upstream flax layout
+            sd["synth_ring"] = self.agent.population.synth_state(self.agent.member)
+        return sd
 
     def save_agent(self, checkpoint: bool = False):
         filename = f"checkpoint_{self.current_step}.pkl" if checkpoint else "params.pkl"

@@ -55,6 +55,14 @@ def member_hparams_for(acfg) -> dict:
     return {"lr": float(acfg.lr), "discount": float(acfg.discount), "tau": float(acfg.tau)}
 
 
+def collect_number(step: int, mr: ModelRolloutConfig) -> int:
+    """Which collect of its group the one after update ``step`` (a multiple of ``mr.interval``,
+    at least ``mr.warmup``) is, from 0: k - k0 with step = k * interval and k0 the first
+    multiple that collects.  The running count of a group that trains in lock step."""
+    first = max(1, -(-mr.warmup // mr.interval))
+    return step // mr.interval - first
+
+
 class Trainer:
     _clones = False  # (DistributedTrainer refuses cloning strategies)
 
@@ -125,8 +133,9 @@ class Trainer:
             pop.set_dataset(dd["val"], "val")
         self._free_slots = list(range(len(configs)))
         if self.model_rollouts.enabled:
-            # the rings start empty, on a resumed run too (they are not checkpointed): until a
-            # member's first collect its minibatches are offline rows only
+            # the rings start empty: until a member's first collect its minibatches are offline
+            # rows only.  On a resumed run each Experiment puts its member's ring back from its
+            # state dict ("synth_ring"), so the run continues as if it had not stopped
             self.task.attach(pop)
             pop.synth_create(self.model_rollouts.buffer_rows)
             pop.set_real_ratio(self.model_rollouts.real_ratio)
@@ -195,7 +204,14 @@ class Trainer:
         ``model_rollouts.interval``; after each such chunk, from ``warmup`` updates on, every
         member of the group rolls its branches into its ring (one ``Population.collect``,
         stream-ordered between the steps: no synchronisation).  The collect after the run's
-        last update is skipped: nothing would train on it."""
+        last update is skipped: nothing would train on it.
+
+        A collect is seeded by the update it follows: the one after update k * interval is
+        number k - k0 of its group, k0 the first multiple that collects.  While all candidates
+        train in lock step that is the running ``collect_index``; a candidate that
+        ``max_evaluations`` defers to a later round or invocation gets the seeds it would have
+        had in lock step, so a run does not depend on how it was cut into invocations.
+        ``collect_index`` still counts the collects done (it is saved with the state)."""
         mr = self.model_rollouts
         cur, target = exps[0].current_step, exps[0].current_step + n
         while cur < target:
@@ -203,7 +219,8 @@ class Trainer:
             train_population(exps, nxt - cur)  # (leaves exactly this group active)
             cur = nxt
             if cur % mr.interval == 0 and cur >= mr.warmup and cur < self.config.steps:
-                self.population.collect(mr.branches, mr.horizon, D.collect_seed(self.config.seed, self.collect_index),
+                self.population.collect(mr.branches, mr.horizon,
+                                        D.collect_seed(self.config.seed, collect_number(cur, mr)),
                                         ensemble=mr.ensemble, penalty=mr.penalty)
                 self.collect_index += 1
 

@@ -505,6 +505,34 @@ int fqlpop_synth_read(fqlpop_t* h, int member, float* obs, float* act, float* re
  * fqlpop_clone_members gives dst[i] a copy of src[i]'s ring and counters. */
 int fqlpop_synth_clear(fqlpop_t* h, int member);
 
+/* The inverse of fqlpop_synth_read plus fqlpop_synth_info, for checkpoints: ring positions
+ * 0 .. n - 1 of one member become the host rows obs [n][obs_dim], act [n][action_dim], rew [n],
+ * mask [n], next_obs [n][obs_dim], and its counters rows = n, head = appended mod capacity,
+ * appended = appended.  Every ring the engine builds has rows = min(capacity, appended) and
+ * head = appended mod capacity, so n must equal min(capacity, appended); n = 0, appended = 0 is
+ * fqlpop_synth_clear(member).  The member need not be active.  Stream-ordered on the stream the
+ * steps, collects and clones run on: work enqueued earlier sees the old ring, later work the new
+ * one, the replay of a captured step graph included (no graph is dropped).  The rows are staged
+ * in host memory of the handle's: the arrays may be reused when the call returns, which may be
+ * before the ring is written (fqlpop_sync waits).  Before any GPU work, with nothing changed:
+ * FQLPOP_E_STATE without rings; FQLPOP_E_ARG for a null handle, a member out of range, a null
+ * array with n > 0, n < 0 or n > capacity, appended < n or n != min(capacity, appended).
+ * [no reference counterpart] */
+int fqlpop_synth_write(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
+                       const float* mask, const float* next_obs, int64_t n, int64_t appended);
+
+/* Appends n host rows (arrays as fqlpop_synth_write's) to one member's ring by
+ * fqlpop_synth_collect's "order" rule with the host rows in place of the branch transitions:
+ * row i goes to position (head + i) mod capacity; then head advances by n, rows = min(capacity,
+ * rows + n) and appended += n.  The placement reads head from the device counters, so an append
+ * enqueued behind a collect lands behind that collect's rows without a host round trip.  This
+ * is how observed transitions of an environment of the caller's reach a ring (FQL's
+ * offline-to-online setting).  0 <= n <= capacity; n = 0 succeeds and does nothing.  Member,
+ * stream order, graphs, staging and the errors are fqlpop_synth_write's (without those on
+ * appended).  [no reference counterpart] */
+int fqlpop_synth_append(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
+                        const float* mask, const float* next_obs, int64_t n);
+
 /* ---------------------------------------------------------------------------
  * Env-model trainer: the reference's world-model
  * trainers, one fused GPU step per train_step.
