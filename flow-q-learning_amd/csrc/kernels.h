@@ -65,7 +65,8 @@ struct AdamArgs {
     const float* p_in;            // parameters read (current buffer, slot stride P)
     float* p_out;                 // parameters written (the other buffer of the pair)
     float *g, *m, *v;             // arenas (slot stride P)
-    float* target;                // target arena (slot stride PT) or null
+    const float* target;          // target arena read (slot stride PT) or null
+    float* target_out;            // target arena written (the other buffer of the pair)
     long long P, PT;
     long long net_off;            // offset of this net inside the params arena
     const Chunk* chunks;          // chunk table of ALL nets (index = stats chunk id)
@@ -85,12 +86,14 @@ struct AdamArgs {
 // the streamed backward reads (hidden layers), and the tile's grad stats
 // (max, min, sum g^2) at chunk id stat_base[gi] + y * tiles_per_problem + tile.
 struct AdamEpi {
-    const float* p_in;
-    float *p_out, *m, *v, *target, *wt_out;
+    const float *p_in, *target;       // (target: the buffer read, or null)
+    float *p_out, *m, *v, *target_out, *wt_out;
     long long P, PT, PTT;             // slot strides of params / target / W^T arenas
     long long ens, wt_sy;             // ensemble strides in params and W^T
     long long w_off[GEMM_GROUP_MAX];  // leaf offset inside a params slot (net offset included)
-    long long wt_off[GEMM_GROUP_MAX]; // offset inside a W^T slot, -1 = no copy
+    long long wt_off[GEMM_GROUP_MAX]; // offset inside a W^T slot, -1 = no copy (none needed, or the
+                                      // net's forward wrote it: StreamArgs::wt_out)
+    int no_ema[GEMM_GROUP_MAX];       // the target forward wrote this leaf's EMA (StreamArgs::ema_out)
     int stat_base[GEMM_GROUP_MAX];
     float* stats;                     // [slots][n_total_chunks][3]
     int n_total_chunks;
@@ -192,6 +195,15 @@ struct StreamArgs {
     HeadArgs head;                        // head outputs (head.M/.ld unused)
     int ny, nz;
     const int* slots;
+    // Copies derived from the hidden kernels W_l (l >= 1) this launch streams anyway (train-step
+    // launches of the unsplit kernel; null: none).  Column tile t < min(tiles, 16) owns the ring
+    // passes q (rows [32q, 32q + 32) of every W_l) with q mod min(tiles, 16) == t.
+    float* wt_out;                        // W_l^T [out][in] at + slot*wt_ss + y*wt_sy + (l-1) H H: the
+    long long wt_ss, wt_sy;               //   copy this step's streamed backward reads
+    float* ema_out;                       // target forward: ema_target(ema_src, params, tau) at the
+    const float* ema_src;                 //   offsets of W_l in the other target buffer (slot stride P);
+    long long ema_ss;                     //   ema_src = the current critic (slot stride ema_ss)
+    const float* hparams;                 // [slots][HP_COUNT]: tau
 };
 bool stream_fwd_supported(int H, int L, int K0, int nout, int M);
 void launch_stream_fwd(int head_mode, bool ln, const StreamArgs& a, hipStream_t s);

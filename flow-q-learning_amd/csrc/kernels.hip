@@ -205,7 +205,8 @@ DEV void adam_chunk_t(const AdamArgs& a, int bx, int z) {
         const float* __restrict__ G = a.g + base;
         float* __restrict__ Mm = a.m + base;
         float* __restrict__ V = a.v + base;
-        float* __restrict__ T = hasT ? a.target + (long long)slot * a.PT + ck.off : nullptr;
+        const float* __restrict__ T = hasT ? a.target + (long long)slot * a.PT + ck.off : nullptr;
+        float* __restrict__ To = hasT ? a.target_out + (long long)slot * a.PT + ck.off : nullptr;
         auto one = [&](float g, float& p, float& m, float& v, float& tp) {
             adam_moments(g, m, v);
             if (hasT) tp = ema_target(p, tp, tau);
@@ -221,7 +222,7 @@ DEV void adam_chunk_t(const AdamArgs& a, int bx, int z) {
                 float4 m4 = *reinterpret_cast<float4*>(Mm + i);
                 float4 v4 = *reinterpret_cast<float4*>(V + i);
                 float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (hasT) t4 = *reinterpret_cast<float4*>(T + i);
+                if (hasT) t4 = *reinterpret_cast<const float4*>(T + i);
                 one(g4.x, p4.x, m4.x, v4.x, t4.x);
                 one(g4.y, p4.y, m4.y, v4.y, t4.y);
                 one(g4.z, p4.z, m4.z, v4.z, t4.z);
@@ -229,7 +230,7 @@ DEV void adam_chunk_t(const AdamArgs& a, int bx, int z) {
                 *reinterpret_cast<float4*>(P + i) = p4;
                 *reinterpret_cast<float4*>(Mm + i) = m4;
                 *reinterpret_cast<float4*>(V + i) = v4;
-                if (hasT) *reinterpret_cast<float4*>(T + i) = t4;
+                if (hasT) *reinterpret_cast<float4*>(To + i) = t4;
             }
         } else {
             for (int i = threadIdx.x; i < ck.len; i += 256) {
@@ -239,7 +240,7 @@ DEV void adam_chunk_t(const AdamArgs& a, int bx, int z) {
                 P[i] = p;
                 Mm[i] = m;
                 V[i] = v;
-                if (hasT) T[i] = tv;
+                if (hasT) To[i] = tv;
             }
         }
     }
@@ -411,7 +412,7 @@ DEV void adam_issue0(const AdamEpi& e, int gi, const GemmArgs& g, int slot, int 
     const long long nleaf = (long long)gM * ldc;
     const rsrc_t rP = make_rsrc(e.p_in + pb, nleaf);
     const rsrc_t rM = make_rsrc(e.m + pb, nleaf), rV = make_rsrc(e.v + pb, nleaf);
-    const bool hasT = e.target != nullptr;
+    const bool hasT = e.target != nullptr && !uni(e.no_ema[gi]);
     const rsrc_t rT = make_rsrc(uniptr(hasT ? e.target + (long long)slot * e.PT + e.w_off[gi] + (long long)y * e.ens
                                             : e.m + pb), nleaf);
     const int cj = (tid % TPR) * 4, ri = tid / TPR;
@@ -441,9 +442,10 @@ DEV void adam_epilogue(const AdamEpi& e, int gi, const GemmArgs& g, f32x16 (&acc
     const rsrc_t rP = make_rsrc(e.p_in + pb, nleaf), rPo = make_rsrc(e.p_out + pb, nleaf);
     const rsrc_t rM = make_rsrc(e.m + pb, nleaf), rV = make_rsrc(e.v + pb, nleaf);
     // the target arena mirrors the critic block, which sits at arena offset 0
-    const bool hasT = e.target != nullptr;
-    const rsrc_t rT = make_rsrc(uniptr(hasT ? e.target + (long long)slot * e.PT + e.w_off[gi] + (long long)y * e.ens
-                                            : e.m + pb), nleaf);
+    const bool hasT = e.target != nullptr && !uni(e.no_ema[gi]);
+    const long long tb = uni64((long long)slot * e.PT + e.w_off[gi] + (long long)y * e.ens);
+    const rsrc_t rT = make_rsrc(uniptr(hasT ? e.target + tb : e.m + pb), nleaf);
+    const rsrc_t rTo = make_rsrc(uniptr(hasT ? e.target_out + tb : e.m + pb), nleaf);
     const float t = (float)(e.count[slot] + 1);
     const float bc1 = 1.0f - powf(0.9f, t), bc2 = 1.0f - powf(0.999f, t);
     const float rbc1 = 1.0f / bc1, rbc2 = 1.0f / bc2;
@@ -523,7 +525,7 @@ DEV void adam_epilogue(const AdamEpi& e, int gi, const GemmArgs& g, f32x16 (&acc
                 bstore4_aux(rPo, float4{pp[0], pp[1], pp[2], pp[3]}, off, 0);
                 bstore4_aux(rM, float4{mm[0], mm[1], mm[2], mm[3]}, off, 1);
                 bstore4_aux(rV, float4{vv[0], vv[1], vv[2], vv[3]}, off, 1);
-                if (hasT) bstore4_aux(rT, float4{tt[0], tt[1], tt[2], tt[3]}, off, 1);
+                if (hasT) bstore4_aux(rTo, float4{tt[0], tt[1], tt[2], tt[3]}, off, 1);
             }
         }
     }
@@ -1536,6 +1538,67 @@ bool stream_fwd_supported(int H, int L, int K0, int nout, int M) {
     return H == EF_H && L >= 1 && L <= EF_MAX_LAYERS && K0 <= EF_K0MAX && nout <= 8 && M % EF_NC == 0;
 }
 
+// 4x4 transpose over the lk lanes (lane = 16 lk + li): a = (M[lk][0..3]) becomes (M[0..3][lk])
+DEV void lk_transpose(float4& a) {
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a.x), "+v"(a.y));
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a.z), "+v"(a.w));
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a.x), "+v"(a.z));
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a.y), "+v"(a.w));
+}
+
+// The copies of hidden kernel W_l (l >= 1) that an owning block of a train-step forward writes
+// (StreamArgs::wt_out / ema_out), before the layer's k-loop: the ring passes q = tile, tile + own,
+// .. < 16, each 8 k-steps (W rows [32q, 32q + 32)) loaded with the k-loop's own addressing, 4
+// fragments at a time.  W^T: after lk_transpose lane (lk, li) holds W[4s .. 4s+3][64w + 4li + lk],
+// a float4 of W^T row 64w + 4li + lk; a pass gives every such row 128 contiguous bytes.  EMA:
+// ema_target of the critic's fragment at the same offset, stored at that offset.
+DEV void fwd_copies(const StreamArgs& g, rsrc_t rW, int wcur, int lo, int l, int tile, int own, int slot, int y,
+                    int w, int lk, int li) {
+    constexpr int H = EF_H;
+    const bool ema = g.ema_out != nullptr;
+    const long long mo = (long long)slot * g.P + (long long)y * g.ens;
+    // W^T of this (slot, ensemble member, layer); EMA: the member's block of the two arenas
+    const rsrc_t rO = ema ? make_rsrc(g.ema_out + mo, g.ens)
+                          : make_rsrc(g.wt_out + (long long)slot * g.wt_ss + (long long)y * g.wt_sy +
+                                          (long long)(l - 1) * H * H, (long long)H * H);
+    const rsrc_t rC = make_rsrc(ema ? g.ema_src + (long long)slot * g.ema_ss + (long long)y * g.ens : g.params, ema ? g.ens : 0);
+    const float tau = ema ? uni_load(g.hparams + (long long)slot * HP_COUNT + HP_TAU) : 0.f;
+    // this lane's W^T row 64w + 4li + lk, from lo = lk H + 64w + 4li (opaque: recomputed here,
+    // not kept in a register across the layers)
+    int lo_ = lo;
+    asm volatile("" : "+v"(lo_));
+    const int to = ((lo_ & (H - 1)) + lo_ / H) * H;
+    // (CH fragments in flight and loops not unrolled: the kernel's register count stays what its
+    // epilogue takes.  Two in flight, or a loop per kind of copy, cost the LN variants 1-2 VGPRs.)
+    constexpr int CH = 1;
+#pragma unroll 1
+    for (int q = tile; q < H / 32; q += own) {
+#pragma unroll 1
+        for (int s0 = 8 * q; s0 < 8 * q + 8; s0 += CH) {
+            float4 a[CH], c[CH];
+#pragma unroll
+            for (int p = 0; p < CH; ++p) a[p] = bload4(rW, wcur + 4 * (s0 + p) * H + lo);
+            if (ema) {
+#pragma unroll
+                for (int p = 0; p < CH; ++p) c[p] = bload4(rC, wcur + 4 * (s0 + p) * H + lo);
+#pragma unroll
+                for (int p = 0; p < CH; ++p) {
+                    const float4 t = a[p];
+                    const float4 r{ema_target(c[p].x, t.x, tau), ema_target(c[p].y, t.y, tau),
+                                   ema_target(c[p].z, t.z, tau), ema_target(c[p].w, t.w, tau)};
+                    bstore4_aux(rO, r, (wcur + 4 * (s0 + p) * H + lo) * 4, 0);
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < CH; ++p) {
+                    lk_transpose(a[p]);
+                    bstore4_aux(rO, a[p], (to + 4 * (s0 + p)) * 4, 0);
+                }
+            }
+        }
+    }
+}
+
 template <int MODE, bool LN>
 __global__ __launch_bounds__(EF_NW * 64, 1) void stream_fwd_kernel(const StreamArgs g) {
     constexpr int H = EF_H, NC = EF_NC, NT = EF_NW * 64, PF = EF_PF;
@@ -1567,6 +1630,8 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void stream_fwd_kernel(const StreamA
     for (int p = 0; p < PF; ++p) ring[p] = bload4(rW, (int)g.w_off[0] + 4 * p * H + lo);
     const bool st = c0 >= g.st_lo && c0 + NC <= g.st_hi;  // block stores activations
     const int m = c0 + li;
+    const bool copies = g.wt_out != nullptr || g.ema_out != nullptr;
+    const int own = tiles < H / 32 ? tiles : H / 32;  // column tiles that own ring passes (fwd_copies)
     if constexpr (LN) {
         // LN variant: layer l's bias / LN scale / LN bias are staged one layer ahead (see below)
         lnp[0][tid] = P[g.b_off[0] + tid];
@@ -1592,6 +1657,8 @@ __global__ __launch_bounds__(EF_NW * 64, 1) void stream_fwd_kernel(const StreamA
         const float pg = LN ? P[g.g_off[lp] + tid] : 0.f;
         const float pe = LN ? P[g.be_off[lp] + tid] : 0.f;
         const int wcur = (int)g.w_off[l], wnext = (int)g.w_off[nl];
+        // train-step launches: this block's share of W_l^T / of the target EMA (block-uniform test)
+        if (l >= 1 && copies && tile < own) fwd_copies(g, rW, wcur, lo, l, tile, own, slot, y, w, lk, li);
         asm volatile("" ::"s"(wcur), "s"(wnext));  // no SMEM load in flight into the k-loop (see euler_flow_kernel)
         const float4 at0 = bload4(rW, wcur + 4 * PF * H + lo);  // layer 0's tail k-step (l > 0: unused)
         ef_kloop(acc, ring, rW, xs, NS, wcur, wnext, lo, lk, li);

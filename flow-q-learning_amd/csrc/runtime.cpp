@@ -75,6 +75,11 @@ struct EngineOptions {
     int lazy_metric = 1;   // the metrics-only third of the one-step actor forward (the mse info value) is
                            // evaluated when the train info is read, not in every step (materialise_metric;
                            // bit-identical); 0 = in the step.  With the streamed forward only (stream_fwd).
+    int fwd_copies = 2;    // bit mask: the train step's unsplit streamed forwards write 1 = the W^T copies of
+                           // the hidden kernels they stream (BC, one-step, critic), 2 = the target EMA of
+                           // those kernels (target forward), and the fused optimiser epilogue leaves them out
+                           // (bit-identical); with stream_fwd, stream_bwd and fused_adam only.  Default 2:
+                           // the EMA half measured +1.9 %, the W^T half -4 %
 };
 // (Schedule experiments that measured slower were removed in round 4 and stay in git history
 // and DESIGN.md section 5: a 4th stream, stream priorities, the critic optimiser on the main
@@ -113,6 +118,7 @@ const EngineOptionRef kEngineOptions[] = {
     {"em_seq_sweep", &EngineOptions::em_seq_sweep, 0, 1},
     {"em_ens_xcd", &EngineOptions::em_ens_xcd, 0, 1},
     {"lazy_metric", &EngineOptions::lazy_metric, 0, 1},
+    {"fwd_copies", &EngineOptions::fwd_copies, 0, 3},
 };
 
 // ---------------------------------------------------------------- host Philox
@@ -259,8 +265,11 @@ struct fqlpop : StepStreams<> {
     Buf paramsT_buf[2];
     int cur = 0;
     float *params = nullptr, *params_nx = nullptr;  // views of params_buf: current / next
-    DevBuf<float> grads, adam_m, adam_v, target_buf;
-    float* target = nullptr;  // view of target_buf (Net::arena points at it, as at params)
+    DevBuf<float> grads, adam_m, adam_v, target_buf[2];
+    // the target critic is double-buffered with the parameters (target_buf[cur] is current): a
+    // train step reads `target` and writes every leaf of `target_nx`
+    float *target = nullptr, *target_nx = nullptr;  // (Net::arena points at target, as at params)
+    int fwd_copies = 0;  // engine option fwd_copies (0 without the streamed / fused paths it needs)
     DevBuf<int> count;
     DevBuf<uint64_t> seeds;
     DevBuf<uint64_t> skeys;  // per-member sampler key: sample_key(seed, alpha)
@@ -541,12 +550,14 @@ void build_chunks(fqlpop* h) {
 }
 
 // ------------------------------------------------------------- params init
-// Copy a slot's current parameters into the other buffer of the pair (after a
+// Copy a slot's current parameters and target into the other buffer of each pair (after a
 // host-side write, or for a member that stops stepping: both buffers must hold
 // its parameters whichever one is current when it steps again).
 void mirror_params(fqlpop* h, int slot, hipStream_t s) {
     HIPCHK(hipMemcpyAsync(h->params_nx + (long long)slot * h->P, h->params + (long long)slot * h->P,
                           sizeof(float) * h->P, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->target_nx + (long long)slot * h->PT, h->target + (long long)slot * h->PT,
+                          sizeof(float) * h->PT, hipMemcpyDeviceToDevice, s));
 }
 
 void upload_skey(fqlpop* h, int member) {
@@ -875,6 +886,7 @@ void bwd_net(const Ctx& c, hipStream_t s, const Net& n, const BwdCols& k, TRef d
 }
 
 AdamArgs adam_args(const Ctx& c, int ni);
+bool fwd_writes(const Ctx& c, const Net& n, int bit);
 int skip_mask();
 
 // Whole-network backward of `n` (stream_bwd_kernel) on `s`: dX chain from the
@@ -974,14 +986,20 @@ void stream_bwd_net(const Ctx& c, hipStream_t s, const Net& n, const BwdCols& k,
         AdamEpi ae{};
         ae.p_in = h->params; ae.p_out = h->params_nx; ae.m = h->adam_m; ae.v = h->adam_v;
         ae.target = ni == 0 ? h->target : nullptr;
+        ae.target_out = h->target_nx;
         ae.wt_out = h->paramsT_nx.p;
+        // copies this step's / the next step's forwards write (engine option fwd_copies): the
+        // target EMA of the hidden kernels, and the W^T the next step's backward reads
+        const bool ema_fwd = ni == 0 && fwd_writes(c, h->n_tg, 2);
+        const bool wt_fwd = fwd_writes(c, ni == 0 ? h->n_cr : ni == 1 ? h->n_bc : h->n_os, 1);
         ae.P = h->P; ae.PT = h->PT; ae.PTT = h->paramsT_nx.ss;
         ae.ens = N.ens_size;
         ae.wt_sy = (long long)(N.L - 1) * N.H * N.H;
         for (int gi = 0; gi < (int)gs.size(); ++gi) {
             const int l = N.L - 1 - gi;
             ae.w_off[gi] = N.off + N.W[l];
-            ae.wt_off[gi] = l >= 1 ? h->wt_net_off[ni] + (long long)(l - 1) * N.H * N.H : -1;
+            ae.wt_off[gi] = l >= 1 && !wt_fwd ? h->wt_net_off[ni] + (long long)(l - 1) * N.H * N.H : -1;
+            ae.no_ema[gi] = l >= 1 && ema_fwd ? 1 : 0;
             ae.stat_base[gi] = h->w_stat_base[ni][l];
         }
         ae.stats = h->stats; ae.n_total_chunks = h->n_chunks_total;
@@ -1046,6 +1064,7 @@ AdamArgs adam_args(const Ctx& c, int ni) {
     a.p_in = h->params; a.p_out = h->params_nx;
     a.g = h->grads; a.m = h->adam_m; a.v = h->adam_v;
     a.target = ni == 0 ? h->target : nullptr;
+    a.target_out = h->target_nx;
     a.P = h->P; a.PT = h->PT;
     a.net_off = nets[ni]->off;
     a.chunks = h->chunks;
@@ -1072,6 +1091,15 @@ void adam_net(const Ctx& c, hipStream_t s, int ni) {
     if (a.n_chunks > 0) launch_adam(a, s);
 }
 
+// Engine option fwd_copies: does the train step's forward of `n` write the copies of `bit` (1:
+// W^T of its hidden kernels into the current paramsT; 2, the target critic: their EMA into
+// target_nx)?  Unsplit launch sites only; the fused optimiser then leaves those copies out, so
+// both sides decide here.  The plan changes only with the active count (fqlpop_set_active,
+// which marks W^T dirty); every step writes all of target_nx either way.
+bool fwd_writes(const Ctx& c, const Net& n, int bit) {
+    return (c.h->fwd_copies & bit) != 0 && n.lay->L > 1 && c.plan.F[n.fwd_site] <= 1;
+}
+
 // Columns of a streamed forward: [st_lo, st_hi) keep their activations (U, G, MU / RS) for
 // the backward pass, the layer outputs G only up to g_hi (default st_hi).  An empty range
 // stores nothing (the target critic).  The launch runs the M columns of the input from column
@@ -1083,7 +1111,9 @@ struct FwdCols {
 };
 
 // One whole-network forward launch (stream_fwd_kernel) of `n` over the columns `k` of its input.
-void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int mode, const HeadArgs& head) {
+// `copies`: a train step's launch, which also writes the copies of fwd_writes.
+void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int mode, const HeadArgs& head,
+                bool copies = false) {
     fqlpop* h = c.h;
     const NetLayout& N = *n.lay;
     const bool store = k.st_hi > k.st_lo, stats = store && !n.MU.empty();
@@ -1117,6 +1147,16 @@ void stream_fwd(const Ctx& c, hipStream_t s, const Net& n, const FwdCols& k, int
     a.head = head;
     a.head.nout = N.out_dim;
     a.ny = N.E; a.nz = c.nz; a.slots = h->slots;
+    if (copies && n.arena == &h->target) {
+        if (fwd_writes(c, n, 2)) {
+            a.ema_out = h->target_nx + N.off;
+            a.ema_src = h->params + N.off; a.ema_ss = h->P;
+            a.hparams = h->hparams;
+        }
+    } else if (copies && fwd_writes(c, n, 1)) {
+        a.wt_out = h->paramsT.p + h->wt_net_off[n.ni];
+        a.wt_ss = h->paramsT.ss; a.wt_sy = (long long)(N.L - 1) * N.H * N.H;
+    }
     if (skip_mask() & n.skip_fwd) return;
     const int F = c.plan.F[n.fwd_site];
     if (F > 1) {
@@ -1391,7 +1431,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         ha.o3 = h->amet.ref(); ha.ld3 = B;
         if (h->stream_fwd) {
             // only the z_d rows [B, 2B) are back-propagated (distill + Q loss)
-            stream_fwd(c, sM, h->n_os, FwdCols{B, 2 * B, -1, 0, lazy ? B2 : 3 * B}, HEAD_OS, ha);
+            stream_fwd(c, sM, h->n_os, FwdCols{B, 2 * B, -1, 0, lazy ? B2 : 3 * B}, HEAD_OS, ha, train);
         } else {
             fwd_hidden(c, sM, h->n_os);
             launch_head_fwd(HEAD_OS, ha, sM);
@@ -1441,7 +1481,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         ha.t_next = (float)(1.0 / (double)S);
         if (h->stream_fwd) {
             // train rows [0, B) feed the BC backward; rows [B, 2B) are Euler step 0
-            stream_fwd(c, sF, h->n_bc, FwdCols{0, B}, HEAD_BC_FUSED, ha);
+            stream_fwd(c, sF, h->n_bc, FwdCols{0, B}, HEAD_BC_FUSED, ha, train);
         } else {
             fwd_hidden(c, sF, h->n_bc);
             launch_head_fwd(HEAD_BC_FUSED, ha, sF);
@@ -1500,7 +1540,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         HeadArgs ht{};
         ht.B = B; ht.D = D; ht.steps_f = (float)S;
         ht.o0 = h->qt.ref(B); ht.ld0 = B;
-        stream_fwd(c, sT, h->n_tg, FwdCols{0, 0}, HEAD_STORE, ht);
+        stream_fwd(c, sT, h->n_tg, FwdCols{0, 0}, HEAD_STORE, ht, train);
     } else {
         fwd_hidden(c, sT, h->n_tg);
         HeadArgs ht = head_args(c, h->n_tg);
@@ -1514,7 +1554,7 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
         if (h->stream_fwd) {
             // the a_pi columns [B, 2B) are back-propagated for dQ/da only: their layer outputs
             // (the dW GEMMs' operand) are not needed by the streamed backward
-            stream_fwd(c, sM, h->n_cr, FwdCols{0, B2, h->stream_bwd ? B : B2}, HEAD_STORE, hc);
+            stream_fwd(c, sM, h->n_cr, FwdCols{0, B2, h->stream_bwd ? B : B2}, HEAD_STORE, hc, train);
         } else {
             fwd_hidden(c, sM, h->n_cr);
             launch_head_fwd(HEAD_STORE, hc, sM);
@@ -1594,13 +1634,15 @@ void enqueue(fqlpop* h, bool train, bool inj_batch, bool inj_noise) {
     HIPCHK(hipGetLastError());
 }
 
-// Swap the parameter buffer pairs after a train step was enqueued.
+// Swap the parameter and target buffer pairs after a train step was enqueued.
 void flip_params(fqlpop* h) {
     h->cur ^= 1;
     h->params = h->params_buf[h->cur];
     h->params_nx = h->params_buf[h->cur ^ 1];
     h->paramsT = h->paramsT_buf[h->cur];
     h->paramsT_nx = h->paramsT_buf[h->cur ^ 1];
+    h->target = h->target_buf[h->cur];
+    h->target_nx = h->target_buf[h->cur ^ 1];
 }
 
 Graphs& graph_for(fqlpop* h, bool train, bool inj_batch, bool inj_noise, bool recapture);
@@ -1989,6 +2031,7 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         h->lazy_metric = h->stream_fwd && eo.lazy_metric;  // (the per-layer forward runs all 3B columns)
         // Adam / EMA / W^T / grad stats fused into the grouped dW epilogue
         h->fused_adam = h->stream_bwd && H % 128 == 0 && L <= GEMM_GROUP_MAX && h->critic.off == 0 && eo.fused_adam;
+        h->fwd_copies = h->stream_fwd && h->fused_adam ? eo.fwd_copies : 0;
         if (h->euler_fused) {  // dominant kernel: one persistent Euler launch per step
             h->probe_pairs = 1;
             // (the split Euler launch: up to 8 blocks per 16-column tile)
@@ -2041,8 +2084,9 @@ int fqlpop_create(const fqlpop_config* cfg, int n_members, const float* alphas, 
         h->grads = DevBuf<float>(Pn, "gradients");
         h->adam_m = DevBuf<float>(Pn, "Adam first moments");
         h->adam_v = DevBuf<float>(Pn, "Adam second moments");
-        h->target_buf = DevBuf<float>((size_t)h->PT * n, "target critic");
-        h->target = h->target_buf;
+        for (auto& tb : h->target_buf) tb = DevBuf<float>((size_t)h->PT * n, "target critic");
+        h->target = h->target_buf[0];
+        h->target_nx = h->target_buf[1];
         HIPCHK(hipMemset(h->grads, 0, sizeof(float) * Pn));
         h->count = DevBuf<int>(n, "step counts");
         h->seeds = DevBuf<uint64_t>(n, "member seeds");
@@ -2241,7 +2285,7 @@ int fqlpop_set_active(fqlpop_t* h, const uint8_t* mask) {
         materialise_metric(h);
         for (int i = 0; i < h->n; ++i) h->active[i] = mask[i] ? 1 : 0;
         update_slots(h);
-        // a member that does not step keeps its parameters in both buffers
+        // a member that does not step keeps its parameters and its target in both buffers
         for (int i = 0; i < h->n; ++i)
             if (!h->active[i]) mirror_params(h, i, h->sM);
         HIPCHK(hipStreamSynchronize(h->sM));
@@ -2450,7 +2494,7 @@ static void state_copy(fqlpop* h, int member, int which, float* flat, const floa
         if (which == 0) {
             HIPCHK(hipMemcpy(h->target + (long long)member * h->PT, tblk.data(), sizeof(float) * h->PT,
                              hipMemcpyHostToDevice));
-            mirror_params(h, member, h->sM);
+            mirror_params(h, member, h->sM);  // (and the target)
             HIPCHK(hipStreamSynchronize(h->sM));
         }
         note_restored(h, member, which);
@@ -2544,7 +2588,7 @@ int fqlpop_get_member_hparams(fqlpop_t* h, int member, float* hp) {
 }
 
 // Per-slot buffers of struct fqlpop and what the clone does with them:
-//   copied   params_buf[0/1], paramsT_buf[0/1], target, adam_m, adam_v, count, hparams (and
+//   copied   params_buf[0/1], paramsT_buf[0/1], target_buf[0/1], adam_m, adam_v, count, hparams (and
 //            its mirror h_hparams); the member's
 //            synthetic-transition ring and its counters (synth, when created: its own launch);
 //   written  alpha, seeds, skeys (the values given for dst), h_alpha / h_seeds;
@@ -2593,6 +2637,7 @@ int fqlpop_clone_members(fqlpop_t* h, int n_pairs, const int* src, const int* ds
             arena(h->paramsT_nx.p, h->paramsT.p, h->paramsT_nx.p, h->paramsT_nx.ss);
         }
         arena(h->target, h->target, h->target, h->PT);
+        arena(h->target_nx, h->target, h->target_nx, h->PT);
         arena(h->adam_m, h->adam_m, h->adam_m, h->P);
         arena(h->adam_v, h->adam_v, h->adam_v, h->P);
         base.count = h->count; base.alpha = h->alpha; base.hparams = h->hparams; base.seed = h->seeds; base.skey = h->skeys;

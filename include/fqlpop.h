@@ -103,6 +103,11 @@ const char* fqlpop_last_error(void);
  *   overwrite what the evaluation reads (fqlpop_set_state, _set_member with reinit,
  *   _set_active, _clone_members, _step_injected, _total_loss).  Bit-identical to 0, which
  *   evaluates it in every step.  Takes effect with the streamed forward (stream_fwd).
+ *   fwd_copies (bit mask 0..3, default 2): in a train step the unsplit streamed forwards
+ *   write 1 = the W^T copies of the hidden kernels that the step's streamed backward reads
+ *   (BC, one-step and critic forwards), 2 = the target EMA of the critic's hidden kernels
+ *   (target forward), and the fused optimiser leaves those copies out.  Bit-identical to 0,
+ *   where the optimiser writes both.  Takes effect with stream_fwd, stream_bwd, fused_adam.
  * The defaults are the measured-fastest configuration.  Unknown names or values
  * out of range: FQLPOP_E_ARG.  (Round 3's schedule experiments that measured slower --
  * streams, prio, cdw_sb, dw_stagger, xstep, bc_late, fuse_dq, early_join -- were
