@@ -8,7 +8,7 @@ import argparse
 from ast import literal_eval
 from pathlib import Path
 
-from trainer.config import AgentConfig, ModelRolloutConfig, TrainerConfig
+from trainer.config import AgentConfig, ModelRolloutConfig, OnlineConfig, TrainerConfig
 
 
 def get_argparser() -> argparse.ArgumentParser:
@@ -55,7 +55,19 @@ def get_argparser() -> argparse.ArgumentParser:
     # penalty x the ensemble's disagreement
     p.add_argument("--model_rollout_ensemble", action="store_true")
     p.add_argument("--model_rollout_penalty", type=float, default=0.0)
+    # offline-to-online fine-tuning (trainer.config.OnlineConfig): the last --online_steps
+    # updates act in the task's online environments; off while it is 0
+    p.add_argument("--online_steps", type=int, default=0)
+    p.add_argument("--online_envs", type=int, default=8)
+    p.add_argument("--online_utd", type=int, default=1)
+    p.add_argument("--online_buffer_rows", type=int, default=100_000)
+    p.add_argument("--online_real_ratio", type=online_real_ratio, default="auto")
     return p
+
+
+def online_real_ratio(text: str):
+    """--online_real_ratio: "auto" or a number."""
+    return "auto" if text == "auto" else float(text)
 
 
 def build_config_from_args(args: argparse.Namespace) -> TrainerConfig:
@@ -88,6 +100,17 @@ def build_model_rollout_config_from_args(args: argparse.Namespace) -> ModelRollo
         buffer_rows=getattr(args, "model_buffer_rows", d.buffer_rows),
         ensemble=getattr(args, "model_rollout_ensemble", d.ensemble),
         penalty=getattr(args, "model_rollout_penalty", d.penalty))
+
+
+def build_online_config_from_args(args: argparse.Namespace) -> OnlineConfig:
+    """The --online_* flags (a namespace without them: the inert defaults)."""
+    d = OnlineConfig()
+    return OnlineConfig(
+        steps=getattr(args, "online_steps", d.steps),
+        envs=getattr(args, "online_envs", d.envs),
+        utd=getattr(args, "online_utd", d.utd),
+        buffer_rows=getattr(args, "online_buffer_rows", d.buffer_rows),
+        real_ratio=getattr(args, "online_real_ratio", d.real_ratio))
 
 
 def get_env_model_argparser() -> argparse.ArgumentParser:

@@ -435,9 +435,18 @@ struct SynthPutArgs {
     long long n;                  // 0 .. cap
     long long appended;           // write only
     const float *obs, *act, *rew, *mask, *nobs;   // [n][D], [n][A], [n], [n], [n][D]
+    // fqlpop_synth_append_active (write == 0, slot unused): the fields are [nz][n][..] and block
+    // z of each goes to slot slots[z]'s ring.  The single-slot launches read neither.
+    int nz;
+    const int* slots;
 };
 void launch_synth_put(const SynthPutArgs& a, hipStream_t s);
 void launch_synth_put_commit(const SynthPutArgs& a, hipStream_t s);
+// The append of every active member in two launches: block (chunk, field, z) is
+// synth_put_kernel's block of slot slots[z] on member block z of the fields, and thread z of
+// the commit advances that slot's counters by the append's rule.
+void launch_synth_put_active(const SynthPutArgs& a, hipStream_t s);
+void launch_synth_put_commit_active(const SynthPutArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- loss ----
 struct LossArgs {
@@ -573,6 +582,35 @@ struct RolloutArgs : EnvModelNet {
 };
 bool rollout_supported(int H, int L, int D, int A);
 void launch_rollout(const RolloutArgs& a, hipStream_t s);
+
+// fqlpop_act: a = clip(actor_onestep_flow([s, z]), -1, 1) for n_envs observations of every
+// active member, the whole network in one launch.  Grid (member z, 16-column tile of its
+// n_envs columns), 8 waves; layer-0 input [s; z] (K0 = D + A rows, zero-padded to a multiple
+// of 4) and the activations [H][16] stay in LDS (two slabs, written in turn), the weights
+// stream from global memory into v_mfma_f32_16x16x4_f32; bias + GELU epilogue, no LayerNorm.
+// Any hidden width that is a multiple of 64 and any depth: layers 1 .. L-1 share one shape,
+// so their offsets are w1 + (l - 1) * lstride.  z is `noise`, or (noise null) rollout_kernel's
+// policy noise at step t: Philox4x32-10 under seed ^ member key * 0x9E3779B97F4A7C15, counter
+// (env, t, 0x5E11, q), Box-Muller pair q -> actions 2q, 2q + 1.
+struct ActArgs {
+    const float* params;           // population arena (slot stride P), one-step actor at os_off
+    long long P, os_off;
+    long long w0, b0, w1, b1, lstride, wh, bh;   // offsets inside the actor: layer 0, layer 1, head
+    int D, A, H, L;
+    const float* obs;              // [nz][n_envs][D]
+    const float* noise;            // null or [nz][n_envs][A]
+    int n_envs;
+    uint64_t seed;
+    uint32_t t;
+    const uint64_t* member_seeds;  // per slot: the member key sample_key(seed, alpha)
+    float* out;                    // [nz][n_envs][A]
+    float* out_noise;              // null or [nz][n_envs][A]: the z used
+    int nz;
+    const int* slots;
+};
+bool act_supported(int H, int L, int D, int A);
+size_t act_lds_bytes(int H);
+void launch_act(const ActArgs& a, hipStream_t s);
 
 // fqlpop_rollout_ensemble: the rollout above under n_models resident env models of one
 // config (one leaf layout; nets[k] is that layout with model k's parameter pointers).

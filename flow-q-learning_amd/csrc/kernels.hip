@@ -4309,6 +4309,158 @@ void launch_rollout(const RolloutArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(rollout_kernel, grid, dim3(EF_NW * 64), 0, s, a);
 }
 
+// ========================================================= population act ==
+// (ActArgs, kernels.h)  One block = 16 observations (columns) of one active member, the
+// whole one-step actor on LDS-resident activations.  LDS (dynamic): in0 [64][16], the layer-0
+// input [s; z] zero-padded, then the head's per-wave partials; slab[2][H][16], the hidden
+// activations, written in turn: (64 + 2H) * 64 bytes, 132 KB of the 160 KB at H = 1024.
+// A wave owns 64 output features per pass (f0 = 64w, 64w + 512, ...) in euler_flow_kernel's
+// fragment layout: lane (li, lk) loads the float4 W[4s + lk][f0 + 4li .. +3], component c
+// feeds accumulator tile c, so acc[c][r] is feature f0 + 16lk + 4r + c of column li.
+constexpr int ACT_KS = 8;  // k-steps whose W fragments a wave issues together (registers)
+bool act_supported(int H, int L, int D, int A) {
+    return H >= 64 && H <= 1024 && H % 64 == 0 && L >= 1 && D >= 1 && A >= 1 && A <= 8 && D + A <= EF_K0MAX;
+}
+size_t act_lds_bytes(int H) { return sizeof(float) * EF_NC * (size_t)(EF_K0MAX + 2 * H); }
+
+// ys[f][c] = gelu(sum_k W[k][f] xs[k][c] + b[f]), f < H, k < K (xs holds zeros in rows K ..
+// 4 ceil(K / 4) - 1; the W rows loaded for them are row K - 1: finite words times exact zeros).
+DEV void act_layer(rsrc_t rW, int woff, int boff, const float* xs, int K, int H, float* ys, int w, int li, int lk) {
+    constexpr int NC = EF_NC;
+    const int nks = (K + 3) / 4;
+    for (int f0 = 64 * w; f0 < H; f0 += 64 * EF_NW) {
+        f32x4 acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float4 bias4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = bload4(rW, boff + f0 + 16 * lk + 4 * r);
+        // two batches of ACT_KS fragments in turn: one is in flight while the other feeds the
+        // MFMAs (a batch past the last k-step loads row K - 1 again and is not used)
+        auto load = [&](float4 (&wv)[ACT_KS], int s0) {
+#pragma unroll
+            for (int u = 0; u < ACT_KS; ++u)
+                wv[u] = bload4(rW, woff + min(4 * (s0 + u) + lk, K - 1) * H + f0 + 4 * li);
+        };
+        auto mma = [&](const float4 (&wv)[ACT_KS], int s0) {
+#pragma unroll
+            for (int u = 0; u < ACT_KS; ++u) {
+                if (s0 + u < nks) {
+                    const float xv = xs[(4 * (s0 + u) + lk) * NC + li];
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].x, xv, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].y, xv, acc[1], 0, 0, 0);
+                    acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].z, xv, acc[2], 0, 0, 0);
+                    acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].w, xv, acc[3], 0, 0, 0);
+                }
+            }
+        };
+        float4 wa[ACT_KS], wb[ACT_KS];
+        load(wa, 0);
+        for (int s0 = 0; s0 < nks; s0 += 2 * ACT_KS) {
+            load(wb, s0 + ACT_KS);
+            mma(wa, s0);
+            load(wa, s0 + 2 * ACT_KS);
+            mma(wb, s0 + ACT_KS);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float bb[4] = {bias4[r].x, bias4[r].y, bias4[r].z, bias4[r].w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ys[(f0 + 16 * lk + 4 * r + c) * NC + li] = gelu_fast(acc[c][r] + bb[c]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(EF_NW * 64) void act_kernel(const ActArgs g) {
+    constexpr int NC = EF_NC, NT = EF_NW * 64;
+    extern __shared__ __attribute__((aligned(16))) float act_lds[];
+    float* in0 = act_lds;                       // [EF_K0MAX][NC], then the head partials [EF_NW][8][NC]
+    float* slab = act_lds + EF_K0MAX * NC;      // [2][H][NC]
+
+    const int ntile = (g.n_envs + NC - 1) / NC;
+    const int bid = blockIdx.x;
+    const int z = bid / ntile, e0 = (bid % ntile) * NC;
+    const int slot = g.slots[z];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lk = lane >> 4;
+    const int D = g.D, A = g.A, H = g.H, L = g.L, K0 = D + A;
+    const float* __restrict__ P = g.params + (long long)slot * g.P + g.os_off;
+    const rsrc_t rW = make_rsrc(P, g.P - g.os_off);
+
+    // ---- actor input [s; z] ------------------------------------------------
+    for (int e = tid; e < EF_K0MAX * NC; e += NT) {
+        const int k = e / NC, c = e % NC;
+        in0[e] = (k < D && e0 + c < g.n_envs) ? g.obs[((long long)z * g.n_envs + e0 + c) * D + k] : 0.f;
+    }
+    __syncthreads();
+    if (tid < NC * ((A + 1) / 2)) {
+        const int c = tid % NC, q = tid / NC;  // normal pair q: actions 2q, 2q+1
+        float n0, n1;
+        if (g.noise) {
+            const float* nz = g.noise + ((long long)z * g.n_envs + e0 + c) * A;
+            const bool ok = e0 + c < g.n_envs;
+            n0 = ok ? nz[2 * q] : 0.f;
+            n1 = (ok && 2 * q + 1 < A) ? nz[2 * q + 1] : 0.f;
+        } else {  // rollout_kernel's draw, statement for statement
+            const uint64_t key = g.seed ^ (g.member_seeds[slot] * 0x9E3779B97F4A7C15ull);
+            uint32_t cc[4] = {(uint32_t)(e0 + c), g.t, 0x5E11u, (uint32_t)q};
+            philox4x32_10(cc, (uint32_t)key, (uint32_t)(key >> 32));
+            const float r = sqrtf(-2.0f * logf(u01_open_closed(cc[0])));
+            float sv, cv;
+            sincosf(6.283185307179586f * u01(cc[1]), &sv, &cv);
+            n0 = r * cv;
+            n1 = r * sv;
+        }
+        in0[(D + 2 * q) * NC + c] = n0;
+        if (2 * q + 1 < A) in0[(D + 2 * q + 1) * NC + c] = n1;
+    }
+    __syncthreads();
+    if (g.out_noise && tid < A * NC) {
+        const int j = tid / NC, c = tid % NC;
+        if (e0 + c < g.n_envs) g.out_noise[((long long)z * g.n_envs + e0 + c) * A + j] = in0[(D + j) * NC + c];
+    }
+    // ---- hidden layers (streamed weights, GELU) ---------------------------
+    act_layer(rW, (int)g.w0, (int)g.b0, in0, K0, H, slab, w, li, lk);
+    __syncthreads();
+    for (int l = 1; l < L; ++l) {
+        const long long o = (l - 1) * g.lstride;
+        act_layer(rW, (int)(g.w1 + o), (int)(g.b1 + o), slab + ((l - 1) & 1) * H * NC, H, H, slab + (l & 1) * H * NC,
+                  w, li, lk);
+        __syncthreads();
+    }
+    // ---- head: a = clip(W_L^T h + b_L) --------------------------------------
+    const float* hs = slab + ((L - 1) & 1) * H * NC;
+    f32x4 hacc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int s = w; s < H / 4; s += EF_NW) {
+        const int k = 4 * s + lk;
+        const float a = li < A ? P[g.wh + (long long)k * A + li] : 0.f;
+        hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, hs[k * NC + li], hacc, 0, 0, 0);
+    }
+    float* hred = in0;  // (layer 0 has read it; a barrier since)
+    if (lk < 2) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hred[w * 8 * NC + (4 * lk + r) * NC + li] = hacc[r];
+    }
+    __syncthreads();
+    if (tid < A * NC) {
+        const int j = tid / NC, c = tid % NC;
+        float v = hred[tid];
+#pragma unroll
+        for (int q = 1; q < EF_NW; ++q) v += hred[q * 8 * NC + tid];
+        if (e0 + c < g.n_envs) g.out[((long long)z * g.n_envs + e0 + c) * A + j] = clip1(v + P[g.bh + j]);
+    }
+}
+
+void launch_act(const ActArgs& a, hipStream_t s) {
+    if (a.nz <= 0) return;
+    const size_t lds = act_lds_bytes(a.H);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const dim3 grid(((a.n_envs + EF_NC - 1) / EF_NC) * a.nz);
+    hipLaunchKernelGGL(act_kernel, grid, dim3(EF_NW * 64), lds, s, a);
+}
+
 // ============================================ synthetic-transition rings ==
 // (SynthCollectArgs, kernels.h)  fqlpop_synth_collect around rollout_kernel's record mode.
 __global__ __launch_bounds__(256) void synth_starts_kernel(const float* obs, long long n_rows, int D,
@@ -4516,6 +4668,50 @@ __global__ void synth_put_commit_kernel(const SynthPutArgs a) {
 
 void launch_synth_put_commit(const SynthPutArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(synth_put_commit_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
+// fqlpop_synth_append_active: synth_put_kernel's append with a member axis (blockIdx.z).
+__global__ __launch_bounds__(256) void synth_put_active_kernel(const SynthPutArgs a) {
+    const int f = blockIdx.y, z = blockIdx.z;
+    const int slot = a.slots[z];
+    const long long w = (f == 0 || f == 4) ? a.D : (f == 1 ? a.A : 1);
+    const float* field = f == 0 ? a.obs : f == 1 ? a.act : f == 2 ? a.rew : f == 3 ? a.mask : a.nobs;
+    float* ring = f == 0 ? a.ring.obs : f == 1 ? a.ring.act : f == 2 ? a.ring.rew : f == 3 ? a.ring.mask : a.ring.nobs;
+    const long long cap = a.ring.cap;
+    const long long total = a.n * w, span = cap * w;
+    const float* __restrict__ src = field + (long long)z * total;
+    float* __restrict__ dst = ring + (long long)slot * span;
+    const long long base = a.ring.ctr[(long long)slot * SYNTH_CTR + 1];
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+        long long j = base * w + i;
+        if (j >= span) j -= span;
+        dst[j] = src[i];
+    }
+}
+
+void launch_synth_put_active(const SynthPutArgs& a, hipStream_t s) {
+    if (a.n <= 0 || a.nz <= 0) return;
+    long long chunks = (a.n * a.D + 255) / 256;
+    if (chunks > 1024) chunks = 1024;
+    hipLaunchKernelGGL(synth_put_active_kernel, dim3((unsigned)chunks, 5, (unsigned)a.nz), dim3(256), 0, s, a);
+}
+
+// Thread z: the only writer of slot slots[z]'s counters in the append.
+__global__ __launch_bounds__(256) void synth_put_commit_active_kernel(const SynthPutArgs a) {
+    const int z = blockIdx.x * 256 + threadIdx.x;
+    if (z >= a.nz) return;
+    long long* c = a.ring.ctr + (long long)a.slots[z] * SYNTH_CTR;
+    const long long cap = a.ring.cap;
+    const long long rows = c[0] + a.n;
+    c[0] = rows < cap ? rows : cap;
+    c[1] = (c[1] + a.n) % cap;
+    c[2] += a.n;
+}
+
+void launch_synth_put_commit_active(const SynthPutArgs& a, hipStream_t s) {
+    if (a.nz <= 0) return;
+    hipLaunchKernelGGL(synth_put_commit_active_kernel, dim3((a.nz + 255) / 256), dim3(256), 0, s, a);
 }
 
 // ====================================================== ensemble rollout ==

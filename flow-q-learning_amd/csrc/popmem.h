@@ -150,6 +150,30 @@ struct PopRowStage {
     long long field_width(int f) const { return f == 0 || f == 4 ? D : f == 1 ? A : 1; }
 };
 
+// The staging of fqlpop_act: one pinned host buffer and one device buffer of the same layout,
+// for `cols` = active members x envs columns, grown on demand by replace_released.  A call of
+// n <= cols columns uses the inputs [obs n x D | noise n x A] from float 0 (one copy up) and
+// the outputs [actions n x A | noise used n x A] from float out_off() (one copy down).
+// Empty: no columns.  (Host test: tests/cpp/actstage_test.cpp.)
+template <class BE = DefaultBackend>
+struct PopActStage {
+    HostBuf<float, BE> host;
+    DevBuf<float, BE> dev;
+    long long cols = 0;
+    int D = 0, A = 0;
+
+    static PopActStage make(long long cols, int D, int A, unsigned flags) {
+        PopActStage s;
+        s.host = HostBuf<float, BE>((size_t)cols * (D + 3 * A), flags, "act stage (host)");
+        s.dev = DevBuf<float, BE>((size_t)cols * (D + 3 * A), "act stage (device)");
+        s.cols = cols;
+        s.D = D;
+        s.A = A;
+        return s;
+    }
+    long long out_off() const { return cols * (D + A); }
+};
+
 // The streams of a population step: the main one and three side streams, which are streams of
 // their own or, when the step runs on one stream, views of the main one.  One owner per
 // stream: the views own nothing.

@@ -376,6 +376,10 @@ struct fqlpop : StepStreams<> {
     PopRowStage<kSynthRowStage> synth_rows;
     Event<> synth_rows_ev[kSynthRowStage];  // buffer i's last reader (made with the first stage)
     int synth_rows_next = 0;
+    // fqlpop_act: its pinned and device staging (sized at the first call, regrown when
+    // active members x envs grows) and act_kernel's time in the last call (HIP events)
+    PopActStage<> act_stage;
+    double act_kernel_us = -1.0;
     bool probe = false;
     int probe_set = -1;            // set used by the step being enqueued (-1: none)
     int probe_idx = 0;             // next launch slot of that set
@@ -2451,6 +2455,68 @@ int fqlpop_sample_actions(fqlpop_t* h, int member, const float* obs, int64_t n, 
     });
 }
 
+int fqlpop_act(fqlpop_t* h, const float* obs, int n_envs, const float* noise, uint64_t seed, uint32_t t, float* out,
+               float* out_noise) {
+    return guard([&] {
+        ARGCHK(h && obs && out, "null argument");
+        ARGCHK(n_envs >= 1, "n_envs must be >= 1");
+        ARGCHK(noise || t >= 1, "t counts environment steps from 1 (device noise)");
+        const int D = h->D, A = h->A, H = h->H, L = h->L;
+        if (!act_supported(H, L, D, A))
+            throw Err{FQLPOP_E_UNSUPPORTED, "act needs obs_dim + action_dim <= 64 and action_dim <= 8"};
+        if (h->os.ln) throw Err{FQLPOP_E_UNSUPPORTED, "act with actor_layer_norm is not supported"};
+        HIPCHK(hipSetDevice(h->device));
+        if (split_error_pending(h)) sync_all_streams(h);
+        check_split_error(h, -1, true);  // a poisoned active member's parameters are not acted on
+        if (h->nz == 0) return;
+        const long long cols = (long long)h->nz * n_envs;
+        auto& st = h->act_stage;
+        if (cols > st.cols) {
+            HIPCHK(hipStreamSynchronize(h->sM));
+            replace_released(st, [&] { return PopActStage<>::make(cols, D, A, hipHostMallocDefault); });
+        }
+        float* hp = st.host;
+        float* dp = st.dev;
+        const size_t n_obs = (size_t)cols * D, n_act = (size_t)cols * A;
+        std::memcpy(hp, obs, sizeof(float) * n_obs);
+        if (noise) std::memcpy(hp + n_obs, noise, sizeof(float) * n_act);
+        const long long oo = st.out_off();
+        hipStream_t s = h->sM;
+        HIPCHK(hipMemcpyAsync(dp, hp, sizeof(float) * (n_obs + (noise ? n_act : 0)), hipMemcpyHostToDevice, s));
+        const NetLayout& N = h->os;
+        ActArgs a{};
+        a.params = h->params; a.P = h->P; a.os_off = N.off;
+        a.w0 = N.W[0]; a.b0 = N.b[0];
+        a.w1 = L > 1 ? N.W[1] : 0; a.b1 = L > 1 ? N.b[1] : 0;
+        a.lstride = L > 2 ? N.W[2] - N.W[1] : 0;
+        a.wh = N.W[L]; a.bh = N.b[L];
+        a.D = D; a.A = A; a.H = H; a.L = L;
+        a.obs = dp; a.noise = noise ? dp + n_obs : nullptr;
+        a.n_envs = n_envs; a.seed = seed; a.t = t; a.member_seeds = h->skeys;
+        a.out = dp + oo; a.out_noise = out_noise ? dp + oo + n_act : nullptr;
+        a.nz = h->nz; a.slots = h->slots;
+        HIPCHK(hipEventRecord(h->ev_t0, s));
+        launch_act(a, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev_t1, s));
+        HIPCHK(hipMemcpyAsync(hp + oo, dp + oo, sizeof(float) * n_act * (out_noise ? 2 : 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+        h->act_kernel_us = 1000.0 * ms;
+        std::memcpy(out, hp + oo, sizeof(float) * n_act);
+        if (out_noise) std::memcpy(out_noise, hp + oo + n_act, sizeof(float) * n_act);
+    });
+}
+
+int fqlpop_act_time(fqlpop_t* h, double* kernel_us) {
+    return guard([&] {
+        ARGCHK(h && kernel_us, "null argument");
+        if (h->act_kernel_us < 0) throw Err{FQLPOP_E_STATE, "no fqlpop_act call yet"};
+        *kernel_us = h->act_kernel_us;
+    });
+}
+
 int fqlpop_state_size(fqlpop_t* h, int64_t* n_floats) {
     return guard([&] {
         ARGCHK(h && n_floats, "null argument");
@@ -3234,6 +3300,50 @@ int fqlpop_synth_write(fqlpop_t* h, int member, const float* obs, const float* a
 int fqlpop_synth_append(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
                         const float* mask, const float* next_obs, int64_t n) {
     return guard([&] { synth_put_run(h, member, obs, act, rew, mask, next_obs, n, false, 0); });
+}
+
+// fqlpop_synth_append for every active member: one staging copy of the [n_active][n][..] fields,
+// one placement launch over (field, member) and one commit launch.
+int fqlpop_synth_append_active(fqlpop_t* h, const float* obs, const float* act, const float* rew, const float* mask,
+                               const float* next_obs, int n) {
+    return guard([&] {
+        need_rings(h);
+        const long long cap = h->synth.cap;
+        ARGCHK(n >= 0 && n <= cap, "n must be in 0..capacity");
+        ARGCHK(n == 0 || (obs && act && rew && mask && next_obs), "null argument");
+        if (n == 0 || h->nz == 0) return;
+        HIPCHK(hipSetDevice(h->device));
+        const long long rows = (long long)n * h->nz;
+        auto& st = h->synth_rows;
+        if (rows > st.rows) {
+            HIPCHK(hipStreamSynchronize(h->sM));
+            for (auto& ev : h->synth_rows_ev)
+                if (!ev) ev = Event<>(hipEventDisableTiming);
+            replace_released(st, [&] {
+                return PopRowStage<fqlpop::kSynthRowStage>::make(rows, h->D, h->A, hipHostMallocMapped);
+            });
+        }
+        const int stage = h->synth_rows_next;
+        h->synth_rows_next = (stage + 1) % fqlpop::kSynthRowStage;
+        // the buffer's last reader (the placement of kSynthRowStage calls ago) has run
+        if (st.used[stage]) HIPCHK(hipEventSynchronize(h->synth_rows_ev[stage]));
+        float* hp = st.host[stage];
+        const float* src[5] = {obs, act, rew, mask, next_obs};
+        for (int f = 0; f < 5; ++f)
+            std::memcpy(hp + st.field(f, rows), src[f], sizeof(float) * (size_t)(rows * st.field_width(f)));
+        float* dp = nullptr;
+        HIPCHK(hipHostGetDevicePointer((void**)&dp, hp, 0));
+        SynthPutArgs p{};
+        p.ring = h->synth; p.D = h->D; p.A = h->A; p.slot = -1; p.write = 0; p.n = n;
+        p.obs = dp + st.field(0, rows); p.act = dp + st.field(1, rows); p.rew = dp + st.field(2, rows);
+        p.mask = dp + st.field(3, rows); p.nobs = dp + st.field(4, rows);
+        p.nz = h->nz; p.slots = h->slots;
+        launch_synth_put_active(p, h->sM);
+        HIPCHK(hipEventRecord(h->synth_rows_ev[stage], h->sM));
+        st.used[stage] = true;
+        launch_synth_put_commit_active(p, h->sM);
+        HIPCHK(hipGetLastError());
+    });
 }
 
 int fqlpop_synth_clear(fqlpop_t* h, int member) {

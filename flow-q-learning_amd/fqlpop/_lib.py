@@ -179,6 +179,9 @@ _SIGS = {
     "fqlpop_synth_clear": (ctypes.c_int, [_P, ctypes.c_int]),
     "fqlpop_synth_write": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64, ctypes.c_int64]),
     "fqlpop_synth_append": (ctypes.c_int, [_P, ctypes.c_int, _F, _F, _F, _F, _F, ctypes.c_int64]),
+    "fqlpop_synth_append_active": (ctypes.c_int, [_P, _F, _F, _F, _F, _F, ctypes.c_int]),
+    "fqlpop_act": (ctypes.c_int, [_P, _F, ctypes.c_int, _F, ctypes.c_uint64, ctypes.c_uint32, _F, _F]),
+    "fqlpop_act_time": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "fqlpop_emtrain_param_count": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), ctypes.POINTER(ctypes.c_int64)]),
     "fqlpop_emtrain_create": (ctypes.c_int, [ctypes.POINTER(EmTrainConfig), _F, ctypes.c_int64, ctypes.c_int,
                                              ctypes.POINTER(_P)]),

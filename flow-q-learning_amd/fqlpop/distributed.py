@@ -178,6 +178,13 @@ def collect_seed(base_seed: int, collect_index: int) -> int:
     return int(np.random.default_rng(words).integers(0, 2**31 - 1))
 
 
+def online_seed(base_seed: int) -> int:
+    """Seed of a run's online phase (the environments' resets and ``Population.act``'s
+    noise): a function of the run seed alone, apart from the seeds above by its last word."""
+    words = [int(base_seed) & 0xFFFFFFFF, 0, 0x5E14]
+    return int(np.random.default_rng(words).integers(0, 2**31 - 1))
+
+
 def member_eval_seed(base_seed: int, round_index: int, cfg) -> int:
     """Seed of one candidate's own evaluation in round ``round_index`` (tasks without
     a batched world-model evaluation): a function of the run seed, the round and the

@@ -301,6 +301,37 @@ class Population:
                                              ctypes.c_uint64(int(seed) & (2**64 - 1)), fptr(out)))
         return out[0] if squeeze else out
 
+    def act(self, observations, seed: int = 0, t: int = 1, noise=None, return_noise: bool = False):
+        """``sample_actions`` for every ACTIVE member in one launch (fqlpop_act), each on its
+        own observations [n_active, n_envs, obs_dim] (slot order); returns actions
+        [n_active, n_envs, action_dim].  ``noise`` [n_active, n_envs, action_dim] injects z;
+        None draws it on the device as ``rollout`` draws its policy noise at step ``t`` (from
+        1) under ``seed``.  return_noise: also the z used.  Reads parameters only; waits for
+        the steps enqueued before it."""
+        D, A = self.cfg.obs_dim, self.cfg.action_dim
+        nz = len(self.active_ids)
+        obs = _f32(observations)
+        if obs.ndim != 3 or obs.shape[0] != nz or obs.shape[2] != D:
+            raise ValueError(f"observations must have shape ({nz}, n_envs, {D}), got {obs.shape}")
+        n_envs = int(obs.shape[1])
+        z = None
+        if noise is not None:
+            z = _f32(noise)
+            if z.shape != (nz, n_envs, A):
+                raise ValueError(f"noise must have shape {(nz, n_envs, A)}, got {z.shape}")
+        out = np.zeros((nz, n_envs, A), dtype=np.float32)
+        used = np.zeros((nz, n_envs, A), dtype=np.float32) if return_noise else None
+        check(self.lib.fqlpop_act(self._h, fptr(obs), n_envs, None if z is None else fptr(z),
+                                  ctypes.c_uint64(int(seed) & (2**64 - 1)), ctypes.c_uint32(int(t) & 0xFFFFFFFF),
+                                  fptr(out), None if used is None else fptr(used)))
+        return (out, used) if return_noise else out
+
+    def last_act_us(self) -> float:
+        """GPU time of the act kernel in the last ``act`` call (fqlpop_act_time), microseconds."""
+        us = ctypes.c_double()
+        check(self.lib.fqlpop_act_time(self._h, ctypes.byref(us)))
+        return us.value
+
     # ------------------------------------------------------ world-model eval
     def set_env_model(self, sp_flat, tp_flat, sp_hidden=(128, 256, 128), tp_hidden=(128, 128)):
         """Upload a BaselineStatePredictor / TerminationPredictor pair as flat
@@ -515,6 +546,10 @@ class Population:
         (fqlpop_synth_create); real_ratio starts at 1, so nothing changes until it is lowered."""
         check(self.lib.fqlpop_synth_create(self._h, int(capacity_rows)))
         self.synth_capacity = int(capacity_rows)
+        # host mirror of each ring's valid rows as the host's own writes leave them
+        # (synth_write, synth_append, synth_append_active, synth_clear; a collect's row count
+        # is known on the device only and is not mirrored): read without synchronising
+        self.synth_rows_host = np.zeros(self.n, dtype=np.int64)
 
     def set_real_ratio(self, real_ratio: float):
         """The share of offline rows in the training minibatch (fqlpop_synth_set_ratio): 1
@@ -569,6 +604,10 @@ class Population:
     def synth_clear(self, member: int = -1):
         """Empty one member's ring, or (-1) all; stream-ordered."""
         check(self.lib.fqlpop_synth_clear(self._h, int(member)))
+        if int(member) < 0:
+            self._rows_mirror()[:] = 0
+        else:
+            self._set_rows(int(member), 0)
 
     def _synth_rows(self, data) -> tuple[dict, int]:
         """``data`` (a ``synth_read`` dict) as float32 C-contiguous arrays and its row count;
@@ -597,6 +636,7 @@ class Population:
         check(self.lib.fqlpop_synth_write(self._h, int(member), fptr(rows["observations"]), fptr(rows["actions"]),
                                           fptr(rows["rewards"]), fptr(rows["masks"]),
                                           fptr(rows["next_observations"]), n, n if appended is None else int(appended)))
+        self._set_rows(int(member), n)
 
     def synth_append(self, member: int, data: dict):
         """Appends the rows of ``data`` (a dict as ``synth_read`` returns, e.g. transitions
@@ -607,6 +647,46 @@ class Population:
         check(self.lib.fqlpop_synth_append(self._h, int(member), fptr(rows["observations"]), fptr(rows["actions"]),
                                            fptr(rows["rewards"]), fptr(rows["masks"]),
                                            fptr(rows["next_observations"]), n))
+        self._note_appended([int(member)], n)
+
+    def _rows_mirror(self) -> np.ndarray:
+        if getattr(self, "synth_rows_host", None) is None:
+            self.synth_rows_host = np.zeros(int(getattr(self, "n", 0)), dtype=np.int64)
+        return self.synth_rows_host
+
+    def _set_rows(self, member: int, rows: int):
+        m = self._rows_mirror()
+        if 0 <= member < m.shape[0]:
+            m[member] = rows
+
+    def _note_appended(self, members, n: int):
+        m = self._rows_mirror()
+        for i in members:
+            m[i] = min(int(self.synth_capacity), int(m[i]) + int(n))
+
+    def synth_append_active(self, data: dict):
+        """``synth_append`` for every ACTIVE member in one call (fqlpop_synth_append_active):
+        ``data`` holds the five fields, each [n_active, n, ..] (float32), block z for the z-th
+        active member in slot order.  One staging copy and two launches; rings and counters
+        end as after one ``synth_append`` per active member."""
+        D, A = self.cfg.obs_dim, self.cfg.action_dim
+        ids = self.active_ids
+        tails = {"observations": (D,), "actions": (A,), "rewards": (), "masks": (), "next_observations": (D,)}
+        if not isinstance(data, dict) or any(k not in data for k in tails):
+            raise ValueError(f"ring rows need the fields {tuple(tails)}")
+        rows, n = {}, None
+        for k, tail in tails.items():
+            a = np.asarray(data[k])
+            if a.dtype != np.float32:
+                raise ValueError(f"ring rows: {k} must be float32, got {a.dtype}")
+            n = a.shape[1] if n is None and a.ndim >= 2 else n
+            if a.shape != (len(ids), n) + tail:
+                raise ValueError(f"ring rows: {k} must have shape {(len(ids), n) + tail}, got {a.shape}")
+            rows[k] = np.ascontiguousarray(a)
+        check(self.lib.fqlpop_synth_append_active(self._h, fptr(rows["observations"]), fptr(rows["actions"]),
+                                                  fptr(rows["rewards"]), fptr(rows["masks"]),
+                                                  fptr(rows["next_observations"]), int(n)))
+        self._note_appended(ids, int(n))
 
     def synth_state(self, member: int) -> dict:
         """One member's ring for a checkpoint: the ``synth_read`` dict of its valid rows plus

@@ -95,5 +95,11 @@ class OfflineTaskSynthetic(Task):
             infos.append(info)
         return self._state.copy(), rewards, terminated, truncated, infos
 
+    def online_envs(self, n_members: int, n_envs: int, seed: int):
+        """``n_envs`` environments of ``step``'s toy reach dynamics for each of ``n_members``
+        population members (task.online_envs.OnlineEnvs), for an online phase."""
+        from task.online_envs import ReachEnvs
+        return ReachEnvs(n_members, n_envs, self.obs_dim, self.action_dim, self.max_episode_steps, seed)
+
     def close(self):
         self._state = None

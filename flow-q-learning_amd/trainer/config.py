@@ -88,6 +88,46 @@ class ModelRolloutConfig:
 
 
 @dataclass
+class OnlineConfig:
+    """Offline-to-online fine-tuning (FQL's main.py after its offline steps; not a
+    TrainerConfig field, as ModelRolloutConfig).  Off while ``steps`` is 0.  The last
+    ``steps`` of the run's updates are online: for every ``utd`` updates each member acts
+    once in its own ``envs`` environments (one ``Population.act`` for the whole group) and
+    the observed transitions go into its ring of ``buffer_rows`` rows.  ``real_ratio`` is the
+    share of offline rows in the minibatch, or "auto": n_offline / (n_offline + ring rows),
+    FQL's uniform draw over dataset and online data together."""
+    steps: int = 0
+    envs: int = 8
+    utd: int = 1
+    buffer_rows: int = 100_000
+    real_ratio: float | str = "auto"
+
+    @property
+    def enabled(self) -> bool:
+        return self.steps > 0
+
+    def validate(self) -> None:
+        if not self.enabled:
+            return
+        if self.envs < 1 or self.utd < 1:
+            raise ValueError("an online phase needs online_envs >= 1 and online_utd >= 1")
+        if self.envs > self.buffer_rows:
+            raise ValueError(f"online_buffer_rows {self.buffer_rows} holds less than one environment step "
+                             f"({self.envs} envs)")
+        if isinstance(self.real_ratio, str):
+            if self.real_ratio != "auto":
+                raise ValueError(f"online_real_ratio must be 'auto' or a number in [0, 1], got {self.real_ratio!r}")
+        elif not 0.0 <= float(self.real_ratio) <= 1.0:
+            raise ValueError(f"online_real_ratio must be in [0, 1], got {self.real_ratio}")
+
+    def ratio(self, n_offline: int, ring_rows: int) -> float:
+        """The real_ratio to train under when a member's ring holds ``ring_rows`` rows."""
+        if self.real_ratio == "auto":
+            return float(n_offline) / float(n_offline + ring_rows)
+        return float(self.real_ratio)
+
+
+@dataclass
 class TrainerConfig:
     seed: int = 0
     steps: int = 1_000_000

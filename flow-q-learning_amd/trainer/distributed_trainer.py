@@ -38,13 +38,17 @@ import numpy as np
 from fqlpop import distributed as D
 from hpo.strategy import HpoStrategy
 from task.task import Task
-from trainer.config import ModelRolloutConfig, TrainerConfig
-from trainer.trainer import MODEL_ROLLOUT_DISTRIBUTED_MSG, PBT_DISTRIBUTED_MSG, Trainer
+from trainer.config import ModelRolloutConfig, OnlineConfig, TrainerConfig
+from trainer.trainer import MODEL_ROLLOUT_DISTRIBUTED_MSG, ONLINE_DISTRIBUTED_MSG, PBT_DISTRIBUTED_MSG, Trainer
 
 
 class DistributedTrainer(Trainer):
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
-                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None):
+                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None,
+                 online: OnlineConfig | None = None):
+        if online is not None and online.enabled:
+            raise NotImplementedError(ONLINE_DISTRIBUTED_MSG)
+        self.online = OnlineConfig()
         if hasattr(strategy, "parent_of"):
             raise NotImplementedError(PBT_DISTRIBUTED_MSG)
         if model_rollouts is not None and model_rollouts.enabled:

@@ -29,8 +29,9 @@ import numpy as np
 from fqlpop import Population, PopulationConfig
 from fqlpop import distributed as D
 from hpo.strategy import HpoStrategy
+from task.online_envs import online_envs_of
 from task.task import Task
-from trainer.config import ModelRolloutConfig, TrainerConfig
+from trainer.config import ModelRolloutConfig, OnlineConfig, TrainerConfig
 from trainer.experiment import Experiment, agent_config_for, train_population
 from dataclasses import asdict
 
@@ -47,6 +48,14 @@ MODEL_ROLLOUT_TASK_MSG = ("training on world-model branches (--model_rollout_bra
 MODEL_ROLLOUT_ENSEMBLE_MSG = ("branches under the env-model ensemble (--model_rollout_ensemble) need a task with an "
                               "ensemble: OfflineTaskWithSimulatedEvaluations(env_models=... or ensemble_size=K) "
                               "(--env_model_ensemble K); this task has one env model")
+ONLINE_ROLLOUT_MSG = ("an online phase (--online_steps) and training on world-model branches "
+                      "(--model_rollout_branches) both write the members' rings: one ring, two writers; choose one")
+ONLINE_CLONE_MSG = ("an online phase (--online_steps) does not run under strategies that clone members (parent_of: "
+                    "PopulationBasedTraining): a clone's environments would not follow its parent's; use --strategy "
+                    "identity or successive_halving")
+ONLINE_DISTRIBUTED_MSG = ("an online phase (--online_steps) runs on one GPU only: a member's environments and ring "
+                          "are not moved when pruning rebalances members between ranks; run tune_alpha.py without "
+                          "torch.distributed.run (WORLD_SIZE = 1)")
 LINEAGE_COLUMNS = ("round", "step", "child", "parent", "parent_alpha", "child_alpha", "parent_score")
 
 
@@ -67,12 +76,28 @@ class Trainer:
     _clones = False  # (DistributedTrainer refuses cloning strategies)
 
     def __init__(self, task: Task, strategy: HpoStrategy, config: TrainerConfig, state_dict: dict | None = None,
-                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None):
+                 device: int = 0, model_rollouts: ModelRolloutConfig | None = None,
+                 online: OnlineConfig | None = None):
         self.task = task
         self.strategy = strategy
         self.config = config
         self.experiments = {}
         self.member_of = {}
+        # offline-to-online fine-tuning: off (and nothing below differs) unless steps > 0
+        self.online = online if online is not None else OnlineConfig()
+        self.online_envs = None
+        self.online_env_steps = int(state_dict.get("online", {}).get("env_steps", 0)) if state_dict else 0
+        if self.online.enabled:  # refused before any GPU call
+            self.online.validate()
+            if model_rollouts is not None and model_rollouts.enabled:
+                raise ValueError(ONLINE_ROLLOUT_MSG)
+            if hasattr(strategy, "parent_of"):
+                raise ValueError(ONLINE_CLONE_MSG)
+            if not hasattr(task, "online_envs"):
+                online_envs_of(task, 0, 0, 0)  # raises: the task offers no online environments
+            if task.device_datasets() is None:
+                raise ValueError("an online phase (--online_steps) needs a task whose dataset the population "
+                                 "samples on the device (Task.device_datasets)")
         # training on world-model branches: off (and nothing below differs) unless branches > 0
         self.model_rollouts = model_rollouts if model_rollouts is not None else ModelRolloutConfig()
         self.collect_index = int(state_dict.get("collect_index", 0)) if state_dict else 0
@@ -95,6 +120,11 @@ class Trainer:
         sampled = None if state_dict else strategy.sample()
         initial = list(state_dict["experiments"]) if state_dict else list(sampled)
         self.population = self._make_population(initial, device)
+        if self.online.enabled:
+            self.online_envs = online_envs_of(task, self.population.n, self.online.envs,
+                                              D.online_seed(config.seed))
+            if state_dict is not None and "envs" in state_dict.get("online", {}):
+                self.online_envs.load_state_dict(state_dict["online"]["envs"])
         if state_dict is not None:
             for cfg, exp_state in state_dict["experiments"].items():
                 self.create_experiment(cfg, state_dict=exp_state)
@@ -139,6 +169,10 @@ class Trainer:
             self.task.attach(pop)
             pop.synth_create(self.model_rollouts.buffer_rows)
             pop.set_real_ratio(self.model_rollouts.real_ratio)
+        if self.online.enabled:
+            # the rings start empty and real_ratio at 1: the offline updates draw offline rows
+            # only.  A resumed run's Experiments put their rings back ("synth_ring")
+            pop.synth_create(self.online.buffer_rows)
         return pop
 
     def _slot_for(self, cfg) -> int:
@@ -169,6 +203,8 @@ class Trainer:
             sd["lineage"] = list(self.lineage)
         if self.model_rollouts.enabled:
             sd["collect_index"] = self.collect_index
+        if self.online.enabled:
+            sd["online"] = {"env_steps": self.online_env_steps, "envs": self.online_envs.state_dict()}
         return sd
 
     def _base_state_dict(self) -> dict:
@@ -191,7 +227,11 @@ class Trainer:
             groups.setdefault(exp.current_step, []).append(exp)
         for step, exps in groups.items():
             n = min(self.config.eval_interval, self.config.steps - step)
-            if exps[0].on_device and self.model_rollouts.enabled:
+            if exps[0].on_device and self.online.enabled and step + n > self.online_start:
+                offline = max(0, self.online_start - step)
+                train_population(exps, offline)
+                self._train_online(exps, n - offline)
+            elif exps[0].on_device and self.model_rollouts.enabled:
                 self._train_with_rollouts(exps, n)
             elif exps[0].on_device:
                 train_population(exps, n)
@@ -223,6 +263,48 @@ class Trainer:
                                         D.collect_seed(self.config.seed, collect_number(cur, mr)),
                                         ensemble=mr.ensemble, penalty=mr.penalty)
                 self.collect_index += 1
+
+    @property
+    def online_start(self) -> int:
+        """The update the online phase begins after: the last ``online.steps`` are online."""
+        return max(0, self.config.steps - self.online.steps)
+
+    def _train_online(self, exps, n: int) -> None:
+        """``n`` online updates of one lock-step group.  Before every ``utd``-th update (counted
+        from the start of the online phase) the group takes one environment step: one
+        ``Population.act`` on the members' current observations (noise drawn on the device at
+        t = the group's environment-step count, from 1, under ``D.online_seed``), one step of
+        their environments, one ``synth_append_active`` of the observed transitions (masks =
+        1 - terminated, the environment's reward) and the real_ratio for the rings' new
+        size; then up to ``utd`` updates.  The environment-step count follows from the
+        group's update count, so a run does not depend on how it was cut into invocations."""
+        on, pop, envs = self.online, self.population, self.online_envs
+        members = [e.agent.member for e in exps]
+        if sorted(members) != members:
+            exps = sorted(exps, key=lambda e: e.agent.member)
+            members = [e.agent.member for e in exps]
+        mask = [False] * pop.n
+        for m in members:
+            mask[m] = True
+        n_offline = int(self.task.device_datasets()["train"]["observations"].shape[0])
+        seed = D.online_seed(self.config.seed)
+        cur, target = exps[0].current_step, exps[0].current_step + n
+        # (a resumed run, or another group's turn: the ratio that belongs to these rings)
+        pop.set_real_ratio(on.ratio(n_offline, int(pop.synth_rows_host[members[0]])))
+        while cur < target:
+            done = cur - self.online_start  # online updates so far
+            if done % on.utd == 0:
+                pop.set_active(mask)
+                obs = envs.observations[members]
+                actions = pop.act(obs, seed=seed, t=done // on.utd + 1)
+                nxt, rew, term, _ = envs.step(actions, members)
+                pop.synth_append_active({"observations": obs, "actions": actions, "rewards": rew,
+                                         "masks": (1.0 - term).astype(np.float32), "next_observations": nxt})
+                pop.set_real_ratio(on.ratio(n_offline, int(pop.synth_rows_host[members[0]])))
+                self.online_env_steps += 1
+            k = min(on.utd - done % on.utd, target - cur)
+            train_population(exps, k)
+            cur += k
 
     def _evaluate_round(self, configs) -> dict:
         """World-model tasks: every candidate of the round in one GPU rollout

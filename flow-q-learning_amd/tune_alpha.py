@@ -29,6 +29,14 @@ R from the offline data, the rest from the ring (trainer/trainer.py; off by defa
 runs the branches under the K-model ensemble instead (a model drawn per branch and step) and
 lowers every synthetic reward by the penalty times the models' disagreement about that step.
 
+Offline-to-online fine-tuning (--task synthetic, one GPU; strategies identity and
+successive_halving): --online_steps N [--online_envs E] [--online_utd U]
+[--online_buffer_rows C] [--online_real_ratio auto|R]: the last N of --steps updates are
+online.  For every U updates each member acts once in its own E environments (one
+Population.act launch for the whole population), the observed transitions go into its
+on-device ring, and its minibatches draw offline and online rows uniformly over both ("auto")
+or with the offline share R (trainer/trainer.py; off by default).
+
 Multi-GPU (BASELINE configs 4 / 5): launched by torch.distributed.run with one
 process per GPU (``python -m torch.distributed.run --nproc-per-node 8
 --master-addr 127.0.0.1 tune_alpha.py ...``), the population is sharded over the
@@ -47,7 +55,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from argparser import build_config_from_args, build_model_rollout_config_from_args, get_argparser  # noqa: E402
+from argparser import (build_config_from_args, build_model_rollout_config_from_args,  # noqa: E402
+                       build_online_config_from_args, get_argparser)
 from hpo.identity import Identity  # noqa: E402
 from hpo.pbt import PopulationBasedTraining  # noqa: E402
 from hpo.successive_halving import SuccessiveHalving  # noqa: E402
@@ -147,8 +156,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     config = build_config_from_args(args)
     model_rollouts = build_model_rollout_config_from_args(args)
+    online = build_online_config_from_args(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     device = 0
+    if world_size > 1 and online.enabled and not args.single_experiment:
+        from trainer.trainer import ONLINE_DISTRIBUTED_MSG
+        sys.exit(ONLINE_DISTRIBUTED_MSG)  # before any process group exists
+    if args.single_experiment and online.enabled:
+        sys.exit("--online_steps needs the population Trainer (drop --single_experiment)")
     if world_size > 1 and model_rollouts.enabled and not args.single_experiment:
         from trainer.trainer import MODEL_ROLLOUT_DISTRIBUTED_MSG
         sys.exit(MODEL_ROLLOUT_DISTRIBUTED_MSG)  # before any process group exists
@@ -218,7 +233,10 @@ def main(argv=None):
         trainer = DistributedTrainer(task, strategy, config, state_dict=state.get("trainer"), device=device,
                                      model_rollouts=model_rollouts)
     else:
-        trainer = Trainer(task, strategy, config, state_dict=state.get("trainer"), model_rollouts=model_rollouts)
+        # (without --online_steps the call is the one it was: no online argument)
+        extra = {"online": online} if online.enabled else {}
+        trainer = Trainer(task, strategy, config, state_dict=state.get("trainer"), model_rollouts=model_rollouts,
+                          **extra)
     trainer.train(max_evaluations=args.max_evaluations)
     trainer_state = trainer.state_dict()  # collective under DistributedTrainer (rank 0 gets it)
     if trainer_state is not None:

@@ -193,6 +193,32 @@ int fqlpop_read_info(fqlpop_t* h, int which, float* out);
 int fqlpop_sample_actions(fqlpop_t* h, int member, const float* obs, int64_t n,
                           const float* noise, uint64_t seed, float* out);
 
+/* The same policy for every ACTIVE member at once, each on its own n_envs observations:
+ * out[z][e] = clip(onestep(obs[z][e], z_noise), -1, 1) for the z-th active member in slot
+ * order, the whole network in one launch.  obs[n_active][n_envs][obs_dim],
+ * out[n_active][n_envs][action_dim] host arrays.  noise[n_active][n_envs][action_dim]
+ * (host) injects z; NULL draws it on the device as fqlpop_rollout draws its policy noise at
+ * step t (counted from 1): Philox4x32-10 under seed ^ member key * 0x9E3779B97F4A7C15,
+ * counter (env, t, 0x5E11, q), Box-Muller pair q -> actions 2q, 2q + 1.  out_noise, if not
+ * NULL, receives the z used (shaped like noise).
+ * The staging (pinned host memory and a device buffer) belongs to the handle: sized at the
+ * first call, regrown when n_active * n_envs grows, freed by fqlpop_destroy.  One
+ * host-to-device copy, one launch and one device-to-host copy on the stream
+ * fqlpop_sample_actions uses, then one synchronisation of that stream: the actions come from
+ * the parameters every step enqueued before the call leaves, captured graphs stay, and a
+ * pending mse evaluation (engine option lazy_metric) stays pending: only parameters are read.
+ * Before any GPU call: FQLPOP_E_ARG for a null obs / out, n_envs < 1, or t == 0 with noise
+ * NULL; FQLPOP_E_UNSUPPORTED unless obs_dim + action_dim <= 64 and action_dim <= 8 (every
+ * hidden_dim and num_hidden fqlpop_create accepts is served).  A poisoned active member is
+ * refused as fqlpop_step refuses it.  No active member: success, nothing written.
+ * [no reference counterpart: the reference acts one agent at a time, main.py's online loop] */
+int fqlpop_act(fqlpop_t* h, const float* obs, int n_envs, const float* noise, uint64_t seed, uint32_t t,
+               float* out, float* out_noise);
+/* GPU time of the act kernel in the last successful fqlpop_act call on this handle that had
+ * an active member, in microseconds (HIP events around the launch; the call's wall time adds
+ * the staging and the copies).  FQLPOP_E_STATE before the first.  [no reference counterpart] */
+int fqlpop_act_time(fqlpop_t* h, double* kernel_us);
+
 /* Number of floats of one member's flat state (flax tree order: networks
  * actor_bc_flow, actor_onestep_flow, critic, target_critic; leaves sorted as
  * flax does).  which = FQLPOP_STATE_*; M/V have the same layout as PARAMS
@@ -537,6 +563,17 @@ int fqlpop_synth_write(fqlpop_t* h, int member, const float* obs, const float* a
  * appended).  [no reference counterpart] */
 int fqlpop_synth_append(fqlpop_t* h, int member, const float* obs, const float* act, const float* rew,
                         const float* mask, const float* next_obs, int64_t n);
+
+/* fqlpop_synth_append for every ACTIVE member in one call: the arrays are
+ * [n_active][n][..] (obs and next_obs rows of obs_dim, act rows of action_dim, rew and mask
+ * scalars), block z for the z-th active member in slot order.  One staging copy, one
+ * placement launch over (field, member) and one commit launch that advances every active
+ * slot's counters: rings and counters are byte for byte what n_active calls of
+ * fqlpop_synth_append in slot order leave.  0 <= n <= capacity rows per member; n = 0, or no
+ * active member, succeeds and does nothing.  Stream order, graphs, staging and the errors
+ * (before any GPU work) are fqlpop_synth_append's.  [no reference counterpart] */
+int fqlpop_synth_append_active(fqlpop_t* h, const float* obs, const float* act, const float* rew,
+                               const float* mask, const float* next_obs, int n);
 
 /* ---------------------------------------------------------------------------
  * Env-model trainer: the reference's world-model
