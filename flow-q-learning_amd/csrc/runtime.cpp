@@ -1043,22 +1043,27 @@ void transpose_nets(fqlpop* h, hipStream_t s, int mask, bool all_slots, const fl
     t.H = h->H;
     const NetLayout* nets[3] = {&h->critic, &h->bc, &h->os};
     const long long HH = (long long)h->H * h->H;
+    if (all_slots) { t.slots = nullptr; t.nz = h->n; }
+    else { t.slots = h->slots; t.nz = h->nz; }
+    // one launch per TR_MAX matrices: (E + 2) * (L - 1) reaches 42 at num_qs = 4, num_hidden = 8
     int n = 0;
+    auto flush = [&] {
+        t.n_mats = n;
+        launch_transpose(t, s);
+        n = 0;
+    };
     for (int ni = 0; ni < 3; ++ni) {
         if (!(mask & (1 << ni))) continue;
         const NetLayout& N = *nets[ni];
         for (int e = 0; e < N.E; ++e)
             for (int l = 1; l < N.L; ++l) {
-                ARGCHK(n < TR_MAX, "too many transposed matrices");
+                if (n == TR_MAX) flush();
                 t.src_off[n] = N.off + e * N.ens_size + N.W[l];
                 t.dst_off[n] = h->wt_net_off[ni] + ((long long)e * (N.L - 1) + (l - 1)) * HH;
                 ++n;
             }
     }
-    t.n_mats = n;
-    if (all_slots) { t.slots = nullptr; t.nz = h->n; }
-    else { t.slots = h->slots; t.nz = h->nz; }
-    launch_transpose(t, s);
+    flush();
 }
 
 AdamArgs adam_args(const Ctx& c, int ni) {
@@ -2968,7 +2973,7 @@ namespace {
 void rollout_check(fqlpop_t* h) {
     if (!h->em) throw Err{FQLPOP_E_STATE, "no env model set (fqlpop_set_env_model)"};
     if (!rollout_supported(h->H, h->L, h->D, h->A))
-        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, num_hidden <= 8, obs_dim + action_dim <= 64"};
     if (h->os.ln) throw Err{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
 }
 // The launch arguments of such a rollout but for its buffers (init_obs, noise and the
@@ -2989,7 +2994,7 @@ RolloutArgs rollout_args(fqlpop_t* h, int n_envs, int max_steps, uint64_t seed) 
 void ens_check(fqlpop_t* h) {
     if (h->ens.n == 0) throw Err{FQLPOP_E_STATE, "no env model ensemble set (fqlpop_set_env_model_ensemble)"};
     if (!rollout_supported(h->H, h->L, h->D, h->A))
-        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, obs_dim + action_dim <= 64"};
+        throw Err{FQLPOP_E_UNSUPPORTED, "rollout needs hidden_dim 512, num_hidden <= 8, obs_dim + action_dim <= 64"};
     if (h->os.ln) throw Err{FQLPOP_E_UNSUPPORTED, "rollout with actor_layer_norm is not supported"};
 }
 // The launch arguments of such a rollout but for its buffers (init_obs, noise, choice and

@@ -49,7 +49,36 @@ enum {
 /* Which state buffer get_state/set_state address. */
 enum { FQLPOP_STATE_PARAMS = 0, FQLPOP_STATE_ADAM_M = 1, FQLPOP_STATE_ADAM_V = 2 };
 
-/* Mirrors trainer/config.py:5-22 (AgentConfig) for the fields update() reads. */
+/* Mirrors trainer/config.py:5-22 (AgentConfig) for the fields update() reads.
+ *
+ * Accepted ranges (fqlpop_create refuses everything else with FQLPOP_E_ARG) and the path that
+ * serves each; every accepted configuration trains, and tests/test_gpu_config_space.py steps
+ * the edges named here against the float64 oracle:
+ *   hidden_dim   64, 128, 256, 512 or 1024.  512 runs the streamed kernels (whole-network
+ *                forwards and backwards, the persistent Euler flow, dW + Adam in one launch),
+ *                every other width one GEMM launch per layer and an unfused Adam.
+ *   num_hidden   1..15 (at 16 the optimiser's table of 128 trainable leaves is full).  At
+ *                hidden_dim 512: 1..8 run the streamed kernels, and small populations split
+ *                them into clusters of blocks, the forwards and the Euler flow from 3 hidden
+ *                layers, the backwards from 2, nothing at 1; 9..15 run the per-layer path with
+ *                one dW GEMM per layer.  fqlpop_rollout and fqlpop_synth_collect serve 1..8
+ *                (FQLPOP_E_UNSUPPORTED above); fqlpop_act and fqlpop_sample_actions any depth.
+ *   num_qs       1..4, on every path, q_agg mean or min.  State layout: the critic's and the
+ *                target critic's leaves are [num_qs][...] for num_qs >= 2 (kernels
+ *                [num_qs][in][out], biases and LayerNorm leaves [num_qs][out]); at num_qs = 1
+ *                they have NO ensemble axis ([in][out], [out]), where a flax tree keeps a
+ *                leading axis of 1.  fqlpop_leaf_info reports the shapes; the flat order and
+ *                the number of floats are the same either way.
+ *   action_dim   1..8, on every path.
+ *   obs_dim      >= 1.  At hidden_dim 512 the streamed forwards and the Euler flow hold up to
+ *                64 layer-0 rows: obs_dim + action_dim + 1 <= 64.  Wider inputs run the
+ *                per-layer forwards and Euler GEMMs into the streamed backwards and fused
+ *                optimiser.  fqlpop_act, fqlpop_rollout and the env-model calls need obs_dim +
+ *                action_dim <= 64 (FQLPOP_E_UNSUPPORTED above).
+ *   flow_steps   >= 2, on every path.
+ *   batch_size   a multiple of 64.
+ * Leaves are ordered by name as strings (flax), so from num_hidden = 10 on Dense_10 comes
+ * before Dense_2: the flat state is not in layer order. */
 typedef struct fqlpop_config {
     int obs_dim;           /* ob_dims[-1]; set by FQLAgent.create from ex_observations */
     int action_dim;        /* set by FQLAgent.create from ex_actions */

@@ -49,6 +49,7 @@ class OptimiserChecker:
         self.pop, self.member, self.lr, self.tau = pop, member, lr, tau
         self.b1, self.b2, self.eps = b1, b2, eps
         self.prev = None
+        self.worst_moment = 0.0   # largest moment error seen, as a fraction of MOMENT_REL * leaf scale
 
     def _state(self):
         from fqlpop._lib import STATE_ADAM_M, STATE_ADAM_V, STATE_PARAMS
@@ -73,6 +74,8 @@ class OptimiserChecker:
                 o = np.asarray(want[net][leaf], dtype=np.float64).reshape(-1)
                 scale = float(np.abs(o).max()) if o.size else 0.0
                 err = float(np.abs(got[sl] - o).max()) if o.size else 0.0
+                if scale > 0:
+                    self.worst_moment = max(self.worst_moment, err / (MOMENT_REL * scale))
                 if err > MOMENT_REL * scale + 1e-30:
                     bad.append(f"{name} adam {what}: max err {err:.3g} vs leaf scale {scale:.3g}")
             if net == "target_critic":
@@ -214,6 +217,15 @@ def f32_tree(tree):
     return O.cast_tree(O.cast_tree(tree, np.float32), np.float64)
 
 
+def device_tree(pop, tree):
+    """The oracle's {net: {leaf: array}} tree in the library's leaf shapes (``pop.leaves``).
+    They differ at num_qs = 1 only: the oracle keeps the critic's leading ensemble axis
+    ([1, in, out]), the library's state layout has none there ([in, out]; include/fqlpop.h)."""
+    shapes = {name: shape for name, _, shape in pop.leaves}
+    return {net: {k: v[0] if v.shape == (1,) + shapes[f"{net}/{k}"] else v for k, v in leaves.items()}
+            for net, leaves in tree.items() if isinstance(leaves, dict)}
+
+
 def close(a, b, rel=REL, floor=1e-6):
     return abs(a - b) <= rel * max(abs(a), abs(b)) + floor
 
@@ -225,6 +237,11 @@ def check_info(got, want, keys, tag):
         if not close(g, w):
             bad.append(f"{k}: gpu={g:.8g} oracle={w:.8g} rel={abs(g - w) / max(abs(w), 1e-30):.3g}")
     assert not bad, f"{tag}:\n" + "\n".join(bad)
+
+
+def info_ratio(got, want, keys, rel=REL, floor=1e-6):
+    """The largest |got - want| over ``close``'s bound, over ``keys`` (<= 1: check_info passes)."""
+    return max(abs(got[k] - float(want[k])) / (rel * max(abs(got[k]), abs(float(want[k]))) + floor) for k in keys)
 
 
 def synthetic_rows(N, D, A, seed):
@@ -250,10 +267,12 @@ class Spec(NamedTuple):
     kw: tuple = ()          # further OracleConfig / PopulationConfig fields, as sorted items
     sampled: tuple = ()     # (population seed, dataset rows): the batch and noise are the
     #                         device sampler's own draws at TRAINED_COUNT, not injected
+    L: int = 4              # hidden layers, each H wide
+    head_scale: float = 3.0  # trained_like_params' factor on both actors' head kernels
 
     def cfg(self):
         from oracle import fql_oracle as O
-        return O.OracleConfig(obs_dim=self.D, action_dim=self.A, hidden_dims=(self.H,) * 4,
+        return O.OracleConfig(obs_dim=self.D, action_dim=self.A, hidden_dims=(self.H,) * self.L,
                               batch_size=self.B, alpha=self.alpha, **dict(self.kw))
 
 
@@ -266,7 +285,8 @@ class TrainedMember:
         from oracle import fql_oracle as O
         self.spec, self.cfg = spec, spec.cfg()
         cfg, B = self.cfg, spec.B
-        self.params = f32_tree(O.trained_like_params(cfg, spec.seed, q_offset=spec.q_offset))
+        self.params = f32_tree(O.trained_like_params(cfg, spec.seed, q_offset=spec.q_offset,
+                                                          head_scale=spec.head_scale))
         self.batches, self.noises = [], []
         if spec.sampled:
             from philox_np import draw, sample_key
@@ -321,7 +341,8 @@ def check_member_conditions(tm: TrainedMember):
 
 
 def _specs(H, B, seeds, alphas=(4.0, 40.0, 400.0), **kw):
-    extra = {k: kw.pop(k) for k in ("n_steps", "D", "A", "q_offset", "sampled") if k in kw}
+    extra = {k: kw.pop(k) for k in ("n_steps", "D", "A", "q_offset", "sampled", "L", "head_scale")
+             if k in kw}
     out = []
     for i, s in enumerate(seeds):
         e = dict(extra)

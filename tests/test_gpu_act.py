@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import act_np as N
-from _helpers import ROLLOUT_SPECS, ROLLOUT_STEPS, rollout_case, trained_member
+from _helpers import ROLLOUT_SPECS, ROLLOUT_STEPS, device_tree, rollout_case, trained_member
 from oracle import fql_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +22,10 @@ def _population(specs, seeds=None):
     """One member per spec (one configuration), its trained-like parameters uploaded."""
     from fqlpop import Population, PopulationConfig
     s0 = specs[0]
-    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * 4, batch_size=s0.B, **dict(s0.kw))
+    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * s0.L, batch_size=s0.B, **dict(s0.kw))
     pop = Population(pc, [s.alpha for s in specs], list(seeds or [11 + i for i in range(len(specs))]))
     for i, s in enumerate(specs):
-        pop.set_params(i, O.cast_tree(trained_member(s).params, np.float32))
+        pop.set_params(i, device_tree(pop, O.cast_tree(trained_member(s).params, np.float32)))
     return pop
 
 

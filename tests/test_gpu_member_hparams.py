@@ -13,8 +13,8 @@ member's row of the device array by SLOT.
 8. the tune_alpha.py driver: --lrs grids, resume, --pbt_explore.
 
 Tolerances are the project's own: _helpers.REL for info values, OptimiserChecker with the
-member's own lr and tau for the moments and the exact optimiser / EMA step.  No test steps a
-num_hidden = 1 population."""
+member's own lr and tau for the moments and the exact optimiser / EMA step.  (Depths other than
+four, num_hidden = 1 among them, are stepped by tests/test_gpu_config_space.py.)"""
 import csv
 import ctypes
 import functools
@@ -57,7 +57,7 @@ def _trained_population(specs, hparams, use_graph=True):
     from fqlpop import Population, PopulationConfig
     from fqlpop._lib import STATE_ADAM_M, STATE_ADAM_V
     s0 = specs[0]
-    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * 4, batch_size=s0.B,
+    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * s0.L, batch_size=s0.B,
                           use_graph=use_graph)
     pop = Population(pc, [s.alpha for s in specs], [11 + i for i in range(len(specs))], hparams=hparams)
     for i, s in enumerate(specs):

@@ -19,9 +19,9 @@ import pytest
 
 from oracle import envmodel_oracle as EO
 from oracle import fql_oracle as O
-from _helpers import (ACTION_SPECS, ROLLOUT_SPECS, ROLLOUT_STEPS, TRAINED, TRAINED_COUNT, OptimiserChecker,
-                      action_probe, check_info, close, engine_options, rollout_case, rollout_raw_actions,
-                      saturated_share, synthetic_rows, trained_member)
+from _helpers import (ACTION_SPECS, ROLLOUT_SPECS, ROLLOUT_STEPS, TRAINED, TRAINED_COUNT,
+                      OptimiserChecker, action_probe, check_info, close, device_tree, engine_options, info_ratio,
+                      rollout_case, rollout_raw_actions, saturated_share, synthetic_rows, trained_member)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,17 +32,18 @@ def _population(specs, use_graph=True):
     from fqlpop import Population, PopulationConfig
     from fqlpop._lib import STATE_ADAM_M, STATE_ADAM_V
     s0 = specs[0]
-    assert all((s.H, s.B, s.D, s.A, s.kw, s.n_steps) == (s0.H, s0.B, s0.D, s0.A, s0.kw, s0.n_steps) for s in specs)
+    assert all((s.H, s.L, s.B, s.D, s.A, s.kw, s.n_steps) == (s0.H, s0.L, s0.B, s0.D, s0.A, s0.kw, s0.n_steps)
+               for s in specs)
     assert len({s.seed for s in specs}) == len(specs)
-    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * 4, batch_size=s0.B,
+    pc = PopulationConfig(obs_dim=s0.D, action_dim=s0.A, hidden_dims=(s0.H,) * s0.L, batch_size=s0.B,
                           use_graph=use_graph, **dict(s0.kw))
     seeds = [s.sampled[0] if s.sampled else 11 + i for i, s in enumerate(specs)]
     pop = Population(pc, [s.alpha for s in specs], seeds)
     for i, s in enumerate(specs):
         tm = trained_member(s)
-        pop.set_params(i, O.cast_tree(tm.params, np.float32))
-        pop.set_flat(i, pop.tree_to_flat(tm.opt["m"]), STATE_ADAM_M)
-        pop.set_flat(i, pop.tree_to_flat(tm.opt["v"]), STATE_ADAM_V)
+        pop.set_params(i, device_tree(pop, O.cast_tree(tm.params, np.float32)))
+        pop.set_flat(i, pop.tree_to_flat(device_tree(pop, tm.opt["m"])), STATE_ADAM_M)
+        pop.set_flat(i, pop.tree_to_flat(device_tree(pop, tm.opt["v"])), STATE_ADAM_V)
         pop.set_count(i, TRAINED_COUNT)
     return pop
 
@@ -51,11 +52,12 @@ def _state(pop):
     return [pop.get_flat(i, w) for i in range(pop.n) for w in (0, 1, 2)]
 
 
-def _run_parity(specs, use_graph=True):
+def _run_parity(specs, use_graph=True, report=None):
     """Step ``specs`` from their trained-like states on the oracle's batches and noises
     (injected, or for a sampled Spec drawn by the device sampler from the dataset) and check
     every step of every member against the oracle.  Returns (population, info of the last
-    step)."""
+    step).  ``report``: a dict that receives the worst info and moment errors as fractions of
+    REL's and MOMENT_REL's bounds, before anything is asserted."""
     pop = _population(specs, use_graph)
     members = [trained_member(s) for s in specs]
     sampled = bool(specs[0].sampled)
@@ -63,6 +65,10 @@ def _run_parity(specs, use_graph=True):
         pop.set_dataset(synthetic_rows(specs[0].sampled[1], specs[0].D, specs[0].A, 5))
     checks = [OptimiserChecker(pop, i, tm.cfg.lr, tm.cfg.tau) for i, tm in enumerate(members)]
     info = None
+    if report is None:
+        report = {}
+    report.update(info=0.0, moment=0.0)
+    errors = []
     for step in range(specs[0].n_steps):
         for c in checks:
             c.before()
@@ -75,8 +81,15 @@ def _run_parity(specs, use_graph=True):
         for i, tm in enumerate(members):
             params_o, opt_o, info_o = tm.steps[step]
             tag = f"{specs[i]} step {step} member {i}"
-            check_info(info[i], info_o, O.TRAIN_INFO_KEYS, tag)
-            checks[i].after(params_o, opt_o, step + 1, tag)
+            report["info"] = max(report["info"], info_ratio(info[i], info_o, O.TRAIN_INFO_KEYS))
+            for check in (lambda: check_info(info[i], info_o, O.TRAIN_INFO_KEYS, tag),
+                          lambda: checks[i].after(params_o, opt_o, step + 1, tag)):
+                try:   # every member is measured before the first miss is raised
+                    check()
+                except AssertionError as e:
+                    errors.append(str(e))
+            report["moment"] = max(report["moment"], checks[i].worst_moment)
+        assert not errors, "\n".join(errors)
     for i in range(len(specs)):
         assert pop.get_count(i) == TRAINED_COUNT + specs[0].n_steps
     return pop, info

@@ -121,13 +121,13 @@ def test_gradients_match_finite_differences_trained(kw, q_offset, net, key):
     _check_finite_differences(kw, q_offset, net, key)
 
 
-def _check_finite_differences(kw, q_offset, net, key):
+def _check_finite_differences(kw, q_offset, net, key, seed=3):
     # each net's own objective: critic <- critic loss (the actor's Q term reads
     # frozen critic params); bc <- BC loss (the Euler target is stop-gradient);
     # onestep <- actor loss, with normalize_q_loss's lambda held (it is a stop-gradient)
     cfg = small_cfg(alpha=3.0, **kw)
     rng = np.random.default_rng(7)
-    params = _state_params(cfg, 3, q_offset)
+    params = _state_params(cfg, seed, q_offset)
     batch, noise = O.make_batch(cfg, 8, rng), O.make_noise(cfg, 8, rng)
     # clip(a_pi) has a kink at +-1, where a central difference is not the gradient: probe on
     # the rows whose a_pi entries are all at least 1e-3 away from it
@@ -353,12 +353,29 @@ def test_trained_like_state_conditions(spec):
     q_agg = min each ensemble member is the minimum in at least 15 % of the rows; and the
     state is trained-like (target != critic in every leaf, moments non-zero except the
     target's)."""
+    _check_state_conditions(spec)
+
+
+def _config_space_specs():
+    from config_space_cases import CASES, TR_CASES, tr_spec
+    out = [pytest.param(s, id=f"{name}-{i}") for name, group in CASES.items() for i, s in enumerate(group)]
+    return out + [pytest.param(tr_spec(e, l), id=f"tr_e{e}_l{l}") for e, l in TR_CASES]
+
+
+@pytest.mark.parametrize("spec", _config_space_specs())
+def test_trained_like_state_conditions_config_space(spec):
+    """The same conditions on every state of tests/config_space_cases.py."""
+    _check_state_conditions(spec)
+
+
+def _check_state_conditions(spec):
     from _helpers import check_member_conditions, trained_member
     tm = trained_member(spec)
     check_member_conditions(tm)
+    head_bias = f"Dense_{spec.L}/bias"
     for k, v in tm.params["critic"].items():
         d = np.abs(tm.params["target_critic"][k] - v)
-        assert (d > 0).mean() > 0.99 and d.mean() >= 0.1 * np.abs(v - (spec.q_offset if k == "Dense_4/bias" else 0)).mean(), k
+        assert (d > 0).mean() > 0.99 and d.mean() >= 0.1 * np.abs(v - (spec.q_offset if k == head_bias else 0)).mean(), k
     for net in O.TRAINABLE:
         for k, m in tm.opt["m"][net].items():
             assert m.all() and (tm.opt["v"][net][k] > 0).all(), (net, k)
@@ -382,3 +399,121 @@ def test_trained_like_action_and_rollout_conditions():
         check_clamp_conditions(raw, f"sample_actions {spec}")
     for i, spec in enumerate(ROLLOUT_SPECS):
         check_clamp_conditions(rollout_raw_actions(i), f"rollout {spec}")
+
+
+# ---------------------------------------------------------------------------
+# the configuration space beyond small_cfg's four hidden layers, two Qs and five actions
+# (tests/config_space_cases.py runs the device there)
+# ---------------------------------------------------------------------------
+_MIN_KW = {"q_agg": "min", "normalize_q_loss": True}
+CONFIG_SPACE = {
+    "l1": {"hidden_dims": (16,)},
+    "l2": {"hidden_dims": (16, 16)},
+    "l10": {"hidden_dims": (16,) * 10},
+    "e1": {"num_qs": 1},
+    "e1_min": {"num_qs": 1, **_MIN_KW},
+    "e3": {"num_qs": 3},
+    "e3_min": {"num_qs": 3, **_MIN_KW},
+    "e4": {"num_qs": 4},
+    "e4_min": {"num_qs": 4, **_MIN_KW},
+    "a1": {"obs_dim": 3, "action_dim": 1},
+    "s2": {"flow_steps": 2},
+}
+
+
+def _config_space_q_offset(kw):
+    return 0.0 if kw.get("q_agg") == "min" else -40.0
+
+
+@pytest.mark.parametrize("name", list(CONFIG_SPACE))
+def test_gradients_match_torch_autograd_config_space(name):
+    """The oracle's hand-written backward against torch autograd at the trained-like state, at
+    the depths, ensemble sizes, head width and flow_steps the other checks never leave."""
+    pytest.importorskip("torch")
+    from oracle.fql_torch import grads_autograd
+    kw = CONFIG_SPACE[name]
+    cfg = small_cfg(**kw)
+    rng = np.random.default_rng(11)
+    p = O.trained_like_params(cfg, 2, q_offset=_config_space_q_offset(kw))
+    b, n = O.make_batch(cfg, 8, rng), O.make_noise(cfg, 8, rng)
+    loss, info, g = O.loss_and_grads(cfg, p, b, n)
+    l2, i2, g2 = grads_autograd(cfg, p, b, n)
+    assert abs(loss - l2) < 1e-10
+    for k in info:
+        assert abs(info[k] - i2[k]) < 1e-10, k
+    for net in O.NETS:
+        assert set(g[net]) == set(g2[net]) == set(O.leaf_order(cfg, net))
+        for k in g[net]:
+            assert g[net][k].shape == p[net][k].shape == g2[net][k].shape, (net, k)
+            assert np.allclose(g[net][k], g2[net][k], atol=1e-11, rtol=1e-9), (name, net, k)
+
+
+def _config_space_fd_cases():
+    for name, kw in CONFIG_SPACE.items():
+        L = len(kw.get("hidden_dims", (16,) * 4))
+        # one probe per net: the critic's first kernel (the whole backward chain), the BC
+        # actor's head, the one-step actor's first kernel
+        for net, key in (("critic", "Dense_0/kernel"), ("actor_bc_flow", f"Dense_{L}/kernel"),
+                         ("actor_onestep_flow", "Dense_0/kernel")):
+            yield pytest.param(kw, net, key, FD_STATE_SEED.get(name, 3), id=f"{name}-{net}")
+
+
+# with one action and eight rows, state 3 saturates no a_pi entry; state 8 saturates four
+FD_STATE_SEED = {"a1": 8}
+
+
+@pytest.mark.parametrize("kw,net,key,seed", list(_config_space_fd_cases()))
+def test_gradients_match_finite_differences_config_space(kw, net, key, seed):
+    _check_finite_differences(kw, _config_space_q_offset(kw), net, key, seed=seed)
+
+
+def _first_two_only(tm):
+    """critic/critic_loss and actor/q of ``tm``'s first step as an update would report them
+    that aggregates only the first two ensemble members, in the TD target and in the actor's Q
+    term (a plain restatement on the oracle's forwards)."""
+    cfg, p, b, n = tm.cfg, tm.params, tm.batches[0], tm.noises[0]
+    a_next = O.sample_actions(cfg, p, b["next_observations"], n["z_next"])
+    qt, _ = O.value_forward(cfg, p["target_critic"], b["next_observations"], a_next)
+    q_next = qt[:2].min(0) if cfg.q_agg == "min" else qt[:2].mean(0)
+    y = b["rewards"] + cfg.discount * b["masks"] * q_next
+    q, _ = O.value_forward(cfg, p["critic"], b["observations"], b["actions"])
+    a_pi = O.sample_actions(cfg, p, b["observations"], n["z_d"])
+    qpi, _ = O.value_forward(cfg, p["critic"], b["observations"], a_pi)
+    return ((q - y[None]) ** 2).mean(), qpi[:2].mean(0).mean(), qt, qpi
+
+
+@pytest.mark.parametrize("case", ["h512_e3_min", "h512_e4_min", "h512_e4", "h64_e4_min"])
+def test_more_than_two_qs_separate_a_two_q_aggregate(case):
+    """At num_qs 3 and 4 an update that aggregates only the first two ensemble members, as
+    every other parity test's E = 2 would let pass, moves critic/critic_loss (the TD target)
+    and actor/q (the actor's Q term) by at least 10x REL."""
+    from _helpers import REL, trained_member
+    from config_space_cases import CASES
+    for spec in CASES[case]:
+        tm = trained_member(spec)
+        info = tm.steps[0][2]
+        loss2, q2, qt, qpi = _first_two_only(tm)
+        # the restatement with every member is the oracle's own value
+        q_next = qt.min(0) if tm.cfg.q_agg == "min" else qt.mean(0)
+        assert np.isclose(qpi.mean(0).mean(), info["actor/q"], rtol=1e-12, atol=0)
+        assert not np.allclose(q_next, qt[:2].min(0) if tm.cfg.q_agg == "min" else qt[:2].mean(0))
+        for key, wrong in (("critic/critic_loss", loss2), ("actor/q", q2)):
+            right = float(info[key])
+            assert abs(right - wrong) >= 10 * (REL * max(abs(right), abs(wrong)) + 1e-6), (spec, key, right, wrong)
+
+
+def test_two_digit_layers_sort_by_name_not_by_layer():
+    """At ten hidden layers the flat state's leaf order (flax: sorted by name) puts Dense_10
+    before Dense_2: a flat vector assembled in layer order differs from the correct one."""
+    from _helpers import trained_member
+    from config_space_cases import CASES
+    tm = trained_member(CASES["h64_l10"][0])
+    for net in O.NETS:
+        names = O.leaf_order(tm.cfg, net)
+        assert names.index("Dense_10/kernel") < names.index("Dense_2/kernel")
+        by_layer = sorted(names, key=lambda k: (k.split("_")[0], int(k.split("_")[1].split("/")[0]), k))
+        assert by_layer != names and sorted(by_layer) == names
+        right = np.concatenate([tm.params[net][k].reshape(-1) for k in names])
+        wrong = np.concatenate([tm.params[net][k].reshape(-1) for k in by_layer])
+        assert right.shape == wrong.shape and (right != wrong).mean() > 0.5
+
